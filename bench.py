@@ -8,7 +8,8 @@ Prints ONE JSON line on rank 0: BASELINE.json's metric (images/s, whole job), pl
                 / measured launch time against the HBM peak (HIP events on the launch stream)
   cpu_baseline  the CPU oracle (oracle/, a port of the reference's forward) timed on this host's cores on a bounded
                 sample of the same model (rank 0, N = 1 only)
-Data is synthetic (uint8-range images, random labels), weights are random-init.
+Data is synthetic (uint8-range images, random labels), weights are random-init; both are seeded, so the same arguments give the
+same inputs on every run.  --dump-outputs DIR writes what the last timed step computed (dump_outputs) for comparing two builds.
 """
 import argparse
 import json
@@ -348,6 +349,9 @@ def main():
     ap.add_argument("--reserved-cus", default="auto",
                     help="compute units the chip-filling launches leave free for RCCL (multiple of 8; auto: 16 when N > 1, else 0)")
     ap.add_argument("--comm-dtype", default="fp32", choices=["fp32", "bf16"], help="wire format of the gradient buckets")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, a fixed sample of the updated parameters and of "
+                         "their gradients) as DIR/<name>.npy, for output-by-output comparison of two builds (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -453,7 +457,7 @@ def main():
     if args.use_checkpoint:
         wl = dict(wl, cfg=dict(wl["cfg"], use_checkpoint=True), name=wl["name"] + " use_checkpoint")
     ctx = types.SimpleNamespace(args=args, wl=wl, dev=dev, world=world, rank=rank, shared_gpu=shared_gpu)
-    res = run_workload(ctx, args.dtype, args.steps, args.warmup, timing=not args.no_kernel_timing)
+    res = run_workload(ctx, args.dtype, args.steps, args.warmup, timing=not args.no_kernel_timing, dump_dir=args.dump_outputs)
     elapsed = res.elapsed
 
     if rank == 0:
@@ -462,7 +466,7 @@ def main():
             "metric": "images/sec fwd+bwd, HEAL-SWIN nside=256 seg, batch=8 at 1/2/4/8 MI355X",
             "value": images / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong" if args.strong_scaling else "weak", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
+            "dtype": args.dtype, "data": "synthetic", "dumped_outputs": res.dumped,
             "config": {"workload": wl["name"], "batch_per_gpu": args.batch, "global_batch": args.batch * world,
                        "parallelism": f"dp{world}",
                        "step": ("drop-in (INTEGRATION.md level 1): module swapped only -- fwd, nn.CrossEntropyLoss on the logits, bwd with autograd's "
@@ -807,18 +811,47 @@ class _NoSink:
         pass
 
 
-def run_workload(ctx, dtype_name, steps, warmup, timing):
+DUMP_SAMPLE = 4 << 20  # elements of the parameter / gradient samples of --dump-outputs (2 x 16 MB in float32)
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step receives from its last call -- the loss and the updated parameters with their gradients --
+    as out_dir/<name>.npy.  Parameters and gradients (all of them, flattened in model.parameters() order) are sampled at the same
+    DUMP_SAMPLE positions, drawn from a fixed seed, so that two builds of the same workload write comparable files."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad.detach().reshape(-1).float() if p.grad is not None else torch.zeros(p.numel(), device=p.device))
+                        for p in params])
+    total = flat_p.numel()
+    if total <= DUMP_SAMPLE:
+        idx = torch.arange(total)
+    else:
+        idx = torch.randint(0, total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    idx = idx.to(flat_p.device)
+    arrays = {"loss": np.array([float(loss.item())], dtype=np.float64),
+              "params_sample": flat_p[idx].cpu().numpy().astype(np.float32),
+              "grads_sample": flat_g[idx].cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "params_total": total, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
+def run_workload(ctx, dtype_name, steps, warmup, timing, dump_dir=None):
     """Build the model / optimizer / gradient exchange for `dtype_name`, run `warmup` untimed and `steps` timed steps
-    (barrier + synchronize on both sides, MAX over ranks) and release everything again."""
+    (barrier + synchronize on both sides, MAX over ranks) and release everything again.  With `dump_dir`, rank 0 writes what the
+    last timed step computed there (dump_outputs)."""
     undo = []  # process-wide registrations of this run (the library's replay counter): withdrawn on EVERY way out, a failed
     try:       # capture included -- the companions swallow exceptions and carry on in this process
-        return _run_workload(ctx, dtype_name, steps, warmup, timing, undo)
+        return _run_workload(ctx, dtype_name, steps, warmup, timing, undo, dump_dir)
     finally:
         for fn in reversed(undo):
             fn()
 
 
-def _run_workload(ctx, dtype_name, steps, warmup, timing, undo):
+def _run_workload(ctx, dtype_name, steps, warmup, timing, undo, dump_dir=None):
     import gc
 
     import torch.distributed as dist
@@ -989,6 +1022,7 @@ def _run_workload(ctx, dtype_name, steps, warmup, timing, undo):
     sync()
     elapsed = time.perf_counter() - t0
     timings, ops.KERNEL_TIMINGS = ops.KERNEL_TIMINGS, None
+    dumped = dump_outputs(dump_dir, model, loss) if (dump_dir and rank == 0) else None  # before anything below steps again
     rccl = None
     if world > 1:
         assert dist.get_world_size() == world == args.gpus
@@ -1040,7 +1074,7 @@ def _run_workload(ctx, dtype_name, steps, warmup, timing, undo):
                 "gemm_policy": gemm_policy,
                 "exchange": ("torch.nn.parallel.DistributedDataParallel (its own buckets and hooks)" if drop_in else
                              f"{args.comm_dtype} wire format of fp32 flat buckets, async all-reduce launched from gradient hooks during backward")}
-    res = types.SimpleNamespace(elapsed=elapsed, loss=float(loss.item()), timings=timings if rank == 0 else None, rccl=rccl,
+    res = types.SimpleNamespace(elapsed=elapsed, loss=float(loss.item()), timings=timings if rank == 0 else None, rccl=rccl, dumped=dumped,
                                 params_m=round(sum(p.numel() for p in model.parameters()) / 1e6, 2),
                                 peak_gb=round(torch.cuda.max_memory_allocated(dev) / 1e9, 1))
     dp.remove()

@@ -243,3 +243,25 @@ def test_bench_self_launches_multi_rank():
     assert out["rccl"]["rccl_ranks"] == 2 and len(out["rccl"]["allreduce_ms_per_step_standalone_per_rank"]) == 2
     assert out["roofline"]["bound"] == "hbm" and out["roofline"]["frac"] > 0 and out["roofline"]["mfma"]["frac"] > 0
     assert len(out["rccl"]["step_ms_per_rank"]) == 2
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: after the timed steps the last step's loss and a fixed sample of the updated parameters and their
+    gradients land in DIR as float32 / float64 .npy files (at most 64 MB), and the line reports the requested number of timed steps."""
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny",
+           "--no-companions", "--no-cpu-baseline", "--no-fp32-companion", "--no-graph-companion", "--no-pmc-traffic",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    arrays = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert set(arrays) == {"loss", "params_sample", "grads_sample"} == set(out["dumped_outputs"]["arrays"])
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert float(arrays["loss"][0]) == out["config"]["final_loss"]
+    n = min(out["dumped_outputs"]["params_total"], 4 << 20)
+    assert arrays["params_sample"].shape == arrays["grads_sample"].shape == (n,) and np.abs(arrays["grads_sample"]).max() > 0

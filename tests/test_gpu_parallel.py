@@ -241,14 +241,19 @@ def test_torch_ddp_wrapper_with_torch_adam_equals_single_process(dtype_name):
 
 
 def test_bench_script_eight_ranks_on_one_gpu():
-    """The first real 8-GPU run must not be the first time eight ranks meet: bench.py --gpus 8 as the driver launches it, the eight
-    ranks sharing this box's GPU over gloo at the tiny size, bf16 wire format.  Checks what a mis-wired exchange would break:
+    """The first real 8-GPU run must not be the first time eight ranks meet: bench.py --gpus 8 as the driver launches it, one rank
+    per GPU over RCCL at the tiny size, bf16 wire format.  Checks what a mis-wired exchange would break:
     every rank arrives (max-over-ranks timing of 8 entries), the bucket order / hooks do not deadlock, the GEMM policy is agreed by
     all ranks (a MAX all-reduce: one dissenting rank would hang the next collective), the timeline diagnostic is there, and the
-    line says rccl_ranks == 8.  The strong-scaling reading (global batch 8 -> 1 per rank) runs the same way."""
+    line says rccl_ranks == 8.  The strong-scaling reading (global batch 8 -> 1 per rank) runs the same way.
+    Eight ranks need eight GPUs, one rank each: eight processes (plus this one) must not share one GPU."""
+    found = torch.cuda.device_count()
+    if found < 8:
+        pytest.skip(f"needs 8 GPUs, found {found}")
     import json
     import subprocess
-    env = dict(os.environ, HS_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("HS_BENCH_SHARED_GPU", None)
     for extra, per_gpu, scaling in ((["--batch", "1"], 1, "weak"), (["--batch", "8", "--strong-scaling"], 1, "strong")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",

@@ -157,6 +157,9 @@ def test_own_gemm_policy_class_rule_tuner_picks_and_overrides(monkeypatch):
     bf = torch.bfloat16
     monkeypatch.setattr(ops, "OWN_GEMM", "auto")
     monkeypatch.setattr(ops.RT, "prefer_own_gemm", False)
+    # the class rule on its own: no trial and no pick left behind by earlier GPU tests in this process, even where a GPU is visible
+    monkeypatch.setattr(G, "GEMM_TUNER", G.GemmTuner())
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     assert ops.own_gemm_ok(_lib.HS_EPI_BIAS, 384, 96, bf) and ops.own_gemm_ok(_lib.HS_EPI_BIAS, 128, 512, bf)  # class rule: narrow / short
     assert not ops.own_gemm_ok(_lib.HS_EPI_BIAS, 512, 2048, bf) and not ops.own_gemm_ok(_lib.HS_EPI_BIAS, 1536, 512, bf)
     assert not ops.own_gemm_ok(_lib.HS_EPI_BIAS, 1152, 384, bf, m=65536)  # (no GPU here: no trial, the class rule answers)
