@@ -11,6 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libhealswin.so")
 
 HS_F32, HS_BF16 = 0, 1
+HS_PRED_LABELS, HS_PRED_ROWS16 = 2, 4
 HS_ATTN_COSINE = 1
 HS_ATTN_FORCE_VALU = 2
 HS_ATTN_RESIDUAL = 4
@@ -60,6 +61,10 @@ _SIGNATURES = {
     "hs_ln_head_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr],
     "hs_sample_bilinear_u8": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_sample_mask_u8": [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr],
+    "hs_hp_interp_weights_nest": [c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "hs_backproject_labels": [c_ptr, c_int, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr],
+    "hs_backproject_image": [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "hs_seg_confusion": [c_ptr, c_int, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     "hs_gelu_fwd": [c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_gelu_bwd": [c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_residual_drop": [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],

@@ -332,4 +332,116 @@ int hs_pix2ang_nest(int nside, int64_t first, int64_t count, double* theta, doub
     return HS_OK;
 }
 
+
+/* healpy.pixelfunc.get_interp_weights(nside, theta, phi, nest=True) (reference data/segmentation/project_on_s2.py:95,
+ * and through get_interp_val :313), which is the HEALPix C++ T_Healpix_Base::get_interpol: the rings ir1 = ring_above(z) and
+ * ir2 = ir1 + 1 bracket the direction; on each, the two ring pixels around phi get weights linear in phi; the two pairs are
+ * then weighted linearly in theta between the ring centres.  Above the first ring (ir1 == 0) and below the last
+ * (ir2 == 4 nside) the missing ring is replaced by the four polar pixels with weight (1 - wtheta) / 4 each.  Indices are
+ * converted to nested order.  pix [host] int64[4][n], wgt [host] f64[4][n] (healpy's layout).
+ * phi is reduced to [0, 2 pi) with HEALPix's fmodulo first (healpy normalises its pointing before the call); theta must
+ * lie in [0, pi] (healpy raises otherwise). */
+int hs_hp_interp_weights_nest(int nside, const double* theta, const double* phi, int64_t n, int64_t* pix, double* wgt) {
+    if (int st = check_nside(nside)) return st;
+    HS_CHECK_ARG(nside <= (1 << 29), "nside %d above HEALPix's limit 2^29", nside);
+    HS_CHECK_ARG(theta && phi && pix && wgt && n >= 0, "null pointer or negative count");
+    const int64_t ns = nside, nl4 = 4 * ns, npix = 12 * ns * ns, ncap = 2 * ns * (ns - 1);
+    const double fact2 = 4.0 / (double)npix, fact1 = (double)(ns << 1) * fact2, twopi = 2.0 * M_PI;
+    // T_Healpix_Base::get_ring_info2: first pixel, pixel count, centre colatitude and phase shift of ring `ring` (1 .. 4 nside - 1)
+    auto ring_info = [&](int64_t ring, int64_t& sp, int64_t& nr, double& th, bool& shifted) {
+        const int64_t north = ring > 2 * ns ? nl4 - ring : ring;
+        if (north < ns) {
+            const double tmp = (double)(north * north) * fact2;
+            th = std::atan2(std::sqrt(tmp * (2.0 - tmp)), 1.0 - tmp);
+            nr = 4 * north;
+            shifted = true;
+            sp = 2 * north * (north - 1);
+        } else {
+            th = std::acos((double)(2 * ns - north) * fact1);
+            nr = nl4;
+            shifted = ((north - ns) & 1) == 0;
+            sp = ncap + (north - ns) * nr;
+        }
+        if (north != ring) {
+            th = M_PI - th;
+            sp = npix - sp - nr;
+        }
+    };
+    // the two pixels of a ring around phi and the weight of the second
+    auto bracket = [&](int64_t ring, double ph, int64_t* p, double* w, double& th) {
+        int64_t sp, nr;
+        bool shifted;
+        ring_info(ring, sp, nr, th, shifted);
+        const double dphi = twopi / (double)nr, half = shifted ? 0.5 : 0.0;
+        const double tmp = ph / dphi - half;
+        int64_t i1 = tmp < 0 ? (int64_t)tmp - 1 : (int64_t)tmp;
+        const double w1 = (ph - ((double)i1 + half) * dphi) / dphi;
+        int64_t i2 = i1 + 1;
+        if (i1 < 0) i1 += nr;
+        if (i2 >= nr) i2 -= nr;
+        p[0] = sp + i1;
+        p[1] = sp + i2;
+        w[0] = 1.0 - w1;
+        w[1] = w1;
+    };
+    for (int64_t k = 0; k < n; ++k) {
+        const double t = theta[k];
+        HS_CHECK_ARG(t >= 0.0 && t <= M_PI, "theta[%lld] = %g outside [0, pi]", (long long)k, t);
+        double ph = phi[k];
+        HS_CHECK_ARG(std::isfinite(ph), "phi[%lld] is not finite", (long long)k);
+        if (ph >= 0.0) {  // HEALPix fmodulo(phi, 2 pi)
+            if (ph >= twopi) ph = std::fmod(ph, twopi);
+        } else {
+            ph = std::fmod(ph, twopi) + twopi;
+            if (ph == twopi) ph = 0.0;
+        }
+        const double z = std::cos(t), az = std::fabs(z);
+        int64_t ir1;  // T_Healpix_Base::ring_above
+        if (az <= 2.0 / 3.0) {
+            ir1 = (int64_t)((double)ns * (2.0 - 1.5 * z));
+        } else {
+            const int64_t r = (int64_t)((double)ns * std::sqrt(3.0 * (1.0 - az)));
+            ir1 = z > 0 ? r : nl4 - r - 1;
+        }
+        const int64_t ir2 = ir1 + 1;
+        int64_t p[4] = {0, 0, 0, 0};
+        double w[4] = {0, 0, 0, 0}, th1 = 0.0, th2 = 0.0;
+        if (ir1 > 0) bracket(ir1, ph, p, w, th1);
+        if (ir2 < nl4) bracket(ir2, ph, p + 2, w + 2, th2);
+        if (ir1 == 0) {
+            const double wtheta = t / th2, fac = (1.0 - wtheta) * 0.25;
+            w[2] *= wtheta;
+            w[3] *= wtheta;
+            w[0] = fac;
+            w[1] = fac;
+            w[2] += fac;
+            w[3] += fac;
+            p[0] = (p[2] + 2) & 3;
+            p[1] = (p[3] + 2) & 3;
+        } else if (ir2 == nl4) {
+            const double wtheta = (t - th1) / (M_PI - th1), fac = wtheta * 0.25;
+            w[0] *= 1.0 - wtheta;
+            w[1] *= 1.0 - wtheta;
+            w[0] += fac;
+            w[1] += fac;
+            w[2] = fac;
+            w[3] = fac;
+            p[2] = ((p[0] + 2) & 3) + npix - 4;
+            p[3] = ((p[1] + 2) & 3) + npix - 4;
+        } else {
+            const double wtheta = (t - th1) / (th2 - th1);
+            w[0] *= 1.0 - wtheta;
+            w[1] *= 1.0 - wtheta;
+            w[2] *= wtheta;
+            w[3] *= wtheta;
+        }
+        for (int m = 0; m < 4; ++m) {
+            const Xyf c = ring_to_xyf(ns, p[m]);
+            pix[m * n + k] = xyf_to_nest(ns, c.ix, c.iy, c.face);
+            wgt[m * n + k] = w[m];
+        }
+    }
+    return HS_OK;
+}
+
 }  // extern "C"

@@ -528,6 +528,49 @@ int hs_sample_mask_u8(const void* mask, int batch, int height, int width, const 
                       int background, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Evaluation: HEALPix predictions scored and back-projected onto the fisheye image plane (heal_swin_amd/evaluation.py).
+ * The tables of a calibration (nearest pixel, four interpolation pixels and weights per image-plane pixel) are built once on
+ * the host; the per-batch work is the three gathers below.
+ *   hs_hp_interp_weights_nest  [host] healpy.pixelfunc.get_interp_weights(nside, theta, phi, nest=True)
+ *                       (data/segmentation/project_on_s2.py:95, :313; HEALPix C++ get_interpol): theta, phi [host] f64[n];
+ *                       pix [host] i64[4][n], wgt [host] f64[4][n] in healpy's order.  phi is reduced to [0, 2 pi) first
+ *                       (HEALPix fmodulo); theta outside [0, pi], NaN or an infinite phi -> HS_ERR_INVALID_ARG.
+ * Predictions `pred` [dev] are logits (pred_kind HS_F32 / HS_BF16, n_classes <= 64, element (b, c, pixel) at
+ * b*stride_b + c*stride_k + pixel*stride_p as in hs_seg_ce_fwd) whose class is torch.max(logits, 1)'s index (the first
+ * maximum; a NaN counts as the maximum), or class ids (pred_kind HS_PRED_LABELS, uint8, element (b, pixel) at
+ * b*stride_b + pixel*stride_p; stride_k unused).  npix = base_pix nside^2 HEALPix pixels per image; a table entry >= npix
+ * (a pixel of the base pixels the model does not see) is "uncovered".
+ *   hs_backproject_labels  project_hp_mask_back (:319-341): out [dev] u8[batch, n_out] = class at nearest[i], or
+ *                       `background` (the reference's s2_bkgd_class) where uncovered.  nearest [dev] i32[n_out].
+ *   hs_backproject_image   project_hp_img_back (:302-316, healpy get_interp_val): hp_img [dev] u8[planes, npix];
+ *                       idx [dev] i32[4][n_out], wgt [dev] f64[4][n_out]; out [dev] f64[planes, n_out] =
+ *                       ((w0 v0 + w1 v1) + w2 v2) + w3 v3 in float64 without FMA, uncovered pixels read 255.0 (the
+ *                       reference's fill): bit-exact.
+ *   hs_seg_confusion    the confusion matrix of torchmetrics 0.3.2 (bincount(target * K + pred), rows = target, columns =
+ *                       prediction; models_lightning/segmentation/model_lightning_swin_hp.py:47-55), ADDED into conf [dev]
+ *                       i64[n_classes, n_classes].  nearest == NULL: HEALPix domain, target [dev] u8[batch, npix].  Otherwise
+ *                       image plane (evaluation/hp_pred_writers.py:110-222): the prediction of pixel i is read at nearest[i],
+ *                       target [dev] u8[batch, n_out], and uncovered pixels count as class `uncovered` (back-projected
+ *                       metrics) or are skipped when uncovered = -1 (evaluation/custom_metrics.py:25-59, HPMaskedIoU).
+ *                       Pixels with target >= n_classes (or a label prediction >= n_classes) are not counted but added to
+ *                       bad [dev] i64[2] (targets, predictions), on which the caller raises as torchmetrics does.  Integer
+ *                       atomics only: exact and deterministic.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_PRED_LABELS 2
+#define HS_PRED_ROWS16 4 /* or'ed into HS_F32 / HS_BF16: stride_k == 1 and every pixel's logits row is 16-byte aligned and may be
+                            read up to the next multiple of 16 bytes (the model's padded rows); the rows are then read with
+                            16-byte loads */
+int hs_hp_interp_weights_nest(int nside, const double* theta, const double* phi, int64_t n, int64_t* pix, double* wgt);
+int hs_backproject_labels(const void* pred, int pred_kind, int64_t batch, int64_t npix, int n_classes, int64_t stride_b,
+                          int64_t stride_k, int64_t stride_p, const int32_t* nearest, int64_t n_out, int background, uint8_t* out,
+                          void* stream);
+int hs_backproject_image(const uint8_t* hp_img, int64_t planes, int64_t npix, const int32_t* idx, const double* wgt, int64_t n_out,
+                         double* out, void* stream);
+int hs_seg_confusion(const void* pred, int pred_kind, int64_t batch, int64_t npix, int n_classes, int64_t stride_b, int64_t stride_k,
+                     int64_t stride_p, const int32_t* nearest, int64_t n_out, const uint8_t* target, int uncovered, int64_t* conf,
+                     int64_t* bad, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decoder tail: LayerNorm(C) of FinalPatchExpand_X4 + the 1x1 class head in one pass, so that the normalised
  * [B, 4 N0, C] tensor is never written.  Replaces `self.norm(x)` (models_torch/swin_hp_transformer.py:448-452) followed by
  * `self.output(x)` (:756-761, :785-788) and their backward.  bf16 rows, C in {64, 96, ..., 256}, <= 16 classes.
