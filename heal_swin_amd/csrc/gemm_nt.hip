@@ -131,20 +131,32 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_nt_kernel(GemmParams p) 
     static_assert(!ALIAS || NW * 4096 <= STAGE, "patches do not fit a stage buffer");
     constexpr bool HAS_IN = EPI == EPI_DGELU || EPI == EPI_RESID;
     constexpr bool RING = HS_GEMM_EPI_RING && HAS_IN && ALIAS && TM == 4 && TN == 2 && STAGE >= NW * 8192;
-#ifdef HS_GEMM_TRACE
-    // (the three-stage 256 x 128 tile has no room for the event buffers beside the bias slots: not traced)
-    constexpr int TRACE_LDS = NSTAGE * STAGE + (ALIAS ? 0 : NW * 4096) + 2048 + NW * kTraceCap * 8 <= 163840 ? NW * kTraceCap * 8 : 0;
-#else
-    constexpr int TRACE_LDS = 0;
-#endif
-    // LBIAS: the tile's BN bias values travel global -> LDS by one DMA piece of wave 0 when the ISSUE cursor enters the tile (two 1-KB
-    // slots by tile parity behind the stages) and the epilogue reads them with ds_read_b128.  A global load at the top of the
+    // LBIAS: the tile's BN bias values travel global -> LDS by one DMA piece of wave 0 when the ISSUE cursor enters the tile (1-KB
+    // slots behind the stages) and the epilogue reads them with ds_read_b128.  A global load at the top of the
     // epilogue is the youngest entry of the wave's in-order vmcnt queue: on the DMA-issuing waves it waited for the whole first
     // k-step of the NEXT tile (64 KB from L2 / HBM) before row block 0 could start -- 3700 cycles per tile on the waves every
     // barrier then waits for (profiles/archive_r01_r04/r03_gemm_pass_overlap.txt: row block 0 8582 cycles on wave 0, 4878 on wave 7).
     // (Not on the 128 x 128 tile: its two workgroups per CU use all 160 KB already.)
+    // Slot invariant: NSLOT = NSTAGE + 1 slots, taken by the workgroup's tile counter modulo NSLOT.  The bias of the tile that holds
+    // k-step s + NSTAGE is issued in the iteration that computes step s, before that iteration's epilogue; a tile spans >= 1 k-step,
+    // so the live tiles are the computed one and at most NSTAGE after it -- NSTAGE + 1 slots.  Tile T + NSLOT, the next user of T's
+    // slot, starts >= NSLOT k-steps after T, so its bias is issued in an iteration after the one that ends with epilogue(T), behind
+    // that iteration's barrier: every wave's ds_read of the slot has returned (lds_bias waits for lgkmcnt(0)).  With two slots by
+    // parity, nk <= NSTAGE - 1 k-steps per tile let tile T + 2 overwrite T's bias before epilogue(T) (tests/test_gpu_gemm_stream.py).
+    // Arrival: wave 0 issues a tile's bias piece right before the operand pieces of the tile's first k-step, in the same in-order
+    // vmcnt queue; the main loop's wait for those pieces (before the barrier that precedes the step's MFMAs) covers the bias, so the
+    // epilogue needs no wait of its own.
     constexpr bool LBIAS = ALIAS && EPI != EPI_DGELU;
-    constexpr int BIAS_OFF = NSTAGE * STAGE + (ALIAS ? 0 : NW * 4096), BIAS_LDS = LBIAS ? 2048 : 0;
+    constexpr int NSLOT = NSTAGE + 1;
+    static_assert(BN * 4 <= 1024, "a bias slot holds one 1-KB DMA piece");
+    constexpr int BIAS_OFF = NSTAGE * STAGE + (ALIAS ? 0 : NW * 4096), BIAS_LDS = LBIAS ? NSLOT * 1024 : 0;
+#ifdef HS_GEMM_TRACE
+    // (the three-stage 256 x 128 tile has no room for the event buffers beside the bias slots: not traced)
+    constexpr int TRACE_LDS = BIAS_OFF + BIAS_LDS + NW * kTraceCap * 8 <= 163840 ? NW * kTraceCap * 8 : 0;
+#else
+    constexpr int TRACE_LDS = 0;
+#endif
+    static_assert(BIAS_OFF + BIAS_LDS + TRACE_LDS <= 163840, "LDS of one workgroup exceeds 160 KB");
     __shared__ __attribute__((aligned(16))) unsigned char smem[BIAS_OFF + BIAS_LDS + TRACE_LDS];  // stages (+ epilogue patches) (+ bias slots)
 
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
@@ -194,7 +206,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_nt_kernel(GemmParams p) 
     int a_off[AJ], b_off[BJ];  // byte offset of this lane's (row, chunk) inside the tile, k-step 0
     int kseg = 0;              // bytes of a row of the current segment
     int a_ld32 = 0, b_ld32 = 0;  // (FAST) bytes of 32 operand rows
-    int par_i = 0;               // (LBIAS) slot the next tile's bias goes to
+    int slot_i = 0;              // (LBIAS) slot the next tile's bias goes to
     __amdgpu_buffer_rsrc_t rbias = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, p.bias ? p.n * 4 : 0, 0x00020000);
     auto retarget = [&](int id, bool s2, bool enter) {
         const int tm = id / p.tiles_n, tn = id - tm * p.tiles_n;
@@ -204,9 +216,9 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_nt_kernel(GemmParams p) 
             if (enter) {
                 // lanes beyond the tile's BN floats (and columns beyond n) read outside the descriptor: zeros
                 if (wave == 0)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rbias, (lds_void*)(smem + BIAS_OFF + par_i * 1024), 16,
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rbias, (lds_void*)(smem + BIAS_OFF + slot_i * 1024), 16,
                                                              lane * 4 < BN ? (uint32_t)(lane * 16) : kOob, n0 * 4, 0, 0);
-                par_i ^= 1;
+                slot_i = slot_i + 1 == NSLOT ? 0 : slot_i + 1;
             }
         }
         const uint16_t* ap = s2 ? p.a2 : p.a;
@@ -391,7 +403,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_nt_kernel(GemmParams p) 
     // odd t swap register halves
     const uint32_t own_out_rel = wave * 4096 + l31 * 128 + 8 * (half ^ ((l31 >> 3) & 1));
     const uint32_t row_rel = wave * 4096 + (lane >> 3) * 128 + (((lane & 7) ^ (lane >> 3)) << 4);  // + t * 1024: row lane/8 + 8 t
-    auto epilogue = [&](int id, int buf_done, int par_c) {
+    auto epilogue = [&](int id, int buf_done, int slot_c) {
         const uint32_t patch_off = ALIAS ? buf_done * STAGE : NSTAGE * STAGE;  // byte offset of the patch area inside smem
         TR(10);
         if (ALIAS) __builtin_amdgcn_s_barrier();  // every wave is done reading the stage buffer the patches live in
@@ -419,7 +431,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_nt_kernel(GemmParams p) 
         float4 bias4[TJ][4];
         // (LBIAS: a column block's four float4 are read from the LDS slot where they are used -- 4 broadcast reads per block instead of
         // 32 registers held across the pass, which the RESID epilogue of the 128 x 64 wave tile does not have)
-        const uint32_t baddr = lds0 + BIAS_OFF + par_c * 1024 + (wn * (BN / WN) + jh * 64 + 4 * half) * 4;
+        const uint32_t baddr = lds0 + BIAS_OFF + slot_c * 1024 + (wn * (BN / WN) + jh * 64 + 4 * half) * 4;
         auto lds_bias = [&](int j, float4 (&b)[4]) {
             u32x4 bq[4];
 #pragma unroll
@@ -657,7 +669,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_nt_kernel(GemmParams p) 
     const int stride = p.blocks_per_xcd;
     int id_i = id0, ks_i = 0;  // next step to issue
     int id_c = id0, ks_c = 0;  // step being computed
-    int par_c = 0;             // (LBIAS) slot that holds the bias of the tile being computed
+    int slot_c = 0;            // (LBIAS) slot that holds the bias of the tile being computed
     auto advance_issue = [&]() {
         ++ks_i;
         if (ks_i == nk) {
@@ -727,8 +739,8 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) gemm_nt_kernel(GemmParams p) 
         buf = buf + 1 == NSTAGE ? 0 : buf + 1;
         buf_free = buf_free + 1 == NSTAGE ? 0 : buf_free + 1;
         if (last) {
-            epilogue(id_c, buf_done, par_c);
-            par_c ^= 1;
+            epilogue(id_c, buf_done, slot_c);
+            slot_c = slot_c + 1 == NSLOT ? 0 : slot_c + 1;
             drained = true;
             ks_c = 0;
             id_c += stride;

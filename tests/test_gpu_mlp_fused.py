@@ -13,6 +13,9 @@ from _util import GRAD_TOL, TOL, assert_close
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF = torch.bfloat16
+# 32-row tiles over min(tiles, usable CUs) persistent workgroups: >= 3 tiles on every workgroup (4 on some), the double buffer
+# carried into a third and fourth tile
+MULTI_TILE_ROWS = 3 * 256 * 32 + 96
 
 
 def _L():
@@ -51,7 +54,7 @@ def _oracle_fwd(t, ln=True, residual=True):
 
 
 @pytest.mark.parametrize("C", [96, 128])
-@pytest.mark.parametrize("rows", [32, 96, 8192 + 64])
+@pytest.mark.parametrize("rows", [32, 96, 8192 + 64, MULTI_TILE_ROWS])
 @pytest.mark.parametrize("ln,residual,keep", [(True, True, True), (True, True, False), (False, False, True), (False, True, True)])
 def test_mlp_fused_forward_vs_oracle(C, rows, ln, residual, keep):
     L = _L()
@@ -84,7 +87,7 @@ def test_mlp_fused_forward_vs_oracle(C, rows, ln, residual, keep):
 
 
 @pytest.mark.parametrize("C", [96, 128])
-@pytest.mark.parametrize("rows", [32, 4096 + 32])
+@pytest.mark.parametrize("rows", [32, 4096 + 32, MULTI_TILE_ROWS])
 @pytest.mark.parametrize("with_res", [False, True])
 def test_mlp_fused_backward_vs_oracle(C, rows, with_res):
     """dh = (dy W2) * gelu'(h), dn = dh W1 against the oracle's autograd through linear / gelu on the same saved h."""
@@ -111,6 +114,21 @@ def test_mlp_fused_backward_vs_oracle(C, rows, with_res):
     tag = f"mlp_fused bwd C={C} rows={rows}"
     assert_close(dh, dh_ref, TOL[BF], tag + " dh")
     assert_close(dn, dn_ref, TOL[BF], tag + " dn")
+
+
+@pytest.mark.parametrize("direction", ["forward", "backward"])
+def test_mlp_fused_multi_tile_with_reserved_cus(direction):
+    """The multi-tile cases at hs_set_reserved_cus(16): 240 workgroups, a different tile -> workgroup assignment."""
+    lib = _L().lib
+    prev = int(lib.hs_get_reserved_cus())
+    try:
+        _L().check(lib.hs_set_reserved_cus(16), "hs_set_reserved_cus")
+        if direction == "forward":
+            test_mlp_fused_forward_vs_oracle(96, MULTI_TILE_ROWS, True, True, True)
+        else:
+            test_mlp_fused_backward_vs_oracle(128, MULTI_TILE_ROWS, True)
+    finally:
+        lib.hs_set_reserved_cus(prev)
 
 
 @pytest.mark.parametrize("C", [96, 128])
