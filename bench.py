@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the HEAL-SWIN hot path (fwd + loss + bwd + gradient exchange + Adam step).
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 Prints ONE JSON line on rank 0: BASELINE.json's metric (images/s, whole job), plus
   roofline      fused shift+window-attention kernels (fwd + bwd launches of the timed steps), algorithmic bytes
                 / measured launch time against the HBM peak (HIP events on the launch stream)
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  Everything that takes runs of
+its own is measured with --full only (N = 1 unless noted):
+  fp32, depth_fp32, drop_in, use_checkpoint, graph_replay, companions
+                the same step in other precisions, launch modes and trainer wirings, and the other BASELINE workloads
+  roofline      .module: the WindowAttention module timed standalone; .traffic: measured by rocprofv3 counter passes (a
+                plain run looks it up in profiles/)
   cpu_baseline  the CPU oracle (oracle/, a port of the reference's forward) timed on this host's cores on a bounded
-                sample of the same model (rank 0, N = 1 only)
+                sample of the same model (rank 0)
+  rccl          (N > 1) the standalone all-reduce time of the gradient buckets and one step's bucket timeline
 Data is synthetic (uint8-range images, random labels), weights are random-init; both are seeded, so the same arguments give the
 same inputs on every run.  --dump-outputs DIR writes what the last timed step computed (dump_outputs) for comparing two builds.
 """
@@ -139,7 +146,7 @@ def pmc_traffic_per_launch(attn_agg, records=None):
         if not os.path.exists(path):
             return None, None
         records = json.load(open(path))["records"]
-        source = "profiles/r04b_attn_pmc_hbm_traffic.json (committed rocprofv3 --pmc passes of the same kernels and shapes; looked up: rocprofv3 unavailable or failed in this run)"
+        source = "profiles/r04b_attn_pmc_hbm_traffic.json (committed rocprofv3 --pmc passes of the same kernels and shapes; looked up: no counter passes in this run, or rocprofv3 unavailable or failed)"
     table = _traffic_table(records)
     tot, n = 0.0, 0
     for tag, a in attn_agg.items():
@@ -314,6 +321,9 @@ def main():
     ap.add_argument("--workload", default="B256", choices=list(WORKLOADS))
     ap.add_argument("--batch", type=int, default=8, help="images per GPU (weak scaling)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own beside the headline (companion lines, roofline.module, rocprofv3 "
+                         "traffic passes, cpu_baseline, N > 1: standalone exchange timing); the --no-* options below trim such a run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--kernel-table", action="store_true", help="print the per-shape table of the event-timed launches to stderr")
@@ -421,8 +431,9 @@ def main():
         torch.cuda.tunable.set_max_tuning_iterations(int(os.environ.get("HS_TUNE_ITERS", "200")))
         torch.cuda.tunable.set_rotating_buffer_size(int(os.environ.get("HS_TUNE_ROTATE_MB", "512")))
     elif os.path.exists(tuned) and not args.no_tuned_gemm:
-        # one results file per process: the headline workload's picks plus those of the companions this run will execute (the
-        # fp32 re-run of the same workload, the fp32 depth-head config), merged into a scratch file
+        # one results file per process: the headline workload's picks plus those of the companions a --full run executes (the
+        # fp32 re-run of the same workload, the fp32 depth-head config), merged into a scratch file -- in plain runs too, so that
+        # the headline's GEMM selection does not depend on --full
         extra = [os.path.join(os.path.dirname(tuned), f"tunableop_gfx950_{args.workload}_bs{args.batch}_fp32.csv"),
                  os.path.join(os.path.dirname(tuned), "tunableop_gfx950_D256_bs2_fp32.csv")]
         extra += [os.path.join(os.path.dirname(tuned), f"tunableop_gfx950_{w}_bs{args.batch}_bf16.csv") for w in COMPANION_WORKLOADS]
@@ -495,7 +506,7 @@ def main():
                           f"{v['TFLOP/s']:7.0f} TF/s {v['GB/s']:6.0f} GB/s  {tag}", file=sys.stderr)
     # the reference trains in fp32 (training/train_config.py:95 `precision: int = 32`): same workload, same batch, fp32
     # activations, a few steps -- so the reference's own precision is measured next to the bf16 headline
-    if world == 1 and args.dtype == "bf16" and not args.no_fp32_companion and not args.graph and not args.tune_gemm:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.no_fp32_companion and not args.graph and not args.tune_gemm:
         try:  # (a companion line must never cost the headline line: its failure is recorded under its key)
             k = max(2, min(args.steps, 8))
             r32 = run_workload(ctx, "fp32", k, 2, timing=False)
@@ -523,7 +534,7 @@ def main():
             torch.cuda.empty_cache()
     # BASELINE configs[4] at its stated size next to it: HEAL-SWIN-T, nside 256, 8 base pixels, depth head (f_out = 1), fp32, masked
     # L1 loss; batch 2 per GPU as in the reference's run configs (run_configs/*/..._train_run_config.py: batch_size 2)
-    if world == 1 and args.dtype == "bf16" and args.workload == "B256" and not args.no_fp32_companion and not args.graph and not args.tune_gemm:
+    if args.full and world == 1 and args.dtype == "bf16" and args.workload == "B256" and not args.no_fp32_companion and not args.graph and not args.tune_gemm:
         try:  # (a companion line must never cost the headline line: its failure is recorded under its key)
             dctx = types.SimpleNamespace(**{**vars(ctx), "wl": WORKLOADS["D256"], "batch": 2})
             kd = 5
@@ -542,7 +553,7 @@ def main():
     # what INTEGRATION.md level 1 delivers when NOTHING but the import line of the reference changes: no gradient sink (autograd
     # accumulates .grad, AccumulateGrad launches included), nn.CrossEntropyLoss on the materialised fp32 logits, torch.optim.Adam as
     # the reference builds it, eager -- in the reference's precision (fp32) and with `model.compute_dtype = torch.bfloat16`
-    if world == 1 and args.dtype == "bf16" and not args.drop_in and not args.no_companions and not args.graph and not args.tune_gemm:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.drop_in and not args.no_companions and not args.graph and not args.tune_gemm:
         try:  # (a companion line must never cost the headline line: its failure is recorded under its key)
             dctx = types.SimpleNamespace(**{**vars(ctx), "args": argparse.Namespace(**{**vars(args), "drop_in": True})})
             out["drop_in"] = {"workload": wl["name"], "batch_per_gpu": args.batch, "unit": "images/s",
@@ -561,7 +572,7 @@ def main():
             torch.cuda.empty_cache()
     # the reference's activation-memory policy (use_checkpoint: every block recomputed in the backward) on the same workload: what the
     # 110 GB (bf16) / 260 GB (fp32) of the lines above shrink to, and what the recomputation costs
-    if world == 1 and args.dtype == "bf16" and not args.use_checkpoint and not args.drop_in and not args.no_companions and not args.graph and not args.tune_gemm:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.use_checkpoint and not args.drop_in and not args.no_companions and not args.graph and not args.tune_gemm:
         try:  # (a companion line must never cost the headline line: its failure is recorded under its key)
             wck = dict(wl, cfg=dict(wl["cfg"], use_checkpoint=True), name=wl["name"] + " use_checkpoint")
             kctx = types.SimpleNamespace(**{**vars(ctx), "wl": wck})
@@ -580,7 +591,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
     # the same step replayed from ONE HIP graph (heal_swin_amd.graphs): what host launch latency costs the eager line above
-    if world == 1 and args.dtype == "bf16" and not args.graph and not args.no_graph_companion and not args.paper_drop_rates and not args.tune_gemm:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.graph and not args.no_graph_companion and not args.paper_drop_rates and not args.tune_gemm:
         try:  # (a companion line must never cost the headline line: its failure is recorded under its key)
             gctx = types.SimpleNamespace(**{**vars(ctx), "args": argparse.Namespace(**{**vars(args), "graph": True})})
             kg = max(2, min(args.steps, 8))
@@ -598,7 +609,7 @@ def main():
     # the reference's own model next to the headline: BASELINE configs[1] (T @ nside 128) and the paper config (T @ nside 256,
     # ring_shift + cosine attention + v2 norms), bf16, same batch, eager AND replayed from one HIP graph (these steps are short
     # enough for host launch latency to matter: the faster of the two is the value, `launch` says which)
-    if world == 1 and args.dtype == "bf16" and args.workload == "B256" and not args.no_companions and not args.graph and not args.tune_gemm:
+    if args.full and world == 1 and args.dtype == "bf16" and args.workload == "B256" and not args.no_companions and not args.graph and not args.tune_gemm:
         try:  # (a companion line must never cost the headline line: its failure is recorded under its key)
             out["companions"] = {}
             for key in COMPANION_WORKLOADS:
@@ -641,7 +652,7 @@ def main():
             import gc
             gc.collect()
             torch.cuda.empty_cache()
-    if rank == 0 and res.timings and world == 1 and not args.no_kernel_timing:
+    if args.full and rank == 0 and res.timings and world == 1 and not args.no_kernel_timing:
         # the WindowAttention MODULE (qkv Linear + fused core + proj Linear, forward + input gradients + weight gradients) at the
         # step's shapes: north_star's ">= 40 % MFMA utilisation in windowed attention" is a statement about this unit, not about
         # the 32-flop/B core kernels the `roofline` object above brackets
@@ -655,7 +666,7 @@ def main():
                 out["roofline"] = {**roofline_of(res.timings, elapsed, detail=args.kernel_table, traffic_records=recs),
                                    "module": out["roofline"]["module"]}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -1032,10 +1043,22 @@ def _run_workload(ctx, dtype_name, steps, warmup, timing, undo, dump_dir=None):
         step_ms_per_rank = [round(1e3 * float(v.item()) / steps, 3) for v in own]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+        if drop_in:  # (torch DDP owns its buckets: an all-reduce of the same volume stands for them)
+            dp.buckets = [torch.zeros(sum(p.numel() for p in model.parameters()), device=dev)]
+        nbytes = sum(f.numel() * 4 for f in dp.buckets)
+        try:
+            rccl_version = ".".join(str(v) for v in torch.cuda.nccl.version())
+        except Exception:  # noqa: BLE001
+            rccl_version = None
+        rccl = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(), "rccl_version": rccl_version,
+                "step_ms_per_rank": step_ms_per_rank, "buckets": len(dp.buckets), "allreduce_bytes_per_step": nbytes,
+                "reserved_cus": int(__import__("heal_swin_amd")._lib.lib.hs_get_reserved_cus()), "NCCL_MAX_NCHANNELS": os.environ.get("NCCL_MAX_NCHANNELS"),
+                "gemm_policy": gemm_policy,
+                "exchange": ("torch.nn.parallel.DistributedDataParallel (its own buckets and hooks)" if drop_in else
+                             f"{args.comm_dtype} wire format of fp32 flat buckets, async all-reduce launched from gradient hooks during backward")}
+    if world > 1 and args.full:
         # the exchange on its own: every gradient bucket all-reduced back to back, timed per rank with events
         reps = 5
-        if drop_in:  # (torch DDP owns its buckets: time an all-reduce of the same volume)
-            dp.buckets = [torch.zeros(sum(p.numel() for p in model.parameters()), device=dev)]
         for flat in dp.buckets:
             dist.all_reduce(flat)
         sync()
@@ -1049,12 +1072,7 @@ def _run_workload(ctx, dtype_name, steps, warmup, timing, undo, dump_dir=None):
         mine = torch.tensor([e0.elapsed_time(e1) / reps], device=dev, dtype=torch.float64)
         per_rank = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(per_rank, mine)
-        nbytes = sum(f.numel() * 4 for f in dp.buckets)
         ms = [float(v.item()) for v in per_rank]
-        try:
-            rccl_version = ".".join(str(v) for v in torch.cuda.nccl.version())
-        except Exception:  # noqa: BLE001
-            rccl_version = None
         # one more (untimed) step with the sink's timeline on: when, in milliseconds after the step began, did each gradient bucket
         # start its exchange (from a hook during the backward, or only in finish()), and when had all of them been waited for
         timeline = None
@@ -1065,15 +1083,8 @@ def _run_workload(ctx, dtype_name, steps, warmup, timing, undo, dump_dir=None):
             step()
             timeline = dp.timeline_ms(t_begin)
             dp.record_timeline(False)
-        rccl = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(), "rccl_version": rccl_version,
-                "bucket_timeline_rank0": timeline,
-                "step_ms_per_rank": step_ms_per_rank, "buckets": len(dp.buckets),
-                "allreduce_bytes_per_step": nbytes, "allreduce_ms_per_step_standalone_per_rank": [round(v, 3) for v in ms],
-                "allreduce_bus_GBps": 2 * (world - 1) / world * nbytes / (max(ms) * 1e-3) / 1e9,
-                "reserved_cus": int(__import__("heal_swin_amd")._lib.lib.hs_get_reserved_cus()), "NCCL_MAX_NCHANNELS": os.environ.get("NCCL_MAX_NCHANNELS"),
-                "gemm_policy": gemm_policy,
-                "exchange": ("torch.nn.parallel.DistributedDataParallel (its own buckets and hooks)" if drop_in else
-                             f"{args.comm_dtype} wire format of fp32 flat buckets, async all-reduce launched from gradient hooks during backward")}
+        rccl.update({"bucket_timeline_rank0": timeline, "allreduce_ms_per_step_standalone_per_rank": [round(v, 3) for v in ms],
+                     "allreduce_bus_GBps": 2 * (world - 1) / world * nbytes / (max(ms) * 1e-3) / 1e9})
     res = types.SimpleNamespace(elapsed=elapsed, loss=float(loss.item()), timings=timings if rank == 0 else None, rccl=rccl, dumped=dumped,
                                 params_m=round(sum(p.numel() for p in model.parameters()) / 1e6, 2),
                                 peak_gb=round(torch.cuda.max_memory_allocated(dev) / 1e9, 1))

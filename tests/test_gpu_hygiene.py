@@ -228,12 +228,12 @@ def test_param_cast_cache_sees_data_swaps_and_invalidate():
 
 
 def test_bench_self_launches_multi_rank():
-    """`python bench.py --gpus 2` with NO launcher around it: re-executes itself under torch.distributed.run (two ranks share
-    this box's single GPU over gloo: HS_BENCH_SHARED_GPU=1) and reports the exchange in the JSON line."""
+    """`python bench.py --gpus 2 --full` with NO launcher around it: re-executes itself under torch.distributed.run (two ranks share
+    one GPU over gloo: HS_BENCH_SHARED_GPU=1), the option included, and reports the exchange in the JSON line."""
     env = dict(os.environ, HS_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "tiny"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "tiny", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -247,10 +247,10 @@ def test_bench_self_launches_multi_rank():
 
 def test_bench_dump_outputs(tmp_path):
     """`bench.py --dump-outputs DIR`: after the timed steps the last step's loss and a fixed sample of the updated parameters and their
-    gradients land in DIR as float32 / float64 .npy files (at most 64 MB), and the line reports the requested number of timed steps."""
+    gradients land in DIR as float32 / float64 .npy files (at most 64 MB), and the line reports the requested number of timed steps.
+    Without --full the run measures nothing beside the headline and its roofline: no companion lines, no runs of their own."""
     out_dir = tmp_path / "dump"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "tiny",
-           "--no-companions", "--no-cpu-baseline", "--no-fp32-companion", "--no-graph-companion", "--no-pmc-traffic",
            "--dump-outputs", str(out_dir)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -258,6 +258,8 @@ def test_bench_dump_outputs(tmp_path):
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert not {"fp32", "depth_fp32", "drop_in", "use_checkpoint", "graph_replay", "companions", "cpu_baseline"} & set(out), sorted(out)
+    assert out["roofline"]["frac"] > 0 and "module" not in out["roofline"]
     arrays = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
     assert set(arrays) == {"loss", "params_sample", "grads_sample"} == set(out["dumped_outputs"]["arrays"])
     assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())

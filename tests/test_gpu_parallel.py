@@ -244,8 +244,8 @@ def test_bench_script_eight_ranks_on_one_gpu():
     """The first real 8-GPU run must not be the first time eight ranks meet: bench.py --gpus 8 as the driver launches it, one rank
     per GPU over RCCL at the tiny size, bf16 wire format.  Checks what a mis-wired exchange would break:
     every rank arrives (max-over-ranks timing of 8 entries), the bucket order / hooks do not deadlock, the GEMM policy is agreed by
-    all ranks (a MAX all-reduce: one dissenting rank would hang the next collective), the timeline diagnostic is there, and the
-    line says rccl_ranks == 8.  The strong-scaling reading (global batch 8 -> 1 per rank) runs the same way.
+    all ranks (a MAX all-reduce: one dissenting rank would hang the next collective), the timeline diagnostic is there (--full), and
+    the line says rccl_ranks == 8.  The strong-scaling reading (global batch 8 -> 1 per rank) runs the same way.
     Eight ranks need eight GPUs, one rank each: eight processes (plus this one) must not share one GPU."""
     found = torch.cuda.device_count()
     if found < 8:
@@ -257,7 +257,7 @@ def test_bench_script_eight_ranks_on_one_gpu():
     for extra, per_gpu, scaling in ((["--batch", "1"], 1, "weak"), (["--batch", "8", "--strong-scaling"], 1, "strong")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-               "--workload", "tiny", "--comm-dtype", "bf16"] + extra
+               "--workload", "tiny", "--comm-dtype", "bf16", "--full"] + extra
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

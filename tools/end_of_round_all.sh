@@ -1,5 +1,5 @@
 #!/bin/bash
-# End-of-round evidence on one box: full GPU suite, smoke, default bench line + rocprof (B256), rocprof of the companions' workloads
+# End-of-round evidence on one box: full GPU suite, smoke, --full bench line + rocprof (B256), rocprof of the companions' workloads
 TAG=${1:-r05_g}
 cd /root/repo; mkdir -p gpurun_out; export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -x -q -m gpu > gpurun_out/${TAG}_gpu_tests.txt 2>&1; tail -3 gpurun_out/${TAG}_gpu_tests.txt
