@@ -11,6 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libhealswin.so")
 
 HS_F32, HS_BF16 = 0, 1
+HS_F64 = 3
 HS_PRED_LABELS, HS_PRED_ROWS16 = 2, 4
 HS_ATTN_COSINE = 1
 HS_ATTN_FORCE_VALU = 2
@@ -65,6 +66,13 @@ _SIGNATURES = {
     "hs_backproject_labels": [c_ptr, c_int, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr],
     "hs_backproject_image": [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_seg_confusion": [c_ptr, c_int, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
+    "hs_depth_points": [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
+                        c_ptr],
+    "hs_chamfer_nn": [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                      c_ptr],
+    "hs_depth_metrics": [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_int, c_i64, c_i64, c_i64, c_int,
+                         ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
+    "hs_backproject_depth": [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_gelu_fwd": [c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_gelu_bwd": [c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_residual_drop": [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
@@ -131,6 +139,8 @@ _OTHER = {
     "hs_reduce_pending": ([c_ptr], c_int),
     "hs_layernorm_bwd_workspace": ([c_i64, c_int], c_i64),
     "hs_seg_ce_partials": ([c_i64, c_i64], c_i64),
+    "hs_depth_points_workspace": ([c_i64, c_i64], c_i64),
+    "hs_depth_metrics_partials": ([c_i64], c_i64),
     "hs_ln_head_partials": ([c_i64], c_i64),
     "hs_expand_ln_head_blocks": ([c_i64], c_i64),
     "hs_linear_wgrad_workspace": ([c_i64, c_int, c_int], c_i64),

@@ -9,6 +9,8 @@ pipeline's other end (`projection.HPProjector` is its input side).  Mirrors the 
   HPBackProjector                                     the tables of one calibration, resident on the GPU:
       .masks(pred)                                    project_hp_mask_back (:319-341)   `hs_backproject_labels`
       .images(hp_img)                                 project_hp_img_back (:302-316)    `hs_backproject_image`
+      .depth(pred)                                    data/depth_estimation/project_depth_on_s2.py:370-386
+                                                      (project_depth_hp_mask_back, NaN fill)  `hs_backproject_depth`
       .valid                                          evaluation/custom_metrics.py:48-53 (HPMaskedIoU.get_mask)
   SegConfusion                                        the confusion matrix behind torchmetrics 0.3.2's IoU / Accuracy
                                                       (models_lightning/segmentation/model_lightning_swin_hp.py:47-55) and
@@ -80,14 +82,20 @@ def _theta_of_rho(ks, rho):
     return theta
 
 
-def project_img_points_to_s2(u, v, cal_info, rotate_pole=False):
+def project_img_points_to_s2(u, v, cal_info, rotate_pole=False, used_size=None):
     """(theta, phi) on S^2 of image points (u, v) of a calibrated fisheye camera: the inverse of
-    projection.project_s2_points_to_img.  phi in [0, 2 pi) without rotation, in (-pi, pi] after rot_grid(inv=True)."""
+    projection.project_s2_points_to_img.  phi in [0, 2 pi) without rotation, in (-pi, pi] after rot_grid(inv=True).
+    used_size = (h, w): (u, v) are coordinates of an h x w image of the camera's frame and are first rescaled to the
+    calibration's size, u * W / w and v * H / h (the depth variant, data/depth_estimation/project_depth_on_s2.py:195-196)."""
     intr = cal_info["intrinsic"]
     width, height = int(intr["width"]), int(intr["height"])
     ks = [float(intr["k" + str(order)]) for order in range(1, intr["poly_order"] + 1)]
-    x = np.asarray(u, dtype=np.float64) - intr["cx_offset"] - width / 2 + 0.5
-    y = (np.asarray(v, dtype=np.float64) - intr["cy_offset"] - height / 2 + 0.5) / intr["aspect_ratio"]
+    u, v = np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    if used_size is not None:
+        u = u * width / int(used_size[1])
+        v = v * height / int(used_size[0])
+    x = u - intr["cx_offset"] - width / 2 + 0.5
+    y = (v - intr["cy_offset"] - height / 2 + 0.5) / intr["aspect_ratio"]
     rho = np.sqrt(x**2 + y**2)
     phi = np.arctan2(y, x)
     phi = np.where(phi < 0, 2 * np.pi + phi, phi)
@@ -222,6 +230,25 @@ class HPBackProjector:
         out = torch.empty(lead + self.shape, dtype=torch.float64, device=self.device)
         check(lib.hs_backproject_image(ptr(src), int(np.prod(lead)), self.npix, ptr(self.idx), ptr(self.wgt), self.n_out, ptr(out),
                                        stream_ptr(self.device)), "hs_backproject_image")
+        return out
+
+    def depth(self, pred, channel=0):
+        """Bilinear back-projection of HEALPix depth values: project_depth_hp_mask_back(..., s2_bkgd_class=nan)
+        (data/depth_estimation/project_depth_on_s2.py:370-386).  pred: fp32 / bf16 [B, C, Npix] (channel `channel` is read
+        in place, any strides) or [B, Npix] -> float64 [B, H', W'].  The map is completed with NaN outside the model's base
+        pixels and NaN propagates from any of the four pixels, a weight-0 one included (0 * NaN in the reference's sum)."""
+        if not torch.is_tensor(pred) or pred.device != self.device or pred.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"pred must be a float32 / bfloat16 tensor on {self.device}")
+        if pred.dim() == 3:
+            pred = pred[:, channel]
+        if pred.dim() != 2 or pred.shape[-1] != self.npix:
+            raise ValueError(f"pred must be [B, C, {self.npix}] or [B, {self.npix}], got {tuple(pred.shape)}")
+        if min(pred.stride()) < 0:
+            raise ValueError("predictions with negative strides are not supported")
+        out = torch.empty((pred.shape[0],) + self.shape, dtype=torch.float64, device=self.device)
+        check(lib.hs_backproject_depth(ptr(pred), HS_F32 if pred.dtype == torch.float32 else HS_BF16, pred.shape[0], self.npix,
+                                       pred.stride(0), pred.stride(1), ptr(self.idx), ptr(self.wgt), self.n_out, ptr(out),
+                                       stream_ptr(self.device)), "hs_backproject_depth")
         return out
 
 

@@ -571,6 +571,66 @@ int hs_seg_confusion(const void* pred, int pred_kind, int64_t batch, int64_t npi
                      int64_t* bad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth evaluation (heal_swin_amd/depth_evaluation.py, csrc/depth_eval.hip): point clouds, Chamfer nearest neighbours, the
+ * depth error metrics and the float back-projection.  Depth values are read in place: kind HS_F32 / HS_BF16, element (b, i) of
+ * n = rows * width at b*stride_b + (i / width)*stride_h + (i % width)*stride_w (HEALPix data: width = n, stride_h unused).
+ *   hs_depth_points     create_point_cloud_from_depth_mask (heal_swin/utils/depth_utils.py:465-539) and the kept set of
+ *                       ChamferDistance.update (evaluation/custom_metrics.py:539-561).  Pixel i of sample b is kept when its depth
+ *                       is finite, differs from every background[0 .. n_background) (<= 4) and, if foreground [dev] u8 (element
+ *                       b*fg_stride_b + i) is given, foreground is nonzero.  Kept points, in pixel order, sample after sample:
+ *                       points [dev] f32[batch * n][3] rows offsets[b] .. offsets[b+1] = fp32(d * dir[:, i]) (float64 product),
+ *                       dir [dev] f64[3][n] the rotated unit directions; offsets [dev] i64[batch + 1].  Rows past offsets[batch]
+ *                       are not written.  workspace [dev]: hs_depth_points_workspace(batch, n) bytes.  Deterministic (counts,
+ *                       one scan, writes).
+ *   hs_chamfer_nn       for every sample s, clouds a (rows a_off[s] .. a_off[s+1] of a [dev] f32[a_rows][3]) and b:
+ *                       dist_a[i] = min_j |a_i - b_j|^2, dist_b[j] = min_i |a_i - b_j|^2 (fp32, dx*dx + dy*dy + dz*dz from the
+ *                       coordinate differences, FMA-chained), idx_a / idx_b [dev] i64 the lowest index within the other cloud
+ *                       attaining it (both NULL: distances only).  a_max / b_max bound the points of one sample (grid size; the
+ *                       offsets are not read on the host).  Rows of a sample whose other cloud is empty, and rows past the last
+ *                       cloud, get NaN and -1.  term [dev] f64[batch] (optional) = mean(dist_a) + mean(dist_b) of the sample,
+ *                       NaN when a cloud is empty.  splits: target-range workgroups per query block (0: automatic); the results
+ *                       are bit-identical for every value.  workspace [dev]: 8 * (a_rows + b_rows) bytes.
+ *   hs_depth_metrics    one pass over pred (kind HS_F32 / HS_BF16 / HS_F64; the mean at channel 0, the log variance at +stride_c
+ *                       when use_logvar) and target (same layout, strides t_stride_*), ADDING the HS_DEPTH_NSUMS sums below into
+ *                       state [dev] f64[HS_DEPTH_NSUMS] (custom_metrics.py:62-468; selections there).  ranges [host] f32[2][n_ranges]
+ *                       (lo, hi) pairs, n_ranges <= 8.  partial [dev] f64[hs_depth_metrics_partials(batch * n)][HS_DEPTH_NSUMS]
+ *                       scratch.  Per-element values in the reference's compute type, sums in float64 in a fixed order.
+ *   hs_backproject_depth  project_depth_hp_mask_back(..., s2_bkgd_class=nan) (data/depth_estimation/project_depth_on_s2.py:370-386):
+ *                       values (b, p) at b*stride_b + p*stride_p, out [dev] f64[batch, n_out] = ((w0 v0 + w1 v1) + w2 v2) + w3 v3
+ *                       with v = NaN where idx >= npix (hs_backproject_image's tables and order).
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_F64 3
+#define HS_DS_N 0       /* pred and target finite: count */
+#define HS_DS_SE 1      /*   sum (p - t)^2 */
+#define HS_DS_AE 2      /*   sum |p - t| */
+#define HS_DS_MEAN_SE 3 /*   sum (total_mean - t)^2 */
+#define HS_DS_MEAN_AE 4 /*   sum |total_mean - t| */
+#define HS_DS_PRED 5    /*   sum p */
+#define HS_DS_SIL_N 6   /*   and p > 0, t > 0: count */
+#define HS_DS_SIL_D 7   /*     sum (log t - log p) */
+#define HS_DS_SIL_D2 8  /*     sum (log t - log p)^2 */
+#define HS_DS_INV_N 9   /* 1 / (0.001 p), 1 / (0.001 t) finite: count */
+#define HS_DS_INV_SE 10 /*   sum of their squared difference */
+#define HS_DS_STD_N 11  /* target not NaN and not +inf: count */
+#define HS_DS_STD 12    /*   sum sqrt(exp(log_var)) */
+#define HS_DS_RANGE 13  /* 2 r, 2 r + 1: count and sum (p - t)^2 of the finite pairs with lo_r <= t < hi_r */
+#define HS_DEPTH_NSUMS 29
+int64_t hs_depth_points_workspace(int64_t batch, int64_t n);
+int hs_depth_points(const void* depth, int kind, int64_t batch, int64_t n, int64_t width, int64_t stride_b, int64_t stride_h,
+                    int64_t stride_w, const uint8_t* foreground, int64_t fg_stride_b, const float* background, int n_background,
+                    const double* dir, void* workspace, float* points, int64_t* offsets, void* stream);
+int hs_chamfer_nn(const float* a, const int64_t* a_off, int64_t a_rows, int64_t a_max, const float* b, const int64_t* b_off,
+                  int64_t b_rows, int64_t b_max, int64_t batch, int splits, void* workspace, float* dist_a, float* dist_b,
+                  int64_t* idx_a, int64_t* idx_b, double* term, void* stream);
+int64_t hs_depth_metrics_partials(int64_t total);
+int hs_depth_metrics(const void* pred, int pred_kind, int64_t batch, int64_t n, int64_t width, int64_t stride_b, int64_t stride_c,
+                     int64_t stride_h, int64_t stride_w, const void* target, int target_kind, int64_t t_stride_b, int64_t t_stride_h,
+                     int64_t t_stride_w, int use_logvar, double total_mean, const float* ranges, int n_ranges, double* partial,
+                     double* state, void* stream);
+int hs_backproject_depth(const void* pred, int kind, int64_t batch, int64_t npix, int64_t stride_b, int64_t stride_p, const int32_t* idx,
+                         const double* wgt, int64_t n_out, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decoder tail: LayerNorm(C) of FinalPatchExpand_X4 + the 1x1 class head in one pass, so that the normalised
  * [B, 4 N0, C] tensor is never written.  Replaces `self.norm(x)` (models_torch/swin_hp_transformer.py:448-452) followed by
  * `self.output(x)` (:756-761, :785-788) and their backward.  bf16 rows, C in {64, 96, ..., 256}, <= 16 classes.
