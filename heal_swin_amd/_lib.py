@@ -20,6 +20,8 @@ HS_ATTN_OVERWRITE_GRADS = 8
 HS_EPI_BIAS, HS_EPI_GELU, HS_EPI_DGELU, HS_EPI_RESID = 0, 1, 2, 3
 HS_ACC_DEFER = 2
 HS_MLP_NORM_AFTER = 16
+HS_U8, HS_I32, HS_I64 = 8, 9, 10
+HS_FLAT_PATCH_ROWS, HS_FLAT_PIXEL_ROWS = 0, 1
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -37,6 +39,12 @@ _SIGNATURES = {
     "hs_build_nest_grid_shift": [c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     "hs_build_ring_shift": [c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
     "hs_attn_mask_from_labels": [c_ptr, c_i64, c_int, c_ptr],
+    "hs_flat_zorder": [c_int, c_int, c_int, c_ptr, c_ptr],
+    "hs_build_flat_shift": [c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    "hs_flat_rel_pos_index": [c_int, c_ptr, c_ptr],
+    "hs_flat_attn_mask": [c_int, c_int, c_int, c_int, c_ptr],
+    "hs_flat_img_to_rows": [c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_ptr],
+    "hs_flat_rows_to_img": [c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_ptr],
     "hs_rel_bias_gather": [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
     "hs_rel_bias_scatter_grad_sorted_add": [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
     "hs_cos_head_scale_fwd": [c_ptr, c_ptr, c_int, c_ptr],
@@ -272,4 +280,35 @@ def attn_mask_from_labels(labels, window_size):
     lab = np.ascontiguousarray(labels, dtype=np.uint8)
     out = np.empty((lab.size // window_size, window_size, window_size), dtype=np.float32)
     check(lib.hs_attn_mask_from_labels(np_ptr(lab), lab.size, int(window_size), np_ptr(out)), "hs_attn_mask_from_labels")
+    return out
+
+
+# ------------------------------------------------------------------ flat Swin-UNet tables (tiled Z order, include/healswin.h)
+def flat_zorder(Ht, Wt, T):
+    """(z_of_rm, rm_of_z) int32[Ht*Wt]: the tiled-Z index of each row-major token and its inverse."""
+    z = np.empty(Ht * Wt, np.int32)
+    rm = np.empty(Ht * Wt, np.int32)
+    check(lib.hs_flat_zorder(int(Ht), int(Wt), int(T), np_ptr(z), np_ptr(rm)), "hs_flat_zorder")
+    return z, rm
+
+
+def build_flat_shift(Ht, Wt, T, window, shift):
+    idx, inv, lab = _shift_out(max(Ht * Wt, 0))
+    check(lib.hs_build_flat_shift(int(Ht), int(Wt), int(T), int(window), int(shift), np_ptr(idx), np_ptr(inv), np_ptr(lab)),
+          "hs_build_flat_shift")
+    return idx, inv, lab
+
+
+def flat_rel_pos_index(window):
+    """(row-major, Z-order) int64[w*w, w*w] relative-position indices of a w x w window."""
+    n = window * window
+    rm = np.empty((n, n), np.int64)
+    z = np.empty((n, n), np.int64)
+    check(lib.hs_flat_rel_pos_index(int(window), np_ptr(rm), np_ptr(z)), "hs_flat_rel_pos_index")
+    return rm, z
+
+
+def flat_attn_mask(Ht, Wt, window, shift):
+    out = np.empty(((Ht // window) * (Wt // window), window * window, window * window), np.float32)
+    check(lib.hs_flat_attn_mask(int(Ht), int(Wt), int(window), int(shift), np_ptr(out)), "hs_flat_attn_mask")
     return out

@@ -256,32 +256,44 @@ class SwinTransformerBlock(nn.Module):
         self.dim, self.input_resolution, self.num_heads = dim, input_resolution, num_heads
         self.window_size, self.shift_size, self.mlp_ratio = window_size, shift_size, mlp_ratio
         self.use_v2_norm_placement = use_v2_norm_placement
+        self.n_tokens = input_resolution
         if input_resolution <= window_size:  # a single window: no partition, no shift (ref :243-246)
             self.shift_size, self.window_size = 0, input_resolution
 
-        self.norm1 = _make_norm(norm_layer, dim)
         # as in the reference the attention module is built with the UNclamped window_size (ref :249-251)
-        self.attn = WindowAttention(dim, window_size=window_size, num_heads=num_heads, rel_pos_bias=rel_pos_bias,
-                                    qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop,
-                                    use_cos_attn=use_cos_attn)
-        self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
-        self.norm2 = _make_norm(norm_layer, dim)
-        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self._build_branches(dim, WindowAttention(dim, window_size=window_size, num_heads=num_heads, rel_pos_bias=rel_pos_bias,
+                                                  qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop,
+                                                  use_cos_attn=use_cos_attn),
+                             mlp_ratio, drop, drop_path, act_layer, norm_layer)
 
         nside = math.sqrt(input_resolution // base_pix)
         assert nside % 1 == 0, "nside has to be an integer in every layer"
         nside = int(nside)
         if self.shift_size > 0:
             if shift_strategy == "nest_roll":
-                self.shifter = hp_shifting.NestRollShift(self.shift_size, self.input_resolution, self.window_size)
+                shifter = hp_shifting.NestRollShift(self.shift_size, self.input_resolution, self.window_size)
             elif shift_strategy == "nest_grid_shift":
-                self.shifter = hp_shifting.NestGridShift(nside, base_pix, self.window_size)
+                shifter = hp_shifting.NestGridShift(nside, base_pix, self.window_size)
             elif shift_strategy == "ring_shift":
-                self.shifter = hp_shifting.RingShift(nside, base_pix, self.window_size, self.shift_size)
+                shifter = hp_shifting.RingShift(nside, base_pix, self.window_size, self.shift_size)
             else:
                 raise KeyError(shift_strategy)
         else:
-            self.shifter = hp_shifting.NoShift()
+            shifter = hp_shifting.NoShift()
+        self._set_shifter(shifter)
+
+    def _build_branches(self, dim, attn, mlp_ratio, drop, drop_path, act_layer, norm_layer):
+        """norm1, attn, drop_path, norm2, mlp -- in the reference's registration order (state-dict key order)."""
+        self.norm1 = _make_norm(norm_layer, dim)
+        self.attn = attn
+        self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
+        self.norm2 = _make_norm(norm_layer, dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+
+    def _set_shifter(self, shifter):
+        """The shift of a shifted block: any object with `tables(device)` -> (idx int32, inv int32, labels uint8 or None) and
+        `get_mask()` (the reference's dense mask or None); NoShift for the others."""
+        self.shifter = shifter
         self._is_roll = isinstance(self.shifter, hp_shifting.NestRollShift)
         self._shifted = self.shift_size > 0
 
@@ -294,7 +306,9 @@ class SwinTransformerBlock(nn.Module):
     @staticmethod
     def _emit_attn_mask(module, state_dict, prefix, local_metadata):
         if EMIT_REFERENCE_BUFFERS and module._shifted:
-            state_dict[prefix + "attn_mask"] = module.shifter.get_mask()
+            mask = module.shifter.get_mask()
+            if mask is not None:  # (a flat block without masking has none)
+                state_dict[prefix + "attn_mask"] = mask
 
     def _accept_attn_mask(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         state_dict.pop(prefix + "attn_mask", None)
@@ -462,7 +476,7 @@ class SwinTransformerBlock(nn.Module):
 
     def forward(self, x):
         B, N, C = x.shape
-        assert N == self.input_resolution, f"expected {self.input_resolution} tokens, got {N}"
+        assert N == self.n_tokens, f"expected {self.n_tokens} tokens, got {N}"
         if self.can_defer():
             return self.resolve_pending(*self.forward_deferred(x, None)[:2])
         train = self.training
@@ -688,46 +702,54 @@ class UnetDecoder(nn.Module):
             if dbg:
                 print(f"feature shape after decoder layer {inx}: {x.size()}")
         w = self.output.weight  # 1x1 conv without bias (ref :756-761) as the [f_out, C] matrix it is (ops.LinearFn)
-        f_out = w.shape[0]
-        up = self.up
-        if (isinstance(up.norm, HSLayerNorm) and isinstance(up.expand, HSLinear) and up.expand.bias is None and
-                ops.expand_ln_head_ok(x, up.dim, up.patch_size, f_out)):
-            # the whole tail in one forward kernel (hs_expand_ln_head_fwd): expand -> view -> LayerNorm -> head with fp32 statistics
-            # on the expand product's accumulators; the [B, Npix, C] tensor is written once for the backward, or not at all
-            xn_lo = None
-            if isinstance(self.norm_up, HSLayerNorm):  # norm_up output as hi + lo: no rounding between norm_up and the logits
-                xn, xn_lo = ops.layer_norm_hilo(x, self.norm_up.weight, self.norm_up.bias)
-            else:
-                xn = self.norm_up(x)
-            B, N0, _ = xn.shape
-            if ce is not None and ce[0].dtype == torch.uint8 and torch.is_grad_enabled():
-                # training: expand -> LayerNorm -> head -> weighted CE in one forward kernel; the logits are never written
-                return ops.expand_ln_head_ce(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
-                                             ce[0].contiguous(), ce[1], xn_lo)
-            lg = ops.expand_ln_head(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w, xn_lo)
-            return self._maybe_loss(ops.pad_slice(lg.view(B, N0 * up.patch_size, -1), f_out).transpose(1, 2), ce)  # B, f_out, Npix (fp32)
-        if isinstance(up.norm, HSLayerNorm) and ops.ln_head_ok(x, up.dim, f_out):
-            # the tail's LayerNorm and the class head in one pass over the expanded rows (hs_ln_head_*): the normalised
-            # [B, Npix, C] tensor is neither written nor kept for the backward
-            x = up.expand(self.norm_up(x))  # B, N0, p * C: row (b, n) holds the p children of token n back to back
-            B, N0, _ = x.shape
-            x = ops.ln_head(x.reshape(B * N0 * up.patch_size, up.dim), up.norm.weight, up.norm.bias, w)
-            return self._maybe_loss(ops.pad_slice(x.view(B, N0 * up.patch_size, -1), f_out).transpose(1, 2), ce)  # B, f_out, Npix (fp32)
-        x = up(self.norm_up(x))  # B, Npix, C
-        if x.dtype == torch.bfloat16 and f_out % 8 and f_out > 8:
-            # 12 classes: rows padded to 16 so that the input gradient (K = 12 -> 16) runs in hs_gemm_nt: 0.33 ms instead of the
-            # library's 0.85 ms; the caller sees the [.., :f_out] view (the loss kernels read logits through their strides)
-            x = ops.pad_slice(ops.linear(x, F.pad(w.reshape(f_out, -1), (0, 0, 0, (-f_out) % 8))), f_out)
-        else:
-            x = ops.linear(x, w)
-        return self._maybe_loss(x.float().transpose(1, 2), ce)  # B, f_out, Npix; logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
+        out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, ce)
+        return out if ce is not None else out.float().transpose(1, 2)  # B, f_out, Npix (fp32)
 
-    @staticmethod
-    def _maybe_loss(logits, ce):
-        if ce is None:
-            return logits
-        from ..losses import seg_loss
-        return seg_loss(logits, ce[0], ce[1])
+
+def decoder_tail(norm_up, up, w, children, x, ce=None):
+    """norm_up -> up (Linear C -> children * C, one LayerNorm(C) per child) -> 1x1 head w [f_out, C, ...] on the decoder output
+    x [B, N0, C].  Returns the logits rows [B, N0 * children, f_out] (the children of a token consecutive; fp32, or the fallback's
+    compute dtype), or with ce = (labels u8 [B, N0 * children] in the same row order, class weights or None) the weighted
+    cross-entropy instead (SwinHPTransformerSys.forward_seg_loss); fused into the tail kernels where they apply."""
+    f_out = w.shape[0]
+    if (isinstance(up.norm, HSLayerNorm) and isinstance(up.expand, HSLinear) and up.expand.bias is None and
+            ops.expand_ln_head_ok(x, up.dim, children, f_out)):
+        # the whole tail in one forward kernel (hs_expand_ln_head_fwd): expand -> view -> LayerNorm -> head with fp32 statistics
+        # on the expand product's accumulators; the [B, Npix, C] tensor is written once for the backward, or not at all
+        xn_lo = None
+        if isinstance(norm_up, HSLayerNorm):  # norm_up output as hi + lo: no rounding between norm_up and the logits
+            xn, xn_lo = ops.layer_norm_hilo(x, norm_up.weight, norm_up.bias)
+        else:
+            xn = norm_up(x)
+        B, N0, _ = xn.shape
+        if ce is not None and ce[0].dtype == torch.uint8 and torch.is_grad_enabled():
+            # training: expand -> LayerNorm -> head -> weighted CE in one forward kernel; the logits are never written
+            return ops.expand_ln_head_ce(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
+                                         ce[0].contiguous(), ce[1], xn_lo)
+        lg = ops.expand_ln_head(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w, xn_lo)
+        return _rows_or_loss(ops.pad_slice(lg.view(B, N0 * children, -1), f_out), ce)
+    if isinstance(up.norm, HSLayerNorm) and ops.ln_head_ok(x, up.dim, f_out):
+        # the tail's LayerNorm and the class head in one pass over the expanded rows (hs_ln_head_*): the normalised
+        # [B, Npix, C] tensor is neither written nor kept for the backward
+        x = up.expand(norm_up(x))  # B, N0, p * C: row (b, n) holds the p children of token n back to back
+        B, N0, _ = x.shape
+        x = ops.ln_head(x.reshape(B * N0 * children, up.dim), up.norm.weight, up.norm.bias, w)
+        return _rows_or_loss(ops.pad_slice(x.view(B, N0 * children, -1), f_out), ce)
+    x = up(norm_up(x))  # B, Npix, C
+    if x.dtype == torch.bfloat16 and f_out % 8 and f_out > 8:
+        # 12 classes: rows padded to 16 so that the input gradient (K = 12 -> 16) runs in hs_gemm_nt: 0.33 ms instead of the
+        # library's 0.85 ms; the caller sees the [.., :f_out] view (the loss kernels read logits through their strides)
+        x = ops.pad_slice(ops.linear(x, F.pad(w.reshape(f_out, -1), (0, 0, 0, (-f_out) % 8))), f_out)
+    else:
+        x = ops.linear(x, w)
+    return _rows_or_loss(x, ce)  # logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
+
+
+def _rows_or_loss(rows, ce):
+    if ce is None:
+        return rows
+    from ..losses import seg_loss
+    return seg_loss(rows.float().transpose(1, 2), ce[0], ce[1])
 
 
 @dataclass

@@ -1,11 +1,12 @@
 """Skip-connection Linear without the concatenation, PatchMerging / PatchExpand as operators, standalone row gather (shift)
-(swin_hp_transformer.py:364-452, :772-775; hp_shifting.py)."""
+(swin_hp_transformer.py:364-452, :772-775; hp_shifting.py), and the flat model's image <-> tiled-Z token-row layouts
+(swin_transformer.py; csrc/flat_layout.hip)."""
 
 import torch
 
 from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
-from .runtime import RT, _cast_param, _f32, _require_gpu, _sink_buffer  # noqa: F401
+from .runtime import RT, _cast_param, _f32, _require_gpu, _sink_buffer, _timed  # noqa: F401
 from .gemm import LinearFn, _cast_param_t, gemm_nt, own_gemm_ok  # noqa: F401
 
 
@@ -206,3 +207,101 @@ class GatherRowsFn(torch.autograd.Function):
 
 def gather_rows(x, idx=None, inv=None, roll=0):
     return GatherRowsFn.apply(x, idx, inv, roll)
+
+
+_FLAT_DTYPES = {torch.float32: _lib.HS_F32, torch.bfloat16: _lib.HS_BF16, torch.uint8: _lib.HS_U8, torch.int32: _lib.HS_I32,
+                torch.int64: _lib.HS_I64}
+
+
+def _flat_code(dtype):
+    if dtype not in _FLAT_DTYPES:
+        raise TypeError(f"flat layout kernels take {sorted(str(d) for d in _FLAT_DTYPES)}, got {dtype}")
+    return _FLAT_DTYPES[dtype]
+
+
+def _img_to_rows(img, out, p, T, mode, ld):
+    B, nch, H, W = img.shape
+    with _timed(f"flat_img_to_rows_{mode}", img.device, img.numel() * img.element_size() + out.numel() * out.element_size(), 0):
+        check(lib.hs_flat_img_to_rows(ptr(img), _flat_code(img.dtype), ptr(out), _flat_code(out.dtype), B, nch, H, W, int(p), int(T),
+                                      mode, int(ld), stream_ptr(img.device)), "hs_flat_img_to_rows")
+    return out
+
+
+def _rows_to_img(rows, out, p, T, mode, ld):
+    B, nch, H, W = out.shape
+    with _timed(f"flat_rows_to_img_{mode}", out.device, rows.numel() * rows.element_size() + out.numel() * out.element_size(), 0):
+        check(lib.hs_flat_rows_to_img(ptr(rows), _flat_code(rows.dtype), ptr(out), _flat_code(out.dtype), B, nch, H, W, int(p), int(T),
+                                      mode, int(ld), stream_ptr(out.device)), "hs_flat_rows_to_img")
+    return out
+
+
+class FlatPatchRowsFn(torch.autograd.Function):
+    """[B, f, H, W] image (uint8 / fp32 / bf16) -> [B, N0, K] patch rows in tiled-Z token order, features (c, kh, kw) as in the
+    Conv2d weight, K = f p^2 zero-padded to a multiple of 8, in `dtype`.  Backward: the patch-row gradient -> the image gradient."""
+
+    @staticmethod
+    def forward(ctx, img, p, T, dtype):
+        _require_gpu(img)
+        img = img.contiguous()
+        B, f, H, W = img.shape
+        K = f * p * p
+        K += (-K) % 8
+        out = torch.empty((B, (H // p) * (W // p), K), dtype=dtype, device=img.device)
+        _img_to_rows(img, out, p, T, _lib.HS_FLAT_PATCH_ROWS, K)
+        ctx.meta = (img.shape, img.dtype, p, T, K)
+        return out
+
+    @staticmethod
+    def backward(ctx, drows):
+        shape, dtype, p, T, K = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        dimg = torch.empty(shape, dtype=dtype, device=drows.device)
+        _rows_to_img(drows.contiguous(), dimg, p, T, _lib.HS_FLAT_PATCH_ROWS, K)
+        return dimg, None, None, None
+
+
+def flat_patch_rows(img, p, T, dtype):
+    return FlatPatchRowsFn.apply(img, int(p), int(T), dtype)
+
+
+class FlatPixelImageFn(torch.autograd.Function):
+    """Logits rows [B, Npix, n_out] fp32 (row = token * p^2 + kh * p + kw in tiled-Z token order; unit column stride, any row pitch:
+    the [.., :n_out] view of the tail's padded 16-wide rows is read in place) -> [B, n_out, H, W] fp32.  Backward: the NCHW gradient
+    -> rows of the same pitch, zero in the padding columns, handed on whole to ops.PadSliceFn (as losses.seg_loss does)."""
+
+    @staticmethod
+    def forward(ctx, rows, H, W, p, T):
+        _require_gpu(rows)
+        B, Npix, n_out = rows.shape
+        ld = rows.stride(1)
+        assert rows.dtype == torch.float32 and rows.stride(2) == 1 and rows.stride(0) == Npix * ld and ld >= n_out, \
+            "logits rows: fp32 [B, Npix, n_out] with unit column stride"
+        out = torch.empty((B, n_out, H, W), dtype=torch.float32, device=rows.device)
+        _rows_to_img(rows, out, p, T, _lib.HS_FLAT_PIXEL_ROWS, ld)
+        ctx.meta = (B, Npix, n_out, ld, p, T)
+        return out
+
+    @staticmethod
+    def backward(ctx, dimg):
+        B, Npix, n_out, ld, p, T = ctx.meta
+        full = torch.empty((B, Npix, ld), dtype=torch.float32, device=dimg.device)
+        _img_to_rows(dimg.float().contiguous(), full, p, T, _lib.HS_FLAT_PIXEL_ROWS, ld)
+        if ld == n_out:
+            return full, None, None, None, None
+        RT.zero_padded_grads[full.data_ptr()] = full  # weak: lives exactly as long as the gradient view does
+        return full[:, :, :n_out], None, None, None, None
+
+
+def flat_pixel_image(rows, H, W, p, T):
+    return FlatPixelImageFn.apply(rows, int(H), int(W), int(p), int(T))
+
+
+def flat_labels(labels, p, T):
+    """[B, H, W] integer class ids (uint8 / int32 / int64) -> uint8 [B, Npix] in the pixel order of the logits rows; ids outside
+    [0, 254] become 255 (ignored by the loss kernels)."""
+    _require_gpu(labels)
+    labels = labels.contiguous()
+    B, H, W = labels.shape
+    out = torch.empty((B, H * W), dtype=torch.uint8, device=labels.device)
+    return _img_to_rows(labels.view(B, 1, H, W), out, p, T, _lib.HS_FLAT_PIXEL_ROWS, 1)

@@ -740,6 +740,42 @@ int hs_patch_expand_bwd(const void* dout, const void* x, const void* expanded, c
                         const void* w_t, void* dexpanded, void* dx, float* dw, float* dgamma, float* dbeta, float* workspace,
                         int accumulate, int64_t rows, int dim, int dim_exp, int children, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Flat Swin-UNet (models_torch/swin_transformer.py:SwinTransformerSys) in tiled Z order.
+ * An Ht x Wt token grid is cut into T x T tiles laid out row-major; inside a tile the tokens follow a Morton order whose least
+ * significant bit is the ROW bit.  With T = w * 2^(L-1) every window of every stage is w*w consecutive tokens and the
+ * reference's PatchMerging concat order (0::2,0::2), (1::2,0::2), (0::2,1::2), (1::2,1::2) is four consecutive tokens.
+ * ---------------------------------------------------------------------------------------------- */
+/* z_of_rm [host] int32[Ht*Wt]: tiled-Z index of row-major token h*Wt + w; rm_of_z [host] its inverse.  Either may be NULL. */
+int hs_flat_zorder(int Ht, int Wt, int T, int32_t* z_of_rm, int32_t* rm_of_z);
+/* Shifted block of window side w and shift s (swin_transformer.py:312-347, :364-390) as a shifter table (see above), in tiled-Z
+ * order: idx[j] = Z index of ((h+s) mod Ht, (w+s) mod Wt) for the cell (h, w) of Z position j (torch.roll by (-s, -s), then
+ * window_partition); labels[j] = region of (h, w) in the img_mask slices (0,-w), (-w,-s), (-s,None) per dimension. */
+int hs_build_flat_shift(int Ht, int Wt, int T, int w, int s, int32_t* idx, int32_t* inv, uint8_t* labels);
+/* relative_position_index of the flat WindowAttention (swin_transformer.py:126-137) for a w x w window: row_major [host]
+ * int64[w^4] as the reference's buffer, zorder [host] int64[w^4] with rows and columns in the in-window Morton order (what
+ * the attention kernels read).  Either may be NULL. */
+int hs_flat_rel_pos_index(int w, int64_t* row_major, int64_t* zorder);
+/* The reference's dense attn_mask buffer [nW, w*w, w*w] in {0, -100}: windows row-major, positions row-major in a window.
+ * out [host] float.  Only emitted by state_dict(); the kernels read labels. */
+int hs_flat_attn_mask(int Ht, int Wt, int w, int s, float* out);
+
+/* element types of the flat layout kernels, beside HS_F32 / HS_BF16 */
+#define HS_U8 8
+#define HS_I32 9
+#define HS_I64 10
+/* row layouts of the flat layout kernels */
+#define HS_FLAT_PATCH_ROWS 0 /* row = token, column = (c, kh, kw) of the p x p patch (PatchEmbed's Conv2d as a Linear) */
+#define HS_FLAT_PIXEL_ROWS 1 /* row = token * p^2 + kh * p + kw (FinalPatchExpand_X4's children), column = c */
+/* [B, nch, H, W] image [dev] (HS_U8 / HS_F32 / HS_BF16; HS_I32 / HS_I64 too when out_dtype is HS_U8) -> token rows [dev] with
+ * row pitch ld (elements) in out_dtype (HS_F32 / HS_BF16, or HS_U8 for labels: ids outside [0, 254] become 255).  Columns past
+ * the valid ones are written as zeros.  H and W are multiples of p * T; T is a power of two. */
+int hs_flat_img_to_rows(const void* img, int in_dtype, void* rows, int out_dtype, int batch, int nch, int H, int W, int p, int T,
+                        int mode, int64_t ld, void* stream);
+/* the inverse: token rows [dev] (HS_F32 / HS_BF16, padding columns ignored) -> [B, nch, H, W] image [dev] (HS_F32 / HS_BF16). */
+int hs_flat_rows_to_img(const void* rows, int in_dtype, void* img, int out_dtype, int batch, int nch, int H, int W, int p, int T,
+                        int mode, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
