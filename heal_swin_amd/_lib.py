@@ -22,6 +22,7 @@ HS_ACC_DEFER = 2
 HS_MLP_NORM_AFTER = 16
 HS_U8, HS_I32, HS_I64 = 8, 9, 10
 HS_FLAT_PATCH_ROWS, HS_FLAT_PIXEL_ROWS = 0, 1
+HS_DEPTH_L1, HS_DEPTH_L2, HS_DEPTH_HUBER, HS_DEPTH_LOGVAR = 0, 1, 2, 3
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -66,6 +67,10 @@ _SIGNATURES = {
     "hs_expand_ln_head_ce_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
                                  c_int, c_ptr],
     "hs_ln_head_ce_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr],
+    "hs_expand_ln_head_depth_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_float, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
+                                    c_int, c_int, c_int, c_ptr],
+    "hs_ln_head_depth_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_float, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
+                             c_int, c_ptr],
     "hs_ln_head_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr],
     "hs_ln_head_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr],
     "hs_sample_bilinear_u8": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
@@ -117,6 +122,8 @@ _SIGNATURES = {
     "hs_seg_ce_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_int, c_i64, c_int, c_ptr],
     "hs_seg_ce_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_i64,
                       c_int, c_ptr],
+    "hs_depth_loss_fwd": [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_int, c_float, c_int, c_ptr],
+    "hs_depth_loss_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_float, c_int, c_ptr],
     "hs_gemm_nt": [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
                    ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_gemm_nt_set_tile": [c_int],
@@ -147,6 +154,7 @@ _OTHER = {
     "hs_reduce_pending": ([c_ptr], c_int),
     "hs_layernorm_bwd_workspace": ([c_i64, c_int], c_i64),
     "hs_seg_ce_partials": ([c_i64, c_i64], c_i64),
+    "hs_depth_loss_partials": ([c_i64, c_i64], c_i64),
     "hs_depth_points_workspace": ([c_i64, c_i64], c_i64),
     "hs_depth_metrics_partials": ([c_i64], c_i64),
     "hs_ln_head_partials": ([c_i64], c_i64),

@@ -18,7 +18,10 @@
 // (A = weight rows from LDS) leaves the child's C channels of a token in ONE lane pair: LayerNorm statistics are in-register
 // sums plus one lane^32 exchange, the normalised registers are (after packing) the B operand of the head product, and the
 // logits of the row land in registers 0..7 of the same lane pair.  32 C / 16 + 4 C / 16 MFMAs per 32 pixel rows.
+#include <type_traits>
+
 #include "hs_device.h"
+#include "hs_depth_loss.h"
 
 namespace hs {
 namespace {
@@ -48,13 +51,26 @@ struct TailCe {
     int n_classes;
 };
 
-template <int NB>
+// ... or the depth caller's regression loss (hs_depth_loss.h; heal_swin/training/loss_depth_regression.py): a head of one or two
+// channels, i.e. accumulator registers 0 and 1 of the lane pair's half 0, against the row's fp32 target.  The kernel is a template
+// over the loss type, so the TailCe instantiation is the code it was before this epilogue existed.
+struct TailDepth {
+    const float* target;  // [rows] in pixel order; rows whose target is infinite are masked out
+    float* loss_part;     // [4 * gridDim.x][2]: per-wave sums of the depth term and of the kept rows
+    int kind;             // HS_DEPTH_*
+    float delta;          // huber delta
+};
+__device__ __forceinline__ bool has_loss(const TailCe& ce) { return ce.labels != nullptr; }
+__device__ __forceinline__ bool has_loss(const TailDepth&) { return true; }
+
+template <int NB, typename Loss>
 __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16_t* __restrict__ xn, const uint16_t* __restrict__ xn_lo,
                                                                     const uint16_t* __restrict__ wexp,
                                                                     const uint16_t* __restrict__ wfold, const float* __restrict__ bvec,
                                                                     uint16_t* __restrict__ y, float* __restrict__ logits,
                                                                     float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                                    int64_t tokens, TailCe ce) {
+                                                                    int64_t tokens, Loss ce) {
+    constexpr bool kCe = std::is_same<Loss, TailCe>::value;
     constexpr int C = 32 * NB, KS = 2 * NB, NCH = C / 8;  // channels (= input width), 16-deep k-steps, 16-byte chunks per row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* wl = smem;                                  // [kP * C][kRowB], 16-byte chunk ^ (row & 15)
@@ -201,7 +217,13 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                     lg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfa[ct][j], __builtin_bit_cast(bf16x8, pack8f(lo)), lg, 0, 0, 0);
                     lg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfl[ct][j], __builtin_bit_cast(bf16x8, hb), lg, 0, 0, 0);
                 }
-            if (ce.labels) {  // weighted cross-entropy of the row, from the fp32 logits in registers
+            if constexpr (!kCe) {  // depth term of the row: channels 0 and 1 are registers 0 and 1 of half 0
+                const float t = live && half == 0 ? ce.target[orow] : INFINITY;
+                if (depth_keep(t)) {
+                    ce_num += depth_term(ce.kind, ce.delta, lg[0] + bk[0], lg[1] + bk[1], t);
+                    ce_den += 1.f;
+                }
+            } else if (ce.labels) {  // weighted cross-entropy of the row, from the fp32 logits in registers
                 constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
                 float v[8];
                 float m = -INFINITY;
@@ -240,7 +262,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             }
         }
     }
-    if (ce.labels) {  // every wave writes its pair (zeros if it owned no rows): the host sums the array
+    if (has_loss(ce)) {  // every wave writes its pair (zeros if it owned no rows): the host sums the array
         const float n = wave_sum(ce_num), d = wave_sum(ce_den);
         if (lane == 0) {
             ce.loss_part[2 * wave] = n;
@@ -258,9 +280,11 @@ int hs_expand_ln_head_supported(int width, int children, int n_classes, int dtyp
     return dtype == HS_BF16 && children == hs::kP && width % 32 == 0 && width >= 64 && width <= 128 && n_classes >= 1 && n_classes <= 16;
 }
 
+extern "C++" {
 namespace {
+template <typename Loss>
 int launch_expand_ln_head(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, void* y, float* logits,
-                          float* mean, float* rstd, int64_t tokens, int width, int children, int dtype, void* stream, hs::TailCe ce,
+                          float* mean, float* rstd, int64_t tokens, int width, int children, int dtype, void* stream, Loss ce,
                           const char* who) {
     using namespace hs;
     HS_CHECK_ARG(xn && wexp && wfold && bvec, "%s: null pointer", who);
@@ -276,7 +300,7 @@ int launch_expand_ln_head(const void* xn, const void* xn_lo, const void* wexp, c
     hipStream_t s = (hipStream_t)stream;
 #define HS_ELH(NB)                                                                                                                  \
     case NB: {                                                                                                                      \
-        auto kern = expand_ln_head_fwd_kernel<NB>;                                                                                 \
+        auto kern = expand_ln_head_fwd_kernel<NB, Loss>;                                                                                 \
         static bool configured = false;                                                                                             \
         if (!configured) {                                                                                                          \
             HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));           \
@@ -293,6 +317,7 @@ int launch_expand_ln_head(const void* xn, const void* xn_lo, const void* wexp, c
     return HS_OK;
 }
 }  // namespace
+}  // extern "C++"
 
 int64_t hs_expand_ln_head_blocks(int64_t tokens) {
     int64_t blocks = (tokens + 127) / 128;  // 4 waves x 32 tokens per workgroup and step
@@ -315,6 +340,16 @@ int hs_expand_ln_head_ce_fwd(const void* xn, const void* xn_lo, const void* wexp
     HS_CHECK_ARG(n_classes >= 1 && n_classes <= 16, "hs_expand_ln_head_ce_fwd: 1..16 classes");
     return launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream,
                                  hs::TailCe{labels, class_weights, loss_partials, n_classes}, "hs_expand_ln_head_ce_fwd");
+}
+
+int hs_expand_ln_head_depth_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const float* target,
+                                int kind, float huber_delta, int n_out, void* y, float* logits, float* mean, float* rstd, float* loss_partials,
+                                int64_t tokens, int width, int children, int dtype, void* stream) {
+    HS_CHECK_ARG(target && loss_partials, "hs_expand_ln_head_depth_fwd: null pointer");
+    HS_CHECK_ARG(hs::depth_head_ok(kind, huber_delta, n_out), "hs_expand_ln_head_depth_fwd: kind %d with %d head channels (1 or 2; Huber 1, "
+                 "log variance 2; huber delta > 0)", kind, n_out);
+    return launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream,
+                                 hs::TailDepth{target, loss_partials, kind, huber_delta}, "hs_expand_ln_head_depth_fwd");
 }
 
 }  // extern "C"

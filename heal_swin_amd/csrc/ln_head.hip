@@ -18,7 +18,10 @@
 // (forward) or the row's g values in the same chunk order as the lane's y registers (backward: the rows of the A operand
 // are permuted to make it so).  HBM-bound: forward reads C x 2 B and writes 32 B per row, backward reads C x 2 + 32 + 8 B
 // and writes C x 2 + 32 B.
+#include <type_traits>
+
 #include "hs_device.h"
+#include "hs_depth_loss.h"
 
 namespace hs {
 namespace {
@@ -236,16 +239,33 @@ __global__ void __launch_bounds__(256) ln_head_bwd_kernel(const uint16_t* __rest
 // in registers, and continues exactly as ln_head_bwd_kernel.  The rows of the folded weight arrive PERMUTED (blocks 4..7 and
 // 8..11 exchanged, ops._fold_head_ce) so that accumulator register r < 8 of lane half h is class 8 h + r: the 8 contiguous
 // classes of a lane are then directly the B operand of the g = dlogits (gamma W) product and the 16 bytes of D'.
-template <int NB>
+//
+// The same kernel with the depth caller's regression loss (BwdDepth, hs_depth_loss.h): dpred of the row's one or two channels
+// from the recomputed head outputs.  Those channels are classes 0 and 1, which sit in registers 0 and 1 of lane half 0 with the
+// exchanged row order AND without it (the exchange moves classes 4..11 only): the depth caller passes the plain folded weight.
+// Loss is a template parameter whose two structs occupy the argument slots of (labels, class_w), so the cross-entropy
+// instantiation is the code it was before.
+struct BwdCe {
+    const uint8_t* labels;
+    const float* class_w;
+};
+struct BwdDepth {
+    const float* target;  // [rows] fp32; rows with an infinite target get a zero gradient
+    int kind;             // HS_DEPTH_*
+    float delta;
+};
+
+template <int NB, typename Loss>
 __global__ void __launch_bounds__(256) ln_head_ce_bwd_kernel(const uint16_t* __restrict__ y, const float* __restrict__ mean_in,
-                                                             const float* __restrict__ rstd_in, const uint8_t* __restrict__ labels,
-                                                             const float* __restrict__ class_w, const float* __restrict__ scale_ptr,
+                                                             const float* __restrict__ rstd_in, const Loss loss,
+                                                             const float* __restrict__ scale_ptr,
                                                              int n_classes, const uint16_t* __restrict__ wfold,
                                                              const float* __restrict__ bvec, const uint16_t* __restrict__ afold,
                                                              uint16_t* __restrict__ dy, uint16_t* __restrict__ dprime,
                                                              float* __restrict__ part, int64_t rows) {
     constexpr int C = NB * 32, NS = NB * 2;
     constexpr float kLog2e = 1.4426950408889634f;
+    constexpr bool kCe = std::is_same<Loss, BwdCe>::value;
     const int lane = threadIdx.x & 63, l31 = lane & 31, half = lane >> 5;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
     bf16x8 wa[NS], wl[NS];  // folded head weight, hi and lo, rows permuted (see above)
@@ -273,7 +293,10 @@ __global__ void __launch_bounds__(256) ln_head_ce_bwd_kernel(const uint16_t* __r
         const int64_t row = row0 + l31;
         const bool live = row < rows;
         const float mean = live ? mean_in[row] : 0.f, rstd = live ? rstd_in[row] : 0.f;
-        const int yl = live ? (int)labels[row] : 255;
+        int yl = 255;
+        float tgt = INFINITY;
+        if constexpr (kCe) yl = live ? (int)loss.labels[row] : 255;
+        else tgt = live && half == 0 ? loss.target[row] : INFINITY;
         uint4 v[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) v[s] = live ? *(const uint4*)(y + row * C + 16 * s + 8 * half) : make_uint4(0, 0, 0, 0);
@@ -298,7 +321,11 @@ __global__ void __launch_bounds__(256) ln_head_ce_bwd_kernel(const uint16_t* __r
         }
         // ---- softmax and the cross-entropy gradient on this lane's classes 8 half .. 8 half + 7
         float d[8];
-        {
+        if constexpr (!kCe) {  // ---- or the depth gradient of channels 0 and 1 (registers 0 and 1 of half 0)
+#pragma unroll
+            for (int r = 0; r < 8; ++r) d[r] = 0.f;
+            if (depth_keep(tgt)) depth_grad(loss.kind, loss.delta, lg[0] + bk[0], lg[1] + bk[1], tgt, scale, &d[0], &d[1]);
+        } else {
             float m = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
@@ -313,7 +340,7 @@ __global__ void __launch_bounds__(256) ln_head_ce_bwd_kernel(const uint16_t* __r
                 ssum += d[r];
             }
             ssum += __shfl_xor(ssum, 32, 64);
-            const float wy = yl < n_classes ? (class_w ? class_w[yl] : 1.f) : 0.f;
+            const float wy = yl < n_classes ? (loss.class_w ? loss.class_w[yl] : 1.f) : 0.f;
             const float coef = scale * wy, pinv = 1.f / ssum;
 #pragma unroll
             for (int r = 0; r < 8; ++r) d[r] = coef * (d[r] * pinv - (8 * half + r == yl ? 1.f : 0.f));
@@ -455,7 +482,7 @@ int hs_ln_head_ce_bwd(const void* y, const float* mean, const float* rstd, const
     hipStream_t s = (hipStream_t)stream;
 #define HS_LNH_CE(NB)                                                                                                                   \
     case NB:                                                                                                                            \
-        hipLaunchKernelGGL((ln_head_ce_bwd_kernel<NB>), grid, block, 0, s, (const uint16_t*)y, mean, rstd, labels, class_weights, scale, \
+        hipLaunchKernelGGL((ln_head_ce_bwd_kernel<NB, BwdCe>), grid, block, 0, s, (const uint16_t*)y, mean, rstd, BwdCe{labels, class_weights}, scale, \
                            n_classes, (const uint16_t*)wfold, bvec, (const uint16_t*)afold, (uint16_t*)dy, (uint16_t*)dprime, partials, rows); \
         break;
     switch (width / 32) {
@@ -463,6 +490,32 @@ int hs_ln_head_ce_bwd(const void* y, const float* mean, const float* rstd, const
     }
 #undef HS_LNH_CE
     HS_LAUNCH_CHECK("ln_head_ce_bwd");
+    return HS_OK;
+}
+
+int hs_ln_head_depth_bwd(const void* y, const float* mean, const float* rstd, const float* target, int kind, float huber_delta,
+                         const float* scale, int n_out, const void* wfold, const float* bvec, const void* afold, void* dy, void* dprime,
+                         float* partials, int64_t rows, int width, int dtype, void* stream) {
+    using namespace hs;
+    HS_CHECK_ARG(y && mean && rstd && target && scale && wfold && bvec && afold && dy && dprime && partials, "null pointer");
+    HS_CHECK_ARG(rows > 0, "bad shape");
+    HS_CHECK_ARG(depth_head_ok(kind, huber_delta, n_out), "hs_ln_head_depth_bwd: kind %d with %d head channels (1 or 2; Huber 1, "
+                 "log variance 2; huber delta > 0)", kind, n_out);
+    if (!hs_ln_head_supported(width, n_out, dtype) || width > 128)
+        return fail(HS_ERR_UNSUPPORTED, "hs_ln_head_depth_bwd: bf16 rows of 64..128 (multiple of 32) columns only");
+    const dim3 grid(grid_for(rows)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    const BwdDepth dep{target, kind, huber_delta};
+#define HS_LNH_DEPTH(NB)                                                                                                                \
+    case NB:                                                                                                                            \
+        hipLaunchKernelGGL((ln_head_ce_bwd_kernel<NB, BwdDepth>), grid, block, 0, s, (const uint16_t*)y, mean, rstd, dep, scale, n_out,  \
+                           (const uint16_t*)wfold, bvec, (const uint16_t*)afold, (uint16_t*)dy, (uint16_t*)dprime, partials, rows);      \
+        break;
+    switch (width / 32) {
+        HS_LNH_DEPTH(2) HS_LNH_DEPTH(3) HS_LNH_DEPTH(4)
+    }
+#undef HS_LNH_DEPTH
+    HS_LAUNCH_CHECK("ln_head_depth_bwd");
     return HS_OK;
 }
 

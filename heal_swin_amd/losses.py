@@ -1,6 +1,6 @@
 """Caller-side losses of the two reference Lightning modules, so that a train step
-is self-contained.  fp32 arithmetic regardless of the logits dtype; the segmentation cross-entropy runs in fused HIP
-kernels on device tensors, the depth losses are thin torch compositions."""
+is self-contained.  fp32 arithmetic regardless of the logits dtype; the segmentation cross-entropy and `depth_loss` run in
+fused HIP kernels on device tensors; the depth_*_loss functions are thin torch compositions (the yardstick of depth_loss)."""
 from functools import partial
 
 import torch
@@ -132,6 +132,93 @@ def depth_mean_log_var_loss(pred, target, mask_background=False):
     zero = torch.zeros((), dtype=torch.float32, device=pred.device)
     means, log_var = torch.where(keep, pred[:, 0].float(), zero), torch.where(keep, pred[:, 1].float(), zero)
     return _masked_mean(0.5 * log_var + (means - tgt) ** 2 * (0.5 * torch.exp(-log_var)), keep, n)
+
+
+DEPTH_KINDS = {"l1": 0, "l2": 1, "huber": 2, "logvar": 3}  # HS_DEPTH_* of include/healswin.h
+
+
+def depth_loss_spec(loss="l2", huber_delta=1.0, use_logvar=False):
+    """(HS_DEPTH_* kind, huber delta) chosen as get_depth_loss chooses: `use_logvar` wins over `loss`.  `loss` may also be a
+    CommonDepthConfig-like object (fields use_logvar, loss, huber_delta), whose fields are then used."""
+    if not isinstance(loss, str):
+        cfg = loss
+        loss, huber_delta, use_logvar = cfg.loss, getattr(cfg, "huber_delta", huber_delta), cfg.use_logvar
+    if use_logvar:
+        return DEPTH_KINDS["logvar"], float(huber_delta)
+    if loss not in ("l1", "l2", "huber"):
+        raise ValueError(f"depth loss must be 'l1', 'l2' or 'huber' (or use_logvar=True), got {loss!r}")
+    if loss == "huber" and not float(huber_delta) > 0:
+        raise ValueError(f"huber_delta must be positive, got {huber_delta}")
+    return DEPTH_KINDS[loss], float(huber_delta)
+
+
+def check_depth_channels(kind, channels):
+    """The channel requirements of losses.py: Huber on a one-channel prediction (as depth_huber_loss asserts), the log-variance
+    loss on (mean, log variance)."""
+    assert kind != DEPTH_KINDS["huber"] or channels == 1, "huber_loss needs a one-channel prediction (reference loss_depth_regression.py:66)"
+    assert kind != DEPTH_KINDS["logvar"] or channels >= 2, "the mean-log-variance loss needs two channels (mean, log variance)"
+
+
+class _DepthLossFn(torch.autograd.Function):
+    """Depth-regression loss by `hs_depth_loss_fwd/bwd`: reads pred [B, C, P] (fp32 / bf16) in place through its strides (the
+    model's padded [B, Npix, 16] rows seen as [B, f_out, Npix] are neither copied nor widened) and the fp32 target [B, P]."""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind, delta):
+        from . import _lib
+        from ._lib import check, lib, ptr, stream_ptr
+        if pred.dtype not in (torch.float32, torch.bfloat16):
+            pred = pred.float()
+        B, C, P = pred.shape
+        sb, sc, sp = pred.stride()
+        parts = torch.empty((int(lib.hs_depth_loss_partials(B, P)), 2), dtype=torch.float32, device=pred.device)
+        check(lib.hs_depth_loss_fwd(ptr(pred), ptr(target), ptr(parts), B, P, C, sb, sc, sp, kind, delta, _lib.dtype_code(pred.dtype),
+                                    stream_ptr(pred.device)), "hs_depth_loss_fwd")
+        tot = parts.sum(0)
+        ctx.save_for_backward(pred, target, tot)
+        ctx.kind, ctx.delta = kind, delta
+        return tot[0] / tot[1]
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import _lib
+        from ._lib import check, lib, ptr, stream_ptr
+        pred, target, tot = ctx.saved_tensors
+        B, C, P = pred.shape
+        sb, sc, sp = pred.stride()
+        dense = sorted(pred.stride(), reverse=True) == sorted(torch.empty(pred.shape, device="meta").stride(), reverse=True)
+        if dense:
+            dp = torch.empty_strided(pred.shape, pred.stride(), dtype=pred.dtype, device=pred.device)
+        elif sc == 1 and sp > C and sb == P * sp:
+            # the model's padded rows ([B, Npix, sp], C of sp columns used, seen as [B, C, Npix]): the gradient goes into a zeroed
+            # padded buffer in the same layout, handed on whole to the head's backward by ops.PadSliceFn (as seg_loss does)
+            from . import ops
+            full = torch.zeros((B, P, sp), dtype=pred.dtype, device=pred.device)
+            dp = full[:, :, :C].transpose(1, 2)
+            ops.RT.zero_padded_grads[full.data_ptr()] = full  # weak: the entry lives exactly as long as the gradient does
+        else:
+            dp = torch.empty_like(pred)
+        scale = (grad.to(torch.float32) / tot[1]).reshape(1)
+        db, dc, dpp = dp.stride()
+        check(lib.hs_depth_loss_bwd(ptr(pred), ptr(target), ptr(scale), ptr(dp), B, P, C, sb, sc, sp, db, dc, dpp, ctx.kind, ctx.delta,
+                                    _lib.dtype_code(pred.dtype), stream_ptr(pred.device)), "hs_depth_loss_bwd")
+        return dp, None, None, None
+
+
+def depth_loss(pred, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
+    """The depth losses above (get_depth_loss's selection: `use_logvar` first, then loss 'l1' | 'l2' | 'huber'; `loss` may be a
+    CommonDepthConfig-like object) by the fused HIP kernels `hs_depth_loss_*`: one pass over pred [B, C, Npix] (fp32 or bf16,
+    read through its strides) and the target [B, Npix] forward, one backward.  Same masking (non-infinite targets), same NaN
+    behaviour and the same gradients as the compositions.  `mask_background` is accepted and ignored, as in the reference.
+    Device tensors only: there is no CPU path."""
+    kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
+    assert pred.dim() == 3 and target.shape == (pred.shape[0], pred.shape[2]), "pred [B, C, Npix], target [B, Npix]"
+    check_depth_channels(kind, pred.shape[1])
+    if not pred.is_cuda:
+        raise RuntimeError("heal_swin_amd.losses.depth_loss runs only on an MI355X (HIP) device: got CPU tensors; "
+                           "there is no CPU fallback")
+    target = target.to(device=pred.device, dtype=torch.float32).contiguous()
+    return _DepthLossFn.apply(pred, target, kind, delta)
 
 
 def get_depth_loss(common_depth_config):

@@ -690,9 +690,10 @@ class UnetDecoder(nn.Module):
         self.output = nn.Conv1d(in_channels=config.embed_dim, out_channels=data_spec.f_out, kernel_size=1, bias=False)
         self.norm_up = _make_norm(config.norm_layer, config.embed_dim)
 
-    def forward(self, x, x_downsample, ce=None):
+    def forward(self, x, x_downsample, ce=None, depth=None):
         """ce = (labels u8 [B, Npix], class weights or None): return the weighted cross-entropy of the logits instead of the logits
-        (SwinHPTransformerSys.forward_seg_loss); fused into the tail kernels where they apply."""
+        (SwinHPTransformerSys.forward_seg_loss); depth = (target f32 [B, Npix], HS_DEPTH_* kind, huber delta): the depth loss
+        (forward_depth_loss).  Fused into the tail kernels where they apply."""
         dbg = self.config.dev_mode
         for inx, layer_up in enumerate(self.layers_up):
             if inx > 0:
@@ -702,15 +703,17 @@ class UnetDecoder(nn.Module):
             if dbg:
                 print(f"feature shape after decoder layer {inx}: {x.size()}")
         w = self.output.weight  # 1x1 conv without bias (ref :756-761) as the [f_out, C] matrix it is (ops.LinearFn)
-        out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, ce)
-        return out if ce is not None else out.float().transpose(1, 2)  # B, f_out, Npix (fp32)
+        out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, ce, depth)
+        return out if ce is not None or depth is not None else out.float().transpose(1, 2)  # B, f_out, Npix (fp32)
 
 
-def decoder_tail(norm_up, up, w, children, x, ce=None):
+def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None):
     """norm_up -> up (Linear C -> children * C, one LayerNorm(C) per child) -> 1x1 head w [f_out, C, ...] on the decoder output
     x [B, N0, C].  Returns the logits rows [B, N0 * children, f_out] (the children of a token consecutive; fp32, or the fallback's
     compute dtype), or with ce = (labels u8 [B, N0 * children] in the same row order, class weights or None) the weighted
-    cross-entropy instead (SwinHPTransformerSys.forward_seg_loss); fused into the tail kernels where they apply."""
+    cross-entropy instead (SwinHPTransformerSys.forward_seg_loss), with depth = (target f32 [B, N0 * children] in the same row
+    order, HS_DEPTH_* kind, huber delta) the depth-regression loss (forward_depth_loss); fused into the tail kernels where they
+    apply, else the standalone loss kernels on the rows."""
     f_out = w.shape[0]
     if (isinstance(up.norm, HSLayerNorm) and isinstance(up.expand, HSLinear) and up.expand.bias is None and
             ops.expand_ln_head_ok(x, up.dim, children, f_out)):
@@ -726,15 +729,19 @@ def decoder_tail(norm_up, up, w, children, x, ce=None):
             # training: expand -> LayerNorm -> head -> weighted CE in one forward kernel; the logits are never written
             return ops.expand_ln_head_ce(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
                                          ce[0].contiguous(), ce[1], xn_lo)
+        if depth is not None and torch.is_grad_enabled() and ops.expand_ln_head_depth_ok(x, up.dim, children, f_out, depth[1], depth[2]):
+            # training: expand -> LayerNorm -> head -> depth loss in one forward kernel; the head rows are never written
+            return ops.expand_ln_head_depth(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
+                                            depth[0], depth[1], depth[2], xn_lo)
         lg = ops.expand_ln_head(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w, xn_lo)
-        return _rows_or_loss(ops.pad_slice(lg.view(B, N0 * children, -1), f_out), ce)
+        return _rows_or_loss(ops.pad_slice(lg.view(B, N0 * children, -1), f_out), ce, depth)
     if isinstance(up.norm, HSLayerNorm) and ops.ln_head_ok(x, up.dim, f_out):
         # the tail's LayerNorm and the class head in one pass over the expanded rows (hs_ln_head_*): the normalised
         # [B, Npix, C] tensor is neither written nor kept for the backward
         x = up.expand(norm_up(x))  # B, N0, p * C: row (b, n) holds the p children of token n back to back
         B, N0, _ = x.shape
         x = ops.ln_head(x.reshape(B * N0 * children, up.dim), up.norm.weight, up.norm.bias, w)
-        return _rows_or_loss(ops.pad_slice(x.view(B, N0 * children, -1), f_out), ce)
+        return _rows_or_loss(ops.pad_slice(x.view(B, N0 * children, -1), f_out), ce, depth)
     x = up(norm_up(x))  # B, Npix, C
     if x.dtype == torch.bfloat16 and f_out % 8 and f_out > 8:
         # 12 classes: rows padded to 16 so that the input gradient (K = 12 -> 16) runs in hs_gemm_nt: 0.33 ms instead of the
@@ -742,10 +749,13 @@ def decoder_tail(norm_up, up, w, children, x, ce=None):
         x = ops.pad_slice(ops.linear(x, F.pad(w.reshape(f_out, -1), (0, 0, 0, (-f_out) % 8))), f_out)
     else:
         x = ops.linear(x, w)
-    return _rows_or_loss(x, ce)  # logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
+    return _rows_or_loss(x, ce, depth)  # logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
 
 
-def _rows_or_loss(rows, ce):
+def _rows_or_loss(rows, ce, depth=None):
+    if depth is not None:
+        from ..losses import _DepthLossFn
+        return _DepthLossFn.apply(rows.float().transpose(1, 2), depth[0], depth[1], depth[2])
     if ce is None:
         return rows
     from ..losses import seg_loss
@@ -925,6 +935,32 @@ class SwinHPTransformerSys(nn.Module):
                 self._prefetch_attn_params()
                 x, x_downsample = self.forward_features(x.to(dt))
                 return self.decoder(x, x_downsample, ce=(labels, w))
+        finally:
+            self._clear_attn_params()
+            ops.RT.cast_cache = prev
+
+    def forward_depth_loss(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
+        """get_depth_loss(cfg)(self(x), target) -- the depth caller's training step (training/loss_depth_regression.py) -- as ONE
+        call, so that the loss rides on the decoder tail's kernels: in bf16 training the [B, f_out, Npix] head rows and their
+        gradient are never written (csrc/expand_ln_head.hip, csrc/ln_head.hip).  Where the fused tail does not apply (fp32, other
+        widths, no gradient) this is losses.depth_loss(self(x), target, ...) on the standalone kernels.  target: [B, Npix] depths
+        (pixels with an infinite target are masked out); `loss` may be a CommonDepthConfig-like object (use_logvar, loss,
+        huber_delta) as get_depth_loss takes; `mask_background` is accepted and ignored, as in the reference."""
+        from ..losses import check_depth_channels, depth_loss_spec
+        kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
+        check_depth_channels(kind, self.data_spec.f_out)
+        if not x.is_cuda:
+            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+        assert target.shape == (x.shape[0], x.shape[-1]), "target [B, Npix]"
+        target = target.to(device=x.device, dtype=torch.float32).contiguous()
+        dt = self._activation_dtype(x)
+        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
+        ops.RT.last_cast_cache = ops.RT.cast_cache
+        try:
+            with torch.autocast(device_type="cuda", enabled=False):
+                self._prefetch_attn_params()
+                x, x_downsample = self.forward_features(x.to(dt))
+                return self.decoder(x, x_downsample, depth=(target, kind, delta))
         finally:
             self._clear_attn_params()
             ops.RT.cast_cache = prev

@@ -407,7 +407,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
             x = layer_up(x)
         return x
 
-    def _run(self, x, ce=None):
+    def _run(self, x, ce=None, depth=None):
         if not x.is_cuda:
             raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
         dt = self._activation_dtype(x)
@@ -419,7 +419,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
                 x, x_downsample = self.forward_features(x, dt)
                 x = self.forward_up_features(x, x_downsample)
                 p = self.config.patch_size[0]
-                return hp.decoder_tail(self.norm_up, self.up, self.output.weight, p * p, x, ce)
+                return hp.decoder_tail(self.norm_up, self.up, self.output.weight, p * p, x, ce, depth)
         finally:
             self._clear_attn_params()
             ops.RT.cast_cache = prev
@@ -443,3 +443,19 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         lab = ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
         w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
         return self._run(x, ce=(lab, w))
+
+    def forward_depth_loss(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
+        """get_depth_loss(cfg)(self(x), target) as ONE call (the flat depth baseline's training step, training/
+        loss_depth_regression.py): the target is laid out in the head rows' pixel order by a HIP kernel (fp32 copied bit for bit:
+        infinite and NaN depths survive), so that the loss rides on the decoder tail's kernels and, in bf16 training, the NCHW
+        prediction and the head rows are never written (the masked mean does not depend on the pixel order).  target: [B, H, W]
+        depths; the other arguments as SwinHPTransformerSys.forward_depth_loss."""
+        from ..losses import check_depth_channels, depth_loss_spec
+        kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
+        check_depth_channels(kind, self.data_spec.f_out)
+        if not x.is_cuda:
+            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+        H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
+        assert tuple(target.shape) == (x.shape[0], H, W), "target [B, H, W]"
+        tgt = ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
+        return self._run(x, depth=(tgt, kind, delta))

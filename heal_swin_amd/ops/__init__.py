@@ -9,7 +9,7 @@ One module per concern; everything is re-exported here, so `from heal_swin_amd i
     norm       LayerNorm family, GELU / residual-drop elementwise ops
     gemm       hs_gemm_nt + its policy, bf16 x 3 products, weight gradients, `LinearFn`
     attention  relative-position bias, cosine scales, attention core, the one-launch WindowAttention module
-    tail       decoder tail: LayerNorm + head (+ expand, + cross-entropy)
+    tail       decoder tail: LayerNorm + head (+ expand, + cross-entropy or depth loss)
     mlp_branch the Mlp branch as GEMM epilogues and as one fused kernel per direction
     patch      skip-connection Linear, PatchMerging / PatchExpand, standalone row gather
 

@@ -297,6 +297,16 @@ def flat_pixel_image(rows, H, W, p, T):
     return FlatPixelImageFn.apply(rows, int(H), int(W), int(p), int(T))
 
 
+def flat_depth_target(target, p, T):
+    """[B, H, W] fp32 depths -> fp32 [B, Npix] in the pixel order of the head rows (a copy through fp32: infinite and NaN depths
+    are kept as they are)."""
+    _require_gpu(target)
+    target = target.float().contiguous()
+    B, H, W = target.shape
+    out = torch.empty((B, H * W), dtype=torch.float32, device=target.device)
+    return _img_to_rows(target.view(B, 1, H, W), out, p, T, _lib.HS_FLAT_PIXEL_ROWS, 1)
+
+
 def flat_labels(labels, p, T):
     """[B, H, W] integer class ids (uint8 / int32 / int64) -> uint8 [B, Npix] in the pixel order of the logits rows; ids outside
     [0, 254] become 255 (ignored by the loss kernels)."""

@@ -51,10 +51,11 @@ class LnHeadFn(torch.autograd.Function):
         return (dy if ctx.needs_input_grad[0] else None), dgamma, dbeta, dw
 
 
-def _ln_head_backward(y2, mean, rstd, gamma, beta, weight, dlogits, want_params, ce=None):
+def _ln_head_backward(y2, mean, rstd, gamma, beta, weight, dlogits, want_params, ce=None, depth=None):
     """(dy, dgamma, dbeta, dWhead) of logits = head(LayerNorm(y2)) by `hs_ln_head_bwd` + one weight-gradient product (LnHeadFn).
     ce = (labels u8 [rows], class weights or None, scale f32[1]): the logits' gradient is that of the weighted cross-entropy and is
-    formed inside the kernel (`hs_ln_head_ce_bwd`) instead of being read."""
+    formed inside the kernel (`hs_ln_head_ce_bwd`) instead of being read; depth = (target f32 [rows], HS_DEPTH_* kind, huber
+    delta, scale f32[1]): likewise for the depth-regression loss (`hs_ln_head_depth_bwd`)."""
     rows, C = y2.shape
     f_out, KP = weight.shape[0], LnHeadFn.KP
     dev = y2.device
@@ -72,6 +73,14 @@ def _ln_head_backward(y2, mean, rstd, gamma, beta, weight, dlogits, want_params,
             check(lib.hs_ln_head_ce_bwd(ptr(y2), ptr(mean), ptr(rstd), ptr(labels), ptr(class_w), ptr(scale), f_out, ptr(wfold), ptr(bvec),
                                         ptr(afold), ptr(dy), ptr(dprime), ptr(part), rows, C, _lib.HS_BF16, stream_ptr(dev)),
                   "hs_ln_head_ce_bwd")
+    elif depth is not None:
+        target, kind, delta, scale = depth
+        # (plain folded weight: the exchange of _fold_head_ce moves classes 4..11 only, a one- or two-channel head is unaffected)
+        wfold, bvec = _fold_head(gamma, beta, weight, C, dev)
+        with _timed("ln_head_depth_bwd", dev, rows * (4 * C + 2 * KP + 4) + 8 * rows, 2 * rows * C * (KP + 96)):
+            check(lib.hs_ln_head_depth_bwd(ptr(y2), ptr(mean), ptr(rstd), ptr(target), kind, delta, ptr(scale), f_out, ptr(wfold),
+                                           ptr(bvec), ptr(afold), ptr(dy), ptr(dprime), ptr(part), rows, C, _lib.HS_BF16, stream_ptr(dev)),
+                  "hs_ln_head_depth_bwd")
     else:
         dlogits = dlogits.to(torch.float32).contiguous()
         with _timed("ln_head_bwd", dev, rows * (4 * C + 6 * KP) + 8 * rows, 2 * rows * C * KP):
@@ -218,6 +227,74 @@ class ExpandLnHeadCeFn(torch.autograd.Function):
         ctx.w_cast = ctx.cast_cache = None
         dwexp, _ = _param_grads(dy2, xn2, wexp, None, ctx.needs_input_grad[1], False)
         return dxn, dwexp, dgamma, dbeta, dw, None, None, None
+
+
+def expand_ln_head_depth_ok(x, width, children, f_out, kind, delta):
+    """Whether `expand_ln_head_depth` runs the decoder tail with the depth loss: as expand_ln_head_ok, and a head of one or two
+    channels that the kind accepts (Huber: one; log variance: two)."""
+    from ..losses import DEPTH_KINDS
+    if kind in (DEPTH_KINDS["l1"], DEPTH_KINDS["l2"]):
+        heads = (1, 2)
+    else:
+        heads = (1,) if kind == DEPTH_KINDS["huber"] else (2,)
+    return f_out in heads and delta > 0 and expand_ln_head_ok(x, width, children, f_out)
+
+
+class ExpandLnHeadDepthFn(torch.autograd.Function):
+    """The decoder tail AND the depth caller's regression loss (losses.depth_loss's kinds; reference
+    training/loss_depth_regression.py) as one forward and one backward kernel (`hs_expand_ln_head_depth_fwd`,
+    `hs_ln_head_depth_bwd`): the [B, Npix, 16] fp32 head rows and their gradient never exist in HBM.  xn2 [tokens, C] bf16,
+    target f32 [4 tokens] in pixel order -> scalar loss (fp32)."""
+
+    @staticmethod
+    def forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo):
+        _require_gpu(xn2, wexp, gamma, beta, weight, target, xn_lo)
+        tokens, C = xn2.shape
+        xn2 = xn2.contiguous()
+        xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
+        P = wexp.shape[0] // C
+        f_out = weight.shape[0]
+        wq = _cast_param(wexp, torch.bfloat16).contiguous()
+        wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
+        need = any(ctx.needs_input_grad[:5])
+        rows = tokens * P
+        target = target.reshape(-1)
+        assert target.dtype == torch.float32 and target.numel() == rows and target.is_contiguous(), "target: contiguous fp32, one per pixel row"
+        y = torch.empty((rows, C), dtype=torch.bfloat16, device=xn2.device) if need else None
+        mean = torch.empty(rows, dtype=torch.float32, device=xn2.device) if need else None
+        rstd = torch.empty_like(mean) if need else None
+        parts = torch.empty((4 * int(lib.hs_expand_ln_head_blocks(tokens)), 2), dtype=torch.float32, device=xn2.device)
+        # algorithmic traffic: xn in, target in (+ the expanded rows once in training); no head rows
+        with _timed("expand_ln_head_depth_fwd", xn2.device, 2 * tokens * C + rows * (4 + (2 * C + 8 if need else 0)),
+                    2 * rows * C * C + 4 * rows * C * 32):
+            check(lib.hs_expand_ln_head_depth_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(target), kind, delta, f_out,
+                                                  ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), tokens, C, P, _lib.HS_BF16,
+                                                  stream_ptr(xn2.device)), "hs_expand_ln_head_depth_fwd")
+        tot = parts.sum(0)
+        ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp, target, tot)
+        ctx.kind, ctx.delta = kind, delta
+        ctx.w_cast = wq if wq.dtype != wexp.dtype else None
+        ctx.cast_cache = RT.cast_cache
+        return tot[0] / tot[1]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        xn2, y, mean, rstd, gamma, beta, weight, wexp, target, tot = ctx.saved_tensors
+        tokens, C = xn2.shape
+        scale = (dloss.to(torch.float32) / tot[1]).reshape(1)
+        dy, dgamma, dbeta, dw = _ln_head_backward(y, mean, rstd, gamma, beta, weight, None, any(ctx.needs_input_grad[2:5]),
+                                                  depth=(target, ctx.kind, ctx.delta, scale))
+        dy2 = dy.view(tokens, wexp.shape[0])
+        dxn = _input_grad(dy2, wexp, ctx.w_cast, None, ctx.cast_cache) if ctx.needs_input_grad[0] else None
+        ctx.w_cast = ctx.cast_cache = None
+        dwexp, _ = _param_grads(dy2, xn2, wexp, None, ctx.needs_input_grad[1], False)
+        return dxn, dwexp, dgamma, dbeta, dw, None, None, None, None
+
+
+def expand_ln_head_depth(xn2, wexp, gamma, beta, weight, target, kind, delta=1.0, xn_lo=None):
+    """Depth-regression loss (HS_DEPTH_* kind, losses.DEPTH_KINDS) of head(LayerNorm(expand(xn2 [+ xn_lo]) viewed per child))
+    against an fp32 per-pixel-row target, without the head rows (ExpandLnHeadDepthFn)."""
+    return ExpandLnHeadDepthFn.apply(xn2, wexp, gamma, beta, weight, target, int(kind), float(delta), xn_lo)
 
 
 def expand_ln_head_ce(xn2, wexp, gamma, beta, weight, labels, class_weights=None, xn_lo=None):

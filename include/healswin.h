@@ -321,6 +321,29 @@ int hs_seg_ce_bwd(const void* logits, const void* labels, const float* class_wei
                   int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth-regression losses of the depth caller (reference: heal_swin/training/loss_depth_regression.py, as
+ * heal_swin_amd/losses.py restates it), d = pred[:, 0] - target over the pixels whose target is not infinite (NaN targets are kept):
+ *     HS_DEPTH_L1 mean |d|,  HS_DEPTH_L2 mean d^2 / 2,  HS_DEPTH_HUBER SmoothL1(beta = huber_delta) (channels == 1 only),
+ *     HS_DEPTH_LOGVAR mean pred[:, 1] / 2 + d^2 exp(-pred[:, 1]) / 2 (channels >= 2).
+ * pred [dev] dtype HS_F32 / HS_BF16, element (b, c, pixel) at b*stride_b + c*stride_c + pixel*stride_p (the model's padded
+ * [B, Npix, 16] rows seen as [B, f_out, Npix] need no copy), channels <= 16; target [dev] f32[batch, npix] contiguous.
+ *   hs_depth_loss_fwd: partials [dev] f32[hs_depth_loss_partials(batch, npix)][2] = per-workgroup (sum, kept count); the caller
+ *                      sums them (fixed order) and divides (no kept pixel: 0 / 0 = NaN, as the reference's mean of nothing).
+ *   hs_depth_loss_bwd: dpred (own strides, every channel written) = scale[0] * dterm / dpred at kept pixels, exactly 0 elsewhere
+ *                      and in the channels the kind does not read; scale [dev] f32[1] = upstream gradient / kept count.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_DEPTH_L1 0
+#define HS_DEPTH_L2 1
+#define HS_DEPTH_HUBER 2
+#define HS_DEPTH_LOGVAR 3
+int64_t hs_depth_loss_partials(int64_t batch, int64_t npix);
+int hs_depth_loss_fwd(const void* pred, const float* target, float* partials, int64_t batch, int64_t npix, int channels,
+                      int64_t stride_b, int64_t stride_c, int64_t stride_p, int kind, float huber_delta, int dtype, void* stream);
+int hs_depth_loss_bwd(const void* pred, const float* target, const float* scale, void* dpred, int64_t batch, int64_t npix, int channels,
+                      int64_t stride_b, int64_t stride_c, int64_t stride_p, int64_t dstride_b, int64_t dstride_c, int64_t dstride_p,
+                      int kind, float huber_delta, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Weight / bias gradient of the path's Linear layers (autograd of nn.Linear at
  * models_torch/swin_hp_transformer.py:33,:35 (Mlp), :116,:118 (qkv, proj), :375 (PatchMerging.reduction), :415-416
  * (PatchExpand.expand), :438, :717 (concat_back_dim)):
@@ -704,6 +727,23 @@ int hs_expand_ln_head_ce_fwd(const void* xn, const void* xn_lo, const void* wexp
 int hs_ln_head_ce_bwd(const void* y, const float* mean, const float* rstd, const uint8_t* labels, const float* class_weights,
                       const float* scale, int n_classes, const void* wfold, const float* bvec, const void* afold, void* dy, void* dprime,
                       float* partials, int64_t rows, int width, int dtype, void* stream);
+
+/* The tail WITH the depth caller's loss (hs_depth_loss_fwd's kinds and semantics): the same forward kernel forms the depth term of
+ * every row from the fp32 head outputs it holds (channel 0 = mean, channel 1 = log variance for HS_DEPTH_LOGVAR) and writes
+ * per-wavefront (sum, kept count) partials; with logits == NULL the [4 tokens, 16] fp32 rows are never written.  The backward
+ * recomputes the head outputs from the saved y, forms dpred in registers (exactly 0 at rows whose target is infinite) and continues
+ * as hs_ln_head_bwd.  n_out (the head's f_out) is 1 or 2: HS_DEPTH_HUBER needs 1, HS_DEPTH_LOGVAR 2.
+ *   target [dev] f32[4 tokens] in pixel order (row = 4 token + child);
+ *   loss_partials [dev] f32[4 * hs_expand_ln_head_blocks(tokens), 2]: loss = sum(col 0) / sum(col 1);
+ *   wfold, bvec as for hs_expand_ln_head_fwd (unpermuted: the exchange of hs_ln_head_ce_bwd moves classes 4..11 only, so a head of
+ *   one or two channels sits in the same accumulator registers with either order);
+ *   backward: scale [dev] f32[1] = dloss / sum(col 1); afold, dy, dprime, partials as for hs_ln_head_bwd.  bf16, C in {64, 96, 128}. */
+int hs_expand_ln_head_depth_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const float* target,
+                                int kind, float huber_delta, int n_out, void* y, float* logits, float* mean, float* rstd, float* loss_partials,
+                                int64_t tokens, int width, int children, int dtype, void* stream);
+int hs_ln_head_depth_bwd(const void* y, const float* mean, const float* rstd, const float* target, int kind, float huber_delta,
+                         const float* scale, int n_out, const void* wfold, const float* bvec, const void* afold, void* dy, void* dprime,
+                         float* partials, int64_t rows, int width, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * PatchMerging / PatchExpand / FinalPatchExpand_X4 as one operator call per module and direction (SURVEY 8b's proposed
