@@ -1,0 +1,350 @@
+// The depth data path (heal_swin_amd/depth_data.py): the per-frame part of the reference's depth projection, the target
+// transforms of its datasets and Lightning module, and the dataset statistics behind their normalization constants.
+//
+//   hs_sample_bilinear_u8_f32  sample_bilinear(img, v, u).astype(np.float32)
+//                              (data/depth_estimation/project_depth_on_s2.py:48-77, :411): projection.hip's float64 arithmetic
+//                              and operation order, rounded once to float32; non-finite coordinates give NaN as in the reference.
+//   hs_sample_nearest_f32      sample_mask(depth, v, u, s2_bkgd_class) (:80-84, :412): nearest pixel by round-half-to-even,
+//                              an exact float32 copy, the background value outside the image.
+//   hs_depth_target            one elementwise pass over [batch, n] rows read and written through their own strides:
+//                              the datasets' target preparation (hp_depth_datasets.py:90-107, flat_depth_datasets.py:122-148),
+//                              transform_and_normalize and unnormalize_and_retransform (utils/depth_utils.py:60-104, :140-170).
+//   hs_depth_stats_update      compute_depth_stats.py's max / min / mean / std (ddof 0) / background count as a streaming
+//                              reduction: per-thread shifted sums, Chan merges in a fixed tree per workgroup, then one workgroup
+//                              merges the partials, in workgroup order, into the caller's state.  No float atomics: the same
+//                              inputs in the same calls give a bit-identical state.
+//
+// Transcendentals are formed in float64 and rounded once (fp32(log(double x)), fp32(exp(double x)), fp32(1 / double x)): a
+// float32 result that does not depend on the math library's float32 accuracy.  The affine steps are float32, unfused, as the
+// reference's tensor-with-scalar arithmetic.
+#include "hs_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kStatsBlocksMax = 1024;
+
+struct Corner {
+    bool ok;
+    int64_t off;
+};
+__device__ __forceinline__ Corner corner(double fx, double fy, int h, int w) {
+    // numpy's bounds test on the integer casts; doubles compare the same way, NaN and +-inf fail it
+    const bool ok = fx >= 0.0 && fx < (double)h && fy >= 0.0 && fy < (double)w;
+    return {ok, ok ? (int64_t)fx * w + (int64_t)fy : 0};
+}
+
+__global__ void __launch_bounds__(kThreads) sample_bilinear_u8_f32_kernel(const uint8_t* __restrict__ img, int planes, int h, int w,
+                                                                          const double* __restrict__ rx, const double* __restrict__ ry,
+                                                                          int64_t n, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = rx[i], y = ry[i];
+    const double x0 = floor(x), x1 = ceil(x), y0 = floor(y), y1 = ceil(y);
+    const Corner c00 = corner(x0, y0, h, w), c10 = corner(x1, y0, h, w), c01 = corner(x0, y1, h, w), c11 = corner(x1, y1, h, w);
+    const double wx0 = x1 - x, wx1 = x - x0, wy0 = y1 - y, wy1 = y - y0;  // NaN for NaN / +-inf coordinates: the result is NaN
+    const int64_t plane = (int64_t)h * w;
+    for (int p = 0; p < planes; ++p) {
+        const uint8_t* s = img + p * plane;
+        const double s00 = c00.ok ? (double)s[c00.off] : 0.0, s10 = c10.ok ? (double)s[c10.off] : 0.0;
+        const double s01 = c01.ok ? (double)s[c01.off] : 0.0, s11 = c11.ok ? (double)s[c11.off] : 0.0;
+        const double fx1 = wx0 * s00 + wx1 * s10;
+        const double fx2 = wx0 * s01 + wx1 * s11;
+        out[p * n + i] = (float)(wy0 * fx1 + wy1 * fx2);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) sample_nearest_f32_kernel(const float* __restrict__ src, int planes, int h, int w,
+                                                                      const double* __restrict__ rx, const double* __restrict__ ry,
+                                                                      int64_t n, float background, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Corner c = corner(rint(rx[i]), rint(ry[i]), h, w);  // np.around: round half to even
+    const int64_t plane = (int64_t)h * w;
+    for (int p = 0; p < planes; ++p) out[p * n + i] = c.ok ? src[p * plane + c.off] : background;
+}
+
+// ------------------------------------------------------------------ target transforms
+struct TargetOp {
+    int flags, transform;
+    float shift, scale;
+};
+
+// inverse_mask (depth_utils.py:60-72): +inf -> 0; x < 1e-3 (0, negatives, -inf) -> +inf; NaN stays; the rest 1 / x
+__device__ __forceinline__ float inverse_mask(float x) {
+    if (x == INFINITY) return 0.f;
+    if (x < 1e-3f) return INFINITY;
+    return (float)(1.0 / (double)x);
+}
+
+__device__ __forceinline__ float target_op(float x, const TargetOp& o) {
+    if (!(o.flags & HS_DT_INVERSE)) {
+        if ((o.flags & HS_DT_ZERO_BKG) && x == 0.f) x = INFINITY;
+        if ((o.flags & HS_DT_1000_BKG) && x == 1000.f) x = INFINITY;
+        if (o.transform == HS_DT_LOG) x = (float)log((double)x);
+        else if (o.transform == HS_DT_INV) x = inverse_mask(x);
+        if (o.flags & HS_DT_AFFINE) x = (x - o.shift) / o.scale;
+    } else {
+        if (o.flags & HS_DT_AFFINE) x = x * o.scale + o.shift;
+        if (o.transform == HS_DT_LOG) x = (float)exp((double)x);
+        else if (o.transform == HS_DT_INV) x = inverse_mask(x);
+    }
+    return x;
+}
+
+// grid (column blocks, rows): element i of row b at in[b * isb + i * isp]; out may be in itself (same element, same thread)
+__global__ void __launch_bounds__(kThreads) depth_target_kernel(const float* in, int64_t isb, int64_t isp, float* out,
+                                                                int64_t osb, int64_t osp, int64_t n, TargetOp o) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = blockIdx.y;
+    out[b * osb + i * osp] = target_op(in[b * isb + i * isp], o);
+}
+
+// unit-stride rows whose starts are 16-byte aligned and n % 4 == 0: four elements per lane, one 16-byte load and store
+__global__ void __launch_bounds__(kThreads) depth_target_vec4_kernel(const float* in, int64_t isb, float* out, int64_t osb,
+                                                                     int64_t n4, TargetOp o) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n4) return;
+    const int64_t b = blockIdx.y;
+    float4 v = ((const float4*)(in + b * isb))[i];
+    v.x = target_op(v.x, o);
+    v.y = target_op(v.y, o);
+    v.z = target_op(v.z, o);
+    v.w = target_op(v.w, o);
+    ((float4*)(out + b * osb))[i] = v;
+}
+
+// ------------------------------------------------------------------ dataset statistics
+// State, HS_DEPTH_STATS_WORDS 8-byte words: int64 counts [0, HS_DSTAT_NCOUNTS), then float64 mean / M2 (sum of squared deviations)
+// / min / max of the finite values and the max of the finite foreground values (raw value != 1000).
+struct Stats {
+    int64_t c[HS_DSTAT_NCOUNTS];
+    double mean, m2, mn, mx, fg_mx;
+};
+static_assert(sizeof(Stats) == HS_DEPTH_STATS_WORDS * 8, "state layout");
+
+__device__ __forceinline__ void stats_zero(Stats& s) {
+#pragma unroll
+    for (int k = 0; k < HS_DSTAT_NCOUNTS; ++k) s.c[k] = 0;
+    s.mean = 0.0;
+    s.m2 = 0.0;
+    s.mn = INFINITY;
+    s.mx = -INFINITY;
+    s.fg_mx = -INFINITY;
+}
+
+// a <- a (+) b: counts add, extrema combine, (mean, M2) by Chan et al.'s pairwise update
+__device__ __forceinline__ void stats_merge(Stats& a, const Stats& b) {
+    const int64_t na = a.c[HS_DSTAT_FINITE], nb = b.c[HS_DSTAT_FINITE];
+    if (nb > 0) {
+        if (na == 0) {
+            a.mean = b.mean;
+            a.m2 = b.m2;
+        } else {
+            const double n = (double)(na + nb);
+            const double delta = b.mean - a.mean;
+            a.mean = a.mean + delta * ((double)nb / n);
+            a.m2 = (a.m2 + b.m2) + delta * delta * ((double)na * (double)nb / n);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < HS_DSTAT_NCOUNTS; ++k) a.c[k] += b.c[k];
+    a.mn = fmin(a.mn, b.mn);
+    a.mx = fmax(a.mx, b.mx);
+    a.fg_mx = fmax(a.fg_mx, b.fg_mx);
+}
+
+// one raw value into the thread's accumulator: finite values as sums shifted by the thread's first finite value
+struct ThreadStats {
+    int64_t c[HS_DSTAT_NCOUNTS];
+    double shift, s1, s2, mn, mx, fg_mx;
+};
+
+template <int TRANSFORM>
+__device__ __forceinline__ void stats_add(ThreadStats& t, float raw, bool masking) {
+    const bool bkg = raw == 1000.f;
+    t.c[HS_DSTAT_TOTAL] += 1;
+    t.c[HS_DSTAT_BACKGROUND] += bkg;
+    if (masking && bkg) return;
+    float x = raw;
+    if (TRANSFORM == HS_DT_LOG) x = (float)log((double)raw);
+    else if (TRANSFORM == HS_DT_INV) x = (float)(1.0 / (double)raw);  // the script's plain 1 / x
+    t.c[HS_DSTAT_VALUES] += 1;
+    t.c[HS_DSTAT_FG_VALUES] += !bkg;
+    if (isnan(x)) {
+        t.c[HS_DSTAT_NAN] += 1;
+        t.c[HS_DSTAT_FG_NAN] += !bkg;
+    } else if (x == INFINITY) {
+        t.c[HS_DSTAT_POSINF] += 1;
+        t.c[HS_DSTAT_FG_POSINF] += !bkg;
+    } else if (x == -INFINITY) {
+        t.c[HS_DSTAT_NEGINF] += 1;
+    } else {
+        const double d = (double)x;
+        if (t.c[HS_DSTAT_FINITE] == 0) t.shift = d;
+        t.c[HS_DSTAT_FINITE] += 1;
+        const double e = d - t.shift;
+        t.s1 += e;
+        t.s2 += e * e;
+        t.mn = fmin(t.mn, d);
+        t.mx = fmax(t.mx, d);
+        if (!bkg) t.fg_mx = fmax(t.fg_mx, d);
+    }
+}
+
+__device__ __forceinline__ void block_merge(Stats& s, Stats* lds) {
+    lds[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if (threadIdx.x < h) stats_merge(lds[threadIdx.x], lds[threadIdx.x + h]);
+        __syncthreads();
+    }
+    s = lds[0];
+}
+
+template <int TRANSFORM>
+__global__ void __launch_bounds__(kThreads) depth_stats_kernel(const float* __restrict__ x, int64_t n, int vec4, int masking,
+                                                               Stats* __restrict__ partial) {
+    __shared__ Stats lds[kThreads];
+    ThreadStats t;
+#pragma unroll
+    for (int k = 0; k < HS_DSTAT_NCOUNTS; ++k) t.c[k] = 0;
+    t.shift = t.s1 = t.s2 = 0.0;
+    t.mn = INFINITY;
+    t.mx = t.fg_mx = -INFINITY;
+    const int64_t tid = (int64_t)blockIdx.x * kThreads + threadIdx.x, stride = (int64_t)gridDim.x * kThreads;
+    int64_t done = 0;
+    if (vec4) {
+        const int64_t n4 = n / 4;
+        for (int64_t i = tid; i < n4; i += stride) {
+            const float4 v = ((const float4*)x)[i];
+            stats_add<TRANSFORM>(t, v.x, masking);
+            stats_add<TRANSFORM>(t, v.y, masking);
+            stats_add<TRANSFORM>(t, v.z, masking);
+            stats_add<TRANSFORM>(t, v.w, masking);
+        }
+        done = n4 * 4;
+    }
+    for (int64_t i = done + tid; i < n; i += stride) stats_add<TRANSFORM>(t, x[i], masking);
+    Stats s;
+#pragma unroll
+    for (int k = 0; k < HS_DSTAT_NCOUNTS; ++k) s.c[k] = t.c[k];
+    const int64_t nf = t.c[HS_DSTAT_FINITE];
+    s.mean = nf ? t.shift + t.s1 / (double)nf : 0.0;
+    s.m2 = nf ? fmax(t.s2 - t.s1 * (t.s1 / (double)nf), 0.0) : 0.0;
+    s.mn = t.mn;
+    s.mx = t.mx;
+    s.fg_mx = t.fg_mx;
+    block_merge(s, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// one workgroup: thread j merges partials j, j + 256, ... in order, the fixed tree merges the threads, thread 0 adds the result to
+// the state.  states == partials of one call, or the gathered states of several ranks (count of them, merged in that order).
+__global__ void __launch_bounds__(kThreads) depth_stats_merge_kernel(const Stats* __restrict__ parts, int count, Stats* __restrict__ state) {
+    __shared__ Stats lds[kThreads];
+    Stats s;
+    stats_zero(s);
+    for (int j = threadIdx.x; j < count; j += kThreads) stats_merge(s, parts[j]);
+    block_merge(s, lds);
+    if (threadIdx.x == 0) {
+        Stats a = *state;
+        stats_merge(a, s);
+        *state = a;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int hs_sample_bilinear_u8_f32(const void* img, int batch, int channels, int height, int width, const double* rx, const double* ry,
+                              int64_t n, float* out, void* stream) {
+    HS_CHECK_ARG(batch > 0 && channels > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
+    HS_CHECK_ARG((int64_t)batch * channels < (1 << 20), "too many image planes");
+    if (n == 0) return HS_OK;
+    HS_CHECK_ARG(img && rx && ry && out, "null pointer");
+    hipLaunchKernelGGL(sample_bilinear_u8_f32_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, (const uint8_t*)img, batch * channels, height, width, rx, ry, n, out);
+    HS_LAUNCH_CHECK("sample_bilinear_u8_f32");
+    return HS_OK;
+}
+
+int hs_sample_nearest_f32(const float* src, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
+                          float background, float* out, void* stream) {
+    HS_CHECK_ARG(batch > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
+    HS_CHECK_ARG(batch < (1 << 20), "too many maps");
+    if (n == 0) return HS_OK;
+    HS_CHECK_ARG(src && rx && ry && out, "null pointer");
+    hipLaunchKernelGGL(sample_nearest_f32_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, src, batch, height, width, rx, ry, n, background, out);
+    HS_LAUNCH_CHECK("sample_nearest_f32");
+    return HS_OK;
+}
+
+int hs_depth_target(const float* in, int64_t in_stride_b, int64_t in_stride_p, float* out, int64_t out_stride_b, int64_t out_stride_p,
+                    int64_t batch, int64_t n, int flags, int transform, float shift, float scale, void* stream) {
+    HS_CHECK_ARG(batch >= 0 && batch <= 65535 && n >= 0, "bad shape (batch <= 65535)");
+    HS_CHECK_ARG((flags & ~(HS_DT_ZERO_BKG | HS_DT_1000_BKG | HS_DT_AFFINE | HS_DT_INVERSE)) == 0, "unknown flags %d", flags);
+    HS_CHECK_ARG(!((flags & HS_DT_INVERSE) && (flags & (HS_DT_ZERO_BKG | HS_DT_1000_BKG))), "background flags are forward only");
+    HS_CHECK_ARG(transform == HS_DT_NONE || transform == HS_DT_LOG || transform == HS_DT_INV, "transform %d", transform);
+    HS_CHECK_ARG(in_stride_b >= 0 && in_stride_p >= 0 && out_stride_b >= 0 && out_stride_p >= 0, "negative strides");
+    if (batch == 0 || n == 0) return HS_OK;
+    HS_CHECK_ARG(in && out, "null pointer");
+    const TargetOp o{flags, transform, shift, scale};
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = in_stride_p == 1 && out_stride_p == 1 && n % 4 == 0 && in_stride_b % 4 == 0 && out_stride_b % 4 == 0 &&
+                     (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0;
+    if (vec) {
+        const int64_t n4 = n / 4;
+        hipLaunchKernelGGL(depth_target_vec4_kernel, dim3((unsigned)((n4 + kThreads - 1) / kThreads), (unsigned)batch), dim3(kThreads), 0,
+                           s, in, in_stride_b, out, out_stride_b, n4, o);
+    } else {
+        hipLaunchKernelGGL(depth_target_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads), (unsigned)batch), dim3(kThreads), 0, s,
+                           in, in_stride_b, in_stride_p, out, out_stride_b, out_stride_p, n, o);
+    }
+    HS_LAUNCH_CHECK("depth_target");
+    return HS_OK;
+}
+
+int64_t hs_depth_stats_partials(int64_t n) {
+    const int64_t blocks = (n + kThreads * 16 - 1) / (kThreads * 16);
+    return std::max<int64_t>(1, std::min<int64_t>(blocks, kStatsBlocksMax));
+}
+
+int hs_depth_stats_update(const float* depth, int64_t n, int transform, int use_masking, int64_t* partial, int64_t* state, void* stream) {
+    HS_CHECK_ARG(n >= 0, "bad size");
+    HS_CHECK_ARG(transform == HS_DT_NONE || transform == HS_DT_LOG || transform == HS_DT_INV, "transform %d", transform);
+    if (n == 0) return HS_OK;
+    HS_CHECK_ARG(depth && partial && state, "null pointer");
+    const int blocks = (int)hs_depth_stats_partials(n);
+    const int vec4 = (uintptr_t)depth % 16 == 0;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(blocks), block(kThreads);
+    Stats* parts = (Stats*)partial;
+    if (transform == HS_DT_LOG)
+        hipLaunchKernelGGL(depth_stats_kernel<HS_DT_LOG>, grid, block, 0, s, depth, n, vec4, use_masking, parts);
+    else if (transform == HS_DT_INV)
+        hipLaunchKernelGGL(depth_stats_kernel<HS_DT_INV>, grid, block, 0, s, depth, n, vec4, use_masking, parts);
+    else
+        hipLaunchKernelGGL(depth_stats_kernel<HS_DT_NONE>, grid, block, 0, s, depth, n, vec4, use_masking, parts);
+    HS_LAUNCH_CHECK("depth_stats");
+    hipLaunchKernelGGL(depth_stats_merge_kernel, dim3(1), block, 0, s, (const Stats*)parts, blocks, (Stats*)state);
+    HS_LAUNCH_CHECK("depth_stats_merge");
+    return HS_OK;
+}
+
+int hs_depth_stats_merge(const int64_t* states, int count, int64_t* state, void* stream) {
+    HS_CHECK_ARG(count >= 0, "bad count");
+    if (count == 0) return HS_OK;
+    HS_CHECK_ARG(states && state, "null pointer");
+    hipLaunchKernelGGL(depth_stats_merge_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const Stats*)states, count,
+                       (Stats*)state);
+    HS_LAUNCH_CHECK("depth_stats_merge");
+    return HS_OK;
+}
+
+}  // extern "C"

@@ -654,6 +654,56 @@ int hs_backproject_depth(const void* pred, int kind, int64_t batch, int64_t npix
                          const double* wgt, int64_t n_out, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The depth data path (heal_swin_amd/depth_data.py): the per-frame sampling of data/depth_estimation/project_depth_on_s2.py
+ * (project_depth_dataset_hp :389-440, against hs_sample_*_u8's coordinate tables), the target transforms of the depth datasets
+ * and Lightning module, and compute_depth_stats.py's statistics.
+ *   hs_sample_bilinear_u8_f32  sample_bilinear(img, rx, ry).astype(np.float32) (:48-77): hs_sample_bilinear_u8's float64
+ *                       arithmetic rounded once to float32, NaN where a coordinate is not finite.  out [dev] f32[batch, channels, n].
+ *   hs_sample_nearest_f32  sample_mask(depth, rx, ry, background) (:80-84): src [dev] f32[batch, height, width] -> out [dev]
+ *                       f32[batch, n], nearest pixel by round-half-to-even, values copied exactly, background outside the image.
+ *   hs_depth_target     out[b * out_stride_b + i * out_stride_p] = op(in[b * in_stride_b + i * in_stride_p]) for b < batch (<= 65535),
+ *                       i < n; out may equal in.  Forward (no HS_DT_INVERSE): 0 -> inf if HS_DT_ZERO_BKG, 1000 -> inf if
+ *                       HS_DT_1000_BKG, the transform (HS_DT_LOG: log; HS_DT_INV: inverse_mask, utils/depth_utils.py:60-72), then
+ *                       (x - shift) / scale if HS_DT_AFFINE.  Inverse: x * scale + shift if HS_DT_AFFINE, then exp / inverse_mask.
+ *                       float32, transcendentals as fp32(f(double x)).
+ *   hs_depth_stats_update  ADDS one float32 array depth [dev] f32[n] (raw depths) into state [dev] (HS_DEPTH_STATS_WORDS words:
+ *                       int64 counts HS_DSTAT_*, then float64 mean, M2, min, max of the finite transformed values and the max of
+ *                       those whose raw value is not 1000).  use_masking drops raw 1000s (they are still counted as background);
+ *                       HS_DT_LOG: fp32(log x), HS_DT_INV: fp32(1 / x) (the script's plain reciprocal).  partial [dev]
+ *                       HS_DEPTH_STATS_WORDS * hs_depth_stats_partials(n) words of scratch.  Deterministic: no float atomics.
+ *   hs_depth_stats_merge  state (+)= states[0], ..., states[count - 1] (each HS_DEPTH_STATS_WORDS words, [dev]), in that order.
+ *                       A state starts as zero counts, mean = M2 = 0, min = +inf, max = fg max = -inf.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_DT_NONE 0
+#define HS_DT_LOG 1
+#define HS_DT_INV 2
+#define HS_DT_ZERO_BKG 1
+#define HS_DT_1000_BKG 2
+#define HS_DT_AFFINE 4
+#define HS_DT_INVERSE 8
+#define HS_DSTAT_TOTAL 0      /* raw values seen */
+#define HS_DSTAT_BACKGROUND 1 /* raw values == 1000 */
+#define HS_DSTAT_VALUES 2     /* values kept (all, or the non-1000 ones with use_masking) */
+#define HS_DSTAT_FINITE 3     /* kept values finite after the transform */
+#define HS_DSTAT_POSINF 4     /*   +inf */
+#define HS_DSTAT_NEGINF 5     /*   -inf */
+#define HS_DSTAT_NAN 6        /*   NaN */
+#define HS_DSTAT_FG_VALUES 7  /* kept values whose raw value is not 1000 */
+#define HS_DSTAT_FG_POSINF 8  /*   +inf */
+#define HS_DSTAT_FG_NAN 9     /*   NaN */
+#define HS_DSTAT_NCOUNTS 10
+#define HS_DEPTH_STATS_WORDS 15
+int hs_sample_bilinear_u8_f32(const void* img, int batch, int channels, int height, int width, const double* rx, const double* ry,
+                              int64_t n, float* out, void* stream);
+int hs_sample_nearest_f32(const float* src, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
+                          float background, float* out, void* stream);
+int hs_depth_target(const float* in, int64_t in_stride_b, int64_t in_stride_p, float* out, int64_t out_stride_b, int64_t out_stride_p,
+                    int64_t batch, int64_t n, int flags, int transform, float shift, float scale, void* stream);
+int64_t hs_depth_stats_partials(int64_t n);
+int hs_depth_stats_update(const float* depth, int64_t n, int transform, int use_masking, int64_t* partial, int64_t* state, void* stream);
+int hs_depth_stats_merge(const int64_t* states, int count, int64_t* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Decoder tail: LayerNorm(C) of FinalPatchExpand_X4 + the 1x1 class head in one pass, so that the normalised
  * [B, 4 N0, C] tensor is never written.  Replaces `self.norm(x)` (models_torch/swin_hp_transformer.py:448-452) followed by
  * `self.output(x)` (:756-761, :785-788) and their backward.  bf16 rows, C in {64, 96, ..., 256}, <= 16 classes.
