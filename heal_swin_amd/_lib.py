@@ -33,6 +33,21 @@ c_uint = ctypes.c_uint
 c_ptr = ctypes.c_void_p
 c_float = ctypes.c_float
 
+
+class WgradProblem(ctypes.Structure):
+    """`hs_wgrad_problem` (include/healswin.h): one member of an hs_linear_wgrad_group call."""
+    _fields_ = [("dy", c_ptr), ("x", c_ptr), ("dw", c_ptr), ("dbias", c_ptr), ("n_out", c_int), ("k_in", c_int), ("accumulate", c_int),
+                ("gelu_x", c_int)]
+
+
+def wgrad_problems(members):
+    """ctypes array of hs_wgrad_problem from (dy, x, dw, dbias or None, n_out, k_in, accumulate, gelu_x) tuples of tensors / ints."""
+    arr = (WgradProblem * len(members))()
+    for q, (dy, x, dw, db, n_out, k_in, acc, gelu_x) in zip(arr, members):
+        q.dy, q.x, q.dw, q.dbias = dy.data_ptr(), x.data_ptr(), dw.data_ptr(), (None if db is None else db.data_ptr())
+        q.n_out, q.k_in, q.accumulate, q.gelu_x = int(n_out), int(k_in), int(acc), int(bool(gelu_x))
+    return arr
+
 # name -> argtypes; every function returns int status unless listed in _OTHER_RESTYPE
 _SIGNATURES = {
     "hs_nest2ring": [c_int, c_ptr, c_ptr, c_i64],
@@ -102,6 +117,8 @@ _SIGNATURES = {
     "hs_set_seed_epoch": [c_ptr],
     "hs_linear_wgrad_gelu": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr],
     "hs_linear_wgrad_gelu_supported": [c_i64, c_int, c_int, c_int],
+    "hs_linear_wgrad_group_variant": [c_i64, c_int, c_int, c_int],
+    "hs_linear_wgrad_group": [c_ptr, c_int, c_ptr, c_i64, c_int, c_ptr],
     "hs_mlp_fused_supported": [c_int, c_int, c_int],
     "hs_mlp_fused_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_uint,
                          c_int, c_ptr],
@@ -169,6 +186,7 @@ _OTHER = {
     "hs_ln_head_partials": ([c_i64], c_i64),
     "hs_expand_ln_head_blocks": ([c_i64], c_i64),
     "hs_linear_wgrad_workspace": ([c_i64, c_int, c_int], c_i64),
+    "hs_linear_wgrad_group_workspace": ([c_ptr, c_int, c_i64, c_int], c_i64),
     "hs_window_attn_bwd_workspace": ([c_int, c_i64, c_int, c_int, c_int, c_int], c_i64),
     "hs_patch_merge_bwd_workspace": ([c_i64, c_int, c_int], c_i64),
     "hs_window_attn_module_bwd_chain_workspace": ([c_int, c_i64, c_int, c_int, c_int], c_i64),

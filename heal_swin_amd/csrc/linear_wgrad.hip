@@ -270,10 +270,28 @@ __device__ __forceinline__ s16x8 tr_frag_asm(uint32_t a, int ks) {
 // Mlp block, csrc/mlp_fused.hip, which then does not write gelu(h) at all).  The activation is applied to the MFMA fragments
 // between their LDS read and the product: 16 packed evaluations per stage and wave, which an HBM-bound launch (C <= 128: the only
 // shapes that use it) has the VALU slots for.
+//
+// GROUPED LAUNCHES: the kernel takes a table of up to kMaxGroup problems (Linear layers over the same token rows) instead of one.
+// The work ids of a token slice run over the output tiles of ALL members (g.tiles = their sum, member i owns the tile range
+// starting at first_tile), so the chip is filled by more output tiles and each member needs fewer token slices: fewer partial
+// tiles to write and to sum.  A workgroup looks its member up once, from its (uniform) tile id, and builds its buffer
+// descriptors from it; everything behind that is the single-problem kernel.  GX instantiations apply the GELU only for members
+// whose `gelu` flag is set (uniform branch), so a group may mix plain and GELU members.
+constexpr int kMaxGroup = 4;
+struct Member {
+    const uint16_t* dy;
+    const uint16_t* x;
+    float* part_w;  // this member's partial records [slices][n_out * k_in + n_out]
+    float* part_b;  // part_w + n_out * k_in, or null (no bias gradient)
+    int n_out, k_in, ldy, ldx, yc0, xc0, tiles_k, first_tile, gelu;
+};
+struct MemberTable {
+    int count;
+    Member m[kMaxGroup];
+};
+
 template <int NB, int TK, bool GX = false>
-__global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
-                                                           float* __restrict__ part_w, float* __restrict__ part_b,
-                                                           int64_t rows, int n_out, int k_in, Geometry g, int ldy, int ldx, int yc0, int xc0) {
+__global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable tb, int64_t rows, Geometry g) {
     // ldy / ldx: row strides of dY / X in elements; yc0 / xc0: first column of the operand inside its row (the operands may be
     // column blocks of wider matrices -- the hi / lo parts of a bf16x3 split, ops.split3).  The descriptors cover whole rows of the
     // WIDE matrices, so a tile that overhangs the operand's columns reads its neighbours (never stored), not unmapped memory
@@ -294,7 +312,19 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const uint16_t* __
     const int wn = wave / WK, wk = wave % WK;
     int slice, tile;
     if (!block_to_work(g, blockIdx.x, slice, tile)) return;
-    const int tn = tile / g.tiles_k, tk = tile % g.tiles_k;
+    int mi = 0;  // the member that owns this tile (uniform: a handful of scalar compares)
+#pragma unroll
+    for (int i = 1; i < kMaxGroup; ++i)
+        if (i < tb.count && tile >= tb.m[i].first_tile) mi = i;
+    const Member& mb = tb.m[__builtin_amdgcn_readfirstlane(mi)];
+    const uint16_t* __restrict__ dy = mb.dy;
+    const uint16_t* __restrict__ x = mb.x;
+    float* __restrict__ part_w = mb.part_w;
+    float* __restrict__ part_b = mb.part_b;
+    const int n_out = mb.n_out, k_in = mb.k_in, ldy = mb.ldy, ldx = mb.ldx, yc0 = mb.yc0, xc0 = mb.xc0;
+    [[maybe_unused]] const bool gelu = mb.gelu != 0;
+    tile -= mb.first_tile;
+    const int tn = tile / mb.tiles_k, tk = tile % mb.tiles_k;
     const int n0 = tn * TN, k0 = tk * TK;
     const int64_t m_begin = (int64_t)slice * g.rows_per_slice;
     int64_t m_end = m_begin + g.rows_per_slice;
@@ -382,15 +412,17 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const uint16_t* __
     };
     auto mma_half = [&](int ks) {
         if constexpr (GX) {
+            if (gelu) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                u32x4 w = __builtin_bit_cast(u32x4, bf[ks][j]);
+                for (int j = 0; j < 2; ++j) {
+                    u32x4 w = __builtin_bit_cast(u32x4, bf[ks][j]);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const f32x2 v = gelu2(f32x2{__uint_as_float(w[e] << 16), __uint_as_float(w[e] & 0xffff0000u)});
-                    w[e] = pack_bf16x2(v.x, v.y);
+                    for (int e = 0; e < 4; ++e) {
+                        const f32x2 v = gelu2(f32x2{__uint_as_float(w[e] << 16), __uint_as_float(w[e] & 0xffff0000u)});
+                        w[e] = pack_bf16x2(v.x, v.y);
+                    }
+                    bf[ks][j] = __builtin_bit_cast(s16x8, w);
                 }
-                bf[ks][j] = __builtin_bit_cast(s16x8, w);
             }
         }
 #pragma unroll
@@ -709,6 +741,76 @@ __global__ void __launch_bounds__(256, 3) wgrad_dma_f32_kernel(const float* __re
 #endif
 }
 
+// Which LDS-DMA kernel a bf16 problem runs on: 0 = none (register-staged kernels), 1 = 256 x 256, 2 = 256 x 128, 3 = 128 x 128
+inline int dma_variant(const Geometry& g) { return !g.dma ? 0 : (g.tile_k == 256 ? 1 : (g.tile_n == 256 ? 2 : 3)); }
+
+inline void launch_dma(int variant, bool any_gelu, dim3 grid, hipStream_t s, const MemberTable& tb, int64_t rows, const Geometry& g) {
+    if (variant == 1)
+        hipLaunchKernelGGL((wgrad_dma_kernel<4, 256>), grid, dim3(512), 0, s, tb, rows, g);
+    else if (variant == 2)
+        hipLaunchKernelGGL((wgrad_dma_kernel<4, 128>), grid, dim3(256), 0, s, tb, rows, g);
+    else if (any_gelu)
+        hipLaunchKernelGGL((wgrad_dma_kernel<2, 128, true>), grid, dim3(256), 0, s, tb, rows, g);
+    else
+        hipLaunchKernelGGL((wgrad_dma_kernel<2, 128>), grid, dim3(256), 0, s, tb, rows, g);
+}
+
+// One launch for several bf16 problems over the same token rows: possible when each of them, launched alone, takes the same
+// LDS-DMA tile variant.  The slice count then comes from the SUM of their tiles (one resident round, as for a single problem).
+// offset[i]: member i's partial records inside the shared workspace (floats).  Not grouped: each member keeps the geometry
+// and the workspace extent of its own launch.
+struct GroupPlan {
+    bool grouped;
+    int variant, any_gelu;
+    Geometry g;
+    int first_tile[kMaxGroup], tiles_k[kMaxGroup];
+    int64_t offset[kMaxGroup], total;
+};
+
+inline GroupPlan plan_group(const hs_wgrad_problem* p, int count, int64_t rows, int dtype) {
+    GroupPlan pl{};
+    pl.grouped = dtype == HS_BF16 && count > 1;
+    int tiles = 0;
+    for (int i = 0; i < count && pl.grouped; ++i) {
+        if (p[i].n_out <= 0 || p[i].k_in <= 0 || p[i].n_out % 4 || p[i].k_in % 8) pl.grouped = false;
+        if (!pl.grouped) break;
+        const Geometry gi = make_geometry(rows, p[i].n_out, p[i].k_in);
+        const int v = dma_variant(gi);
+        if (i == 0) {
+            pl.variant = v;
+            pl.g = gi;
+        }
+        if (v == 0 || v != pl.variant || (p[i].gelu_x && v != 3)) pl.grouped = false;
+        pl.first_tile[i] = tiles;
+        pl.tiles_k[i] = gi.tiles_k;
+        pl.any_gelu |= p[i].gelu_x ? 1 : 0;
+        tiles += gi.tiles;
+    }
+    if (pl.grouped) {
+        Geometry& g = pl.g;
+        g.tiles = tiles;
+        int64_t want = ((int64_t)usable_cus() * (pl.variant == 1 ? 1 : 2)) / tiles;
+        const int64_t max_by_rows = (rows + 511) / 512;
+        if (want > max_by_rows) want = max_by_rows;
+        if (want > kMaxSlices) want = kMaxSlices;
+        if (want < 1) want = 1;
+        g.slices = (int)want;
+        const int64_t rps = (rows + g.slices - 1) / g.slices;
+        g.rows_per_slice = ((rps + kTok - 1) / kTok) * kTok;
+        g.per_xcd = (g.slices * g.tiles + 7) / 8;
+        for (int i = 0; i < count; ++i)  // longer slices than alone: every member must still fit the 32-bit buffer offsets
+            if (g.rows_per_slice * (int64_t)(p[i].n_out > p[i].k_in ? p[i].n_out : p[i].k_in) * 2 >= ((int64_t)1 << 31)) pl.grouped = false;
+    }
+    int64_t off = 0;
+    for (int i = 0; i < count; ++i) {
+        pl.offset[i] = off;
+        off += pl.grouped ? (int64_t)pl.g.slices * ((int64_t)p[i].n_out * p[i].k_in + p[i].n_out)
+                          : hs_linear_wgrad_workspace(rows, p[i].n_out, p[i].k_in);
+    }
+    pl.total = off;
+    return pl;
+}
+
 }  // namespace
 }  // namespace hs
 
@@ -785,15 +887,12 @@ int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, fl
     if (dtype == HS_F32)
         hipLaunchKernelGGL(wgrad_dma_f32_kernel, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, part_w, part_b, rows, n_out,
                            k_in, g);
-    else if (g.dma && g.tile_k == 256)
-        hipLaunchKernelGGL((wgrad_dma_kernel<4, 256>), grid, dim3(512), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g, ldy, ldx, yc0, xc0);
-    else if (g.dma && g.tile_n == 256)
-        hipLaunchKernelGGL((wgrad_dma_kernel<4, 128>), grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g, ldy, ldx, yc0, xc0);
-    else if (g.dma && gelu_x)
-        hipLaunchKernelGGL((wgrad_dma_kernel<2, 128, true>), grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g, ldy, ldx, yc0, xc0);
-    else if (g.dma)
-        hipLaunchKernelGGL((wgrad_dma_kernel<2, 128>), grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g, ldy, ldx, yc0, xc0);
-    else if (g.tile_n == 256)
+    else if (g.dma) {  // a group of one: the same slices, tiles and summation order as before the kernels took a table
+        MemberTable tb{};
+        tb.count = 1;
+        tb.m[0] = Member{dyp, xp, part_w, part_b, n_out, k_in, ldy, ldx, yc0, xc0, g.tiles_k, 0, gelu_x ? 1 : 0};
+        launch_dma(dma_variant(g), gelu_x, grid, s, tb, rows, g);
+    } else if (g.tile_n == 256)
         hipLaunchKernelGGL(wgrad_kernel<4>, grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g);
     else
         hipLaunchKernelGGL(wgrad_kernel<2>, grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g);
@@ -804,5 +903,53 @@ int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, fl
     return reduce_now(part_w, rec, g.slices, n, count, dw, dbias, accumulate & 1, s);
 }
 }  // namespace
+
+int hs_linear_wgrad_group_variant(int64_t rows, int n_out, int k_in, int dtype) {
+    if (dtype != HS_BF16 || rows <= 0 || n_out <= 0 || k_in <= 0 || n_out % 4 || k_in % 8) return 0;
+    return hs::dma_variant(hs::make_geometry(rows, n_out, k_in));
+}
+
+int64_t hs_linear_wgrad_group_workspace(const hs_wgrad_problem* problems, int count, int64_t rows, int dtype) {
+    if (!problems || count < 1 || count > hs::kMaxGroup || rows <= 0) return 0;
+    return hs::plan_group(problems, count, rows, dtype).total;
+}
+
+int hs_linear_wgrad_group(const hs_wgrad_problem* problems, int count, float* workspace, int64_t rows, int dtype, void* stream) {
+    using namespace hs;
+    HS_CHECK_ARG(problems && workspace, "null pointer");
+    HS_CHECK_ARG(count >= 1 && count <= kMaxGroup, "hs_linear_wgrad_group: 1 to 4 problems");
+    HS_CHECK_ARG(rows > 0, "bad shape");
+    HS_CHECK_ARG(dtype == HS_BF16 || dtype == HS_F32, "dtype must be HS_F32 or HS_BF16");
+    const GroupPlan pl = plan_group(problems, count, rows, dtype);
+    if (!pl.grouped) {  // members that take different kernels when launched alone: one launch each, results as from the single entry points
+        for (int i = 0; i < count; ++i) {
+            const hs_wgrad_problem& p = problems[i];
+            if (int st = linear_wgrad_impl(p.dy, p.x, p.dw, p.dbias, workspace + pl.offset[i], rows, p.n_out, p.k_in, p.accumulate, dtype,
+                                           stream, p.n_out, p.k_in, 0, 0, p.gelu_x != 0))
+                return st;
+        }
+        return HS_OK;
+    }
+    MemberTable tb{};
+    tb.count = count;
+    for (int i = 0; i < count; ++i) {
+        const hs_wgrad_problem& p = problems[i];
+        HS_CHECK_ARG(p.dy && p.x && p.dw, "null pointer");
+        float* part = workspace + pl.offset[i];
+        tb.m[i] = Member{(const uint16_t*)p.dy, (const uint16_t*)p.x, part, p.dbias ? part + (int64_t)p.n_out * p.k_in : nullptr,
+                         p.n_out, p.k_in, p.n_out, p.k_in, 0, 0, pl.tiles_k[i], pl.first_tile[i], p.gelu_x ? 1 : 0};
+    }
+    hipStream_t s = (hipStream_t)stream;
+    launch_dma(pl.variant, pl.any_gelu != 0, dim3((unsigned)(8 * pl.g.per_xcd)), s, tb, rows, pl.g);
+    HS_LAUNCH_CHECK("linear_wgrad_group");
+    for (int i = 0; i < count; ++i) {  // one slice sum per member, with the group's slice count
+        const hs_wgrad_problem& p = problems[i];
+        const int64_t n = (int64_t)p.n_out * p.k_in, rec = n + p.n_out, cnt = p.dbias ? rec : n;
+        const int st = (p.accumulate & HS_ACC_DEFER) ? reduce_defer(tb.m[i].part_w, rec, pl.g.slices, n, cnt, p.dw, p.dbias, p.accumulate & 1, s)
+                                                     : reduce_now(tb.m[i].part_w, rec, pl.g.slices, n, cnt, p.dw, p.dbias, p.accumulate & 1, s);
+        if (st) return st;
+    }
+    return HS_OK;
+}
 
 }  // extern "C"

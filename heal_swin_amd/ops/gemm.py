@@ -7,6 +7,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
+from . import runtime
 from .runtime import RT, _cast_param, _defer_flag, _defer_keep, _require_gpu, _sink_buffer, _timed  # noqa: F401
 
 
@@ -320,6 +321,48 @@ def _cast_param_t(p, dtype, cache=None):
     return c
 
 
+def _wgrad_group_ok(dy2, x2, n_out, k_in, want_b, bbuf, x3):
+    """Whether this deposit may share a launch with its neighbour (hs_linear_wgrad_group): a deferred bf16 deposit on the 256 x 256
+    tile (C >= 256: the stages where the partial tiles of a launch cost as much as its prologue)."""
+    return bool(runtime.WGRAD_GROUP and x3 is None and x2 is not None and x2.dtype == torch.bfloat16 and dy2.dtype == torch.bfloat16 and
+                (bbuf is not None or not want_b) and _defer_flag(dy2.device) and
+                lib.hs_linear_wgrad_group_variant(dy2.shape[0], n_out, k_in, _lib.HS_BF16) == 1)
+
+
+def _wgrad_issue(members, dev):
+    """One hs_linear_wgrad_group launch for 1-2 parked problems (a single one runs exactly as hs_linear_wgrad would)."""
+    rows = members[0][0].shape[0]
+    arr = _lib.wgrad_problems(members)
+    ws = torch.empty(int(lib.hs_linear_wgrad_group_workspace(arr, len(members), rows, _lib.HS_BF16)), dtype=torch.float32, device=dev)
+    with _timed("linear_wgrad" if len(members) == 1 else "linear_wgrad group", dev, sum(2 * rows * (m[4] + m[5]) for m in members),
+                sum(2 * rows * m[4] * m[5] for m in members)):
+        check(lib.hs_linear_wgrad_group(arr, len(members), ptr(ws), rows, _lib.HS_BF16, stream_ptr(dev)), "hs_linear_wgrad_group")
+    _defer_keep(dev, ws)
+
+
+def _wgrad_grouped(member):
+    """Park the problem, or launch it together with the one parked on this stream (same token rows: the other Linear of the block
+    half).  A parked problem whose partner never comes is launched alone by the next non-matching deposit or by flush_reductions."""
+    dev = member[0].device
+    s = torch.cuda.current_stream(dev).cuda_stream
+    parked = runtime._PARKED.pop(s, None)
+    if parked is not None and parked[0].shape[0] == member[0].shape[0]:
+        _wgrad_issue([parked, member], dev)
+        return
+    if parked is not None:
+        _wgrad_issue([parked], dev)
+    runtime._PARKED[s] = member
+
+
+def _wgrad_flush_parked(s, device=None):
+    parked = runtime._PARKED.pop(s, None)
+    if parked is not None:
+        _wgrad_issue([parked], parked[0].device)
+
+
+runtime._PARK_FLUSH[:] = [_wgrad_flush_parked]
+
+
 def _param_grads(dy2, x2, weight, bias, want_w, want_b, x3=None, gelu_x=False):
     """Weight / bias gradient of y = x W^T + b from dy2 [rows, n_out], x2 [rows, k_in]: deposited straight into the gradient
     sink's buffers when one knows the parameters (returns (None, None)), else returned in the parameters' dtype.
@@ -349,6 +392,8 @@ def _param_grads(dy2, x2, weight, bias, want_w, want_b, x3=None, gelu_x=False):
             (x2 if x2 is not None else x3).record_stream(aw.stream)
             with torch.cuda.stream(aw.stream):
                 LinearFn._wgrad_hip(dy2, x2, n_out, k_in, want_b, wbuf, bbuf, x3, gelu_x)
+        elif _wgrad_group_ok(dy2, x2, n_out, k_in, want_b, bbuf, x3):
+            _wgrad_grouped((dy2, x2, wbuf, bbuf if want_b else None, n_out, k_in, 1 | _lib.HS_ACC_DEFER, gelu_x))
         else:
             LinearFn._wgrad_hip(dy2, x2, n_out, k_in, want_b, wbuf, bbuf, x3, gelu_x)
         RT.grad_sink.deposited(weight)

@@ -133,6 +133,11 @@ def _sink_buffer(p):
 DEFER_REDUCTIONS = os.environ.get("HS_DEFER_REDUCE", "1") != "0"
 _DEFER_KEEP = {}   # stream handle -> workspaces of the queued sums
 _DEFER_FLUSH_AT = 32
+# Grouped weight gradients (hs_linear_wgrad_group): the first Linear of a block half (fc2, proj) parks its problem, the
+# next one over the same rows (fc1, qkv) launches both together.  HS_WGRAD_GROUP=0: one launch per Linear (A/B runs).
+WGRAD_GROUP = os.environ.get("HS_WGRAD_GROUP", "1") != "0"
+_PARKED = {}      # stream handle -> the parked problem (gemm._wgrad_grouped); flush_reductions launches a leftover alone
+_PARK_FLUSH = []  # [gemm._wgrad_flush_parked]
 
 
 def _defer_flag(device):
@@ -157,6 +162,8 @@ def flush_reductions(device=None):
     if not torch.cuda.is_available():
         return
     s = torch.cuda.current_stream(device).cuda_stream
+    if s in _PARKED:  # a weight gradient still waiting for a partner is launched alone: nothing is lost
+        _PARK_FLUSH[0](s, device)
     check(lib.hs_reduce_flush(ctypes.c_void_p(s)), "hs_reduce_flush")
     keep = _DEFER_KEEP.get(s)
     if keep:

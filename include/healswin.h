@@ -365,6 +365,26 @@ int hs_linear_wgrad(const void* dy, const void* x, float* dw, float* dbias, floa
 int hs_linear_wgrad_gelu_supported(int64_t rows, int n_out, int k_in, int dtype);
 int hs_linear_wgrad_gelu(const void* dy, const void* h, float* dw, float* dbias, float* workspace, int64_t rows, int n_out, int k_in,
                          int accumulate, int dtype, void* stream);
+/* Several weight gradients over the SAME token rows in one launch (the Linear layers of one block half: fc2 + fc1, proj + qkv).
+ * A launch is one resident round of workgroups whatever the layer is, so the slice count follows from the number of output tiles;
+ * with the tiles of 2-4 layers in one launch each layer needs that many fewer token slices, i.e. fewer partial tiles to write and to
+ * sum.  A problem is what the single entry points take: dy [rows, n_out], x [rows, k_in] (gelu_x != 0: x is the pre-activation
+ * and gelu(x) the operand, as hs_linear_wgrad_gelu), dw, dbias (may be NULL), accumulate (bit 0 | HS_ACC_DEFER), per problem.
+ * Problems share one launch when each of them alone takes the same LDS-DMA tile (hs_linear_wgrad_group_variant: equal and non-zero;
+ * 1 = 256 x 256, 2 = 256 x 128, 3 = 128 x 128; bf16 only); otherwise the call launches them one by one, as the single entry points
+ * would.  Results equal those of the single entry points up to the summation order over the token slices (deterministic either way).
+ * workspace [dev] f32[hs_linear_wgrad_group_workspace(...)]: every problem has its own partial records in it, so a deferring caller
+ * keeps it until the flush, as with the single entry points. */
+typedef struct hs_wgrad_problem {
+    const void* dy;
+    const void* x;
+    float* dw;
+    float* dbias;
+    int n_out, k_in, accumulate, gelu_x;
+} hs_wgrad_problem;
+int hs_linear_wgrad_group_variant(int64_t rows, int n_out, int k_in, int dtype);
+int64_t hs_linear_wgrad_group_workspace(const hs_wgrad_problem* problems, int count, int64_t rows, int dtype);
+int hs_linear_wgrad_group(const hs_wgrad_problem* problems, int count, float* workspace, int64_t rows, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Deferred parameter-gradient reductions.  hs_linear_wgrad / hs_linear_wgrad_ld and the four LayerNorm backward entry points
