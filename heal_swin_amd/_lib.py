@@ -104,6 +104,9 @@ _SIGNATURES = {
     "hs_depth_metrics": [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_int, c_i64, c_i64, c_i64, c_int,
                          ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     "hs_backproject_depth": [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "hs_flat_depth_to_hp": [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "hs_depth_metrics_gather": [c_ptr, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_int, c_i64, c_i64,
+                                c_int, ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     "hs_sample_bilinear_u8_f32": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_sample_nearest_f32": [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_float, c_ptr, c_ptr],
     "hs_depth_target": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_float, c_float, c_ptr],

@@ -29,8 +29,12 @@
 
 #pragma clang fp contract(off)
 
+#include "hs_depth_metrics.h"
+
 namespace hs {
 namespace {
+
+using depth_metrics::block_sum;
 
 constexpr int kThreads = 256;
 constexpr int kPtsPer = 8;                     // pixels per lane in the compaction kernels
@@ -38,9 +42,6 @@ constexpr int kPtsChunk = kThreads * kPtsPer;  // pixels per compaction workgrou
 constexpr int kQ = 8;                          // query points per lane in the Chamfer pass
 constexpr int kTile = 512;                     // target points per LDS tile
 constexpr int kMaxBg = 4;
-constexpr int kMaxRanges = 8;
-constexpr int kNSums = HS_DEPTH_NSUMS;
-constexpr int kMetricBlocksMax = 1024;
 
 // ------------------------------------------------------------------ point clouds
 struct DepthIn {
@@ -283,18 +284,6 @@ __global__ void __launch_bounds__(kThreads) chamfer_unpack_kernel(const unsigned
     if (idx) idx[i] = set ? (int64_t)(uint32_t)w : -1;
 }
 
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-    lds[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = kThreads / 2; h > 0; h >>= 1) {
-        if (threadIdx.x < h) lds[threadIdx.x] += lds[threadIdx.x + h];
-        __syncthreads();
-    }
-    const double r = lds[0];
-    __syncthreads();
-    return r;
-}
-
 // one workgroup per sample: term[s] = mean(dist_a) + mean(dist_b) in float64 (NaN when a cloud is empty: 0 / 0)
 __global__ void __launch_bounds__(kThreads) chamfer_term_kernel(const float* __restrict__ da, const int64_t* __restrict__ a_off,
                                                                 const float* __restrict__ db, const int64_t* __restrict__ b_off,
@@ -319,95 +308,27 @@ struct MetricIn {
     int tkind;
     int64_t tb, th, tw;
     int64_t width, n, batch;
-    int use_logvar, n_ranges;
-    double total_mean;
-    float lo[kMaxRanges], hi[kMaxRanges];
+    depth_metrics::Rule rule;
 };
 
-template <typename C>
-__device__ __forceinline__ C load_val(const void* p, int kind, int64_t off) {
-    if (kind == HS_F64) return (C)((const double*)p)[off];
-    if (kind == HS_BF16) return (C)bf16_to_float(((const uint16_t*)p)[off]);
-    return (C)((const float*)p)[off];
-}
-
-__device__ __forceinline__ float log_c(float x) { return logf(x); }
-__device__ __forceinline__ double log_c(double x) { return log(x); }
-__device__ __forceinline__ float std_of(float lv) { return sqrtf(expf(lv)); }
-__device__ __forceinline__ double std_of(double lv) { return sqrt(exp(lv)); }
-template <typename C>
-__device__ __forceinline__ C inv_km(C x) {  // DepthiRMSE's 1 / (0.001 x), the scalar in the tensor's own type
-    return (C)1 / ((C)0.001 * x);
-}
-
-// P, T: the types the reference computes in for the prediction and the target (float for fp32 / bf16 tensors, double for the
-// float64 back-projected predictions); a per-element value is formed in those types, every sum in float64
+// P, T: the types the reference computes in for the prediction and the target (hs_depth_metrics.h holds the per-element rules)
 template <typename P, typename T>
 __global__ void __launch_bounds__(kThreads) depth_metrics_kernel(MetricIn a, double* __restrict__ partial) {
+    using depth_metrics::load_val;
     __shared__ double lds[kThreads];
-    double acc[kNSums];
+    double acc[depth_metrics::kNSums];
 #pragma unroll
-    for (int k = 0; k < kNSums; ++k) acc[k] = 0.0;
+    for (int k = 0; k < depth_metrics::kNSums; ++k) acc[k] = 0.0;
     const int64_t total = a.n * a.batch;
-    const double tm = (double)a.total_mean;
     for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
         const int64_t b = e / a.n, i = e - b * a.n;
         const int64_t h = i / a.width, w = i - h * a.width;
         const int64_t po = b * a.sb + h * a.sh + w * a.sw;
         const P p = load_val<P>(a.pred, a.kind, po);
         const T t = load_val<T>(a.target, a.tkind, b * a.tb + h * a.th + w * a.tw);
-        if (isfinite(p) && isfinite(t)) {  // get_non_inf_non_nan_idxs
-            const double d = (double)p - (double)t;
-            const double dm = tm - (double)t;
-            acc[HS_DS_N] += 1.0;
-            acc[HS_DS_SE] += d * d;
-            acc[HS_DS_AE] += fabs(d);
-            acc[HS_DS_MEAN_SE] += dm * dm;
-            acc[HS_DS_MEAN_AE] += fabs(dm);
-            acc[HS_DS_PRED] += (double)p;
-            if (p > (P)0 && t > (T)0) {
-                const double dl = (double)log_c(t) - (double)log_c(p);
-                acc[HS_DS_SIL_N] += 1.0;
-                acc[HS_DS_SIL_D] += dl;
-                acc[HS_DS_SIL_D2] += dl * dl;
-            }
-#pragma unroll
-            for (int r = 0; r < kMaxRanges; ++r) {
-                if (r < a.n_ranges && (T)a.lo[r] <= t && t < (T)a.hi[r]) {
-                    acc[HS_DS_RANGE + 2 * r] += 1.0;
-                    acc[HS_DS_RANGE + 2 * r + 1] += d * d;
-                }
-            }
-        }
-        // DepthiRMSE: transformed first, then selected: a target of +inf becomes 0 and counts, a prediction of 0 is dropped
-        const P ip = inv_km(p);
-        const T it = inv_km(t);
-        if (isfinite(ip) && isfinite(it)) {
-            const double d = (double)ip - (double)it;
-            acc[HS_DS_INV_N] += 1.0;
-            acc[HS_DS_INV_SE] += d * d;
-        }
-        // MeanSTD: +inf targets become NaN, NaN targets are dropped, the prediction is not looked at
-        if (a.use_logvar && !isnan(t) && t != (T)INFINITY) {
-            acc[HS_DS_STD_N] += 1.0;
-            acc[HS_DS_STD] += (double)std_of(load_val<P>(a.pred, a.kind, po + a.sc));
-        }
+        depth_metrics::accumulate(acc, a.rule, p, t, [&] { return load_val<P>(a.pred, a.kind, po + a.sc); });
     }
-    for (int k = 0; k < kNSums; ++k) {
-        const double v = block_sum(acc[k], lds);
-        if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * kNSums + k] = v;
-    }
-}
-
-// one workgroup: state[k] += sum over blocks of partial[blk][k], in a fixed order
-__global__ void __launch_bounds__(kThreads) depth_metrics_reduce_kernel(const double* __restrict__ partial, int blocks, double* __restrict__ state) {
-    __shared__ double lds[kThreads];
-    for (int k = 0; k < kNSums; ++k) {
-        double v = 0.0;
-        for (int j = threadIdx.x; j < blocks; j += kThreads) v += partial[(int64_t)j * kNSums + k];
-        v = block_sum(v, lds);
-        if (threadIdx.x == 0) state[k] += v;
-    }
+    depth_metrics::store_partials(acc, lds, partial);
 }
 
 // ------------------------------------------------------------------ back-projection of depth values
@@ -529,10 +450,7 @@ int hs_chamfer_nn(const float* a, const int64_t* a_off, int64_t a_rows, int64_t 
     return HS_OK;
 }
 
-int64_t hs_depth_metrics_partials(int64_t total) {
-    const int64_t blocks = (total + kThreads * 8 - 1) / (kThreads * 8);
-    return std::max<int64_t>(1, std::min<int64_t>(blocks, kMetricBlocksMax));
-}
+int64_t hs_depth_metrics_partials(int64_t total) { return depth_metrics::blocks_for(total); }
 
 int hs_depth_metrics(const void* pred, int pred_kind, int64_t batch, int64_t n, int64_t width, int64_t stride_b, int64_t stride_c,
                      int64_t stride_h, int64_t stride_w, const void* target, int target_kind, int64_t t_stride_b, int64_t t_stride_h,
@@ -541,14 +459,11 @@ int hs_depth_metrics(const void* pred, int pred_kind, int64_t batch, int64_t n, 
     HS_CHECK_ARG(pred_kind == HS_F32 || pred_kind == HS_BF16 || pred_kind == HS_F64, "prediction kind %d", pred_kind);
     HS_CHECK_ARG(target_kind == HS_F32 || target_kind == HS_BF16 || target_kind == HS_F64, "target kind %d", target_kind);
     HS_CHECK_ARG(batch > 0 && n > 0 && width > 0 && n % width == 0, "bad shape");
-    HS_CHECK_ARG(n_ranges >= 0 && n_ranges <= kMaxRanges && (n_ranges == 0 || ranges), "at most %d distance ranges", kMaxRanges);
+    depth_metrics::Rule rule;
+    if (int st = depth_metrics::fill_rule(rule, use_logvar, total_mean, ranges, n_ranges)) return st;
     HS_CHECK_ARG(pred && target && partial && state, "null pointer");
-    MetricIn a{pred, pred_kind, stride_b, stride_c, stride_h, stride_w, target, target_kind, t_stride_b, t_stride_h, t_stride_w,
-               width, n, batch, use_logvar, n_ranges, total_mean, {}, {}};
-    for (int r = 0; r < n_ranges; ++r) {
-        a.lo[r] = ranges[2 * r];
-        a.hi[r] = ranges[2 * r + 1];
-    }
+    const MetricIn a{pred, pred_kind, stride_b, stride_c, stride_h, stride_w, target, target_kind, t_stride_b, t_stride_h, t_stride_w,
+                     width, n, batch, rule};
     const int blocks = (int)hs_depth_metrics_partials(n * batch);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(kThreads);
@@ -561,7 +476,7 @@ int hs_depth_metrics(const void* pred, int pred_kind, int64_t batch, int64_t n, 
     else
         hipLaunchKernelGGL((depth_metrics_kernel<float, float>), grid, block, 0, s, a, partial);
     HS_LAUNCH_CHECK("depth_metrics");
-    hipLaunchKernelGGL(depth_metrics_reduce_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, state);
+    hipLaunchKernelGGL(depth_metrics::reduce_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, state);
     HS_LAUNCH_CHECK("depth_metrics_reduce");
     return HS_OK;
 }

@@ -283,7 +283,8 @@ class DepthMetrics:
 
     update(pred, target): pred [B, C, Npix] / [B, C, H, W] (channel 0 the mean, channel 1 the log variance) or, without a
     channel dimension, [B, Npix] / [B, H, W] (the back-projected float64 means); fp32, bf16 or float64, any strides.
-    target [B, Npix] / [B, H, W].  compute() returns a dict keyed by the reference's metric names:
+    target [B, Npix] / [B, H, W].  update(pred, target, projector): a flat prediction scored on the sphere (see
+    _update_projected).  compute() returns a dict keyed by the reference's metric names:
       mse, RelSE, RelAE (with total_mean), iRMSE, SILogE, mean_pred_dist, mse_range_* (distance_ranges, at most 8) and,
       with use_logvar, mean_std and median_std.
     total_mean and the range bounds are taken in fp32, as the reference's scalar-with-fp32-tensor arithmetic does."""
@@ -316,7 +317,34 @@ class DepthMetrics:
             return t.shape[-1], 0, t.stride(-1)
         return t.shape[-1], t.stride(-2), t.stride(-1)
 
-    def update(self, pred, target):
+    def _update_projected(self, pred, target, projector):
+        """update() of a FLAT prediction sampled onto the sphere through a flat_evaluation.FlatToHPProjector
+        (`hs_depth_metrics_gather`): target [B, Npix] fp32 / bf16, pred in the projector's layout, read in place; the
+        projected map is not written.  The state is the one update(projector.depth(pred), target) gives, bit for bit."""
+        if not torch.is_tensor(target) or target.device != self.device:
+            raise TypeError(f"target must be a tensor on {self.device}")
+        pred, sb, sc, sp = projector._depth_args(pred, 2 if self.use_logvar else 1)
+        if target.dim() != 2 or tuple(target.shape) != (pred.shape[0], projector.n_out):
+            raise ValueError(f"target must be [{pred.shape[0]}, {projector.n_out}], got {tuple(target.shape)}")
+        if min(target.stride()) < 0:
+            raise ValueError("negative strides are not supported")
+        b, n = target.shape
+        partial = torch.empty(int(lib.hs_depth_metrics_partials(b * n)) * NSUMS, dtype=torch.float64, device=self.device)
+        rng = self._ranges
+        near, idx, wgt = projector._tables()
+        check(lib.hs_depth_metrics_gather(ptr(pred), _dtype_kind(pred), b, projector.npix, sb, sc, sp, near, idx, wgt, n, ptr(target),
+                                          _dtype_kind(target), target.stride(0), target.stride(1), int(self.use_logvar),
+                                          0.0 if self.total_mean is None else self.total_mean, np_ptr(rng) if rng.size else None,
+                                          len(self.distance_ranges), ptr(partial), ptr(self.state), stream_ptr(self.device)),
+              "hs_depth_metrics_gather")
+        if self.use_logvar:  # MeanSTDMedian needs the projected log variance itself
+            stds = torch.sqrt(torch.exp(projector.depth(pred, channel=1)))
+            self.median[0] += stds.median(1).values.double().sum()
+            self.median[1] += b
+
+    def update(self, pred, target, projector=None):
+        if projector is not None:
+            return self._update_projected(pred, target, projector)
         for t, name in ((pred, "pred"), (target, "target")):
             if not torch.is_tensor(t) or t.device != self.device:
                 raise TypeError(f"{name} must be a tensor on {self.device}")

@@ -262,6 +262,9 @@ class SegConfusion:
                                                        nearest table, target uint8 [B, H', W']; uncovered pixels count as
                                                        projector.s2_bkgd_class (the *_back_projected metrics)
     update(pred, target, projector, masked=True)       uncovered pixels skipped (back_projected_hp_masked_iou)
+    update(proj.logits(pred), target, proj)            a FLAT prediction on the sphere or on its covered image pixels: proj a
+                                                       flat_evaluation.FlatToHPProjector (target uint8 [B, Npix]) or
+                                                       FlatCoverage (target [B, H, W], masked=True)
     update(pred, target, [p0, p1, ...], camera=cams)   a batch that mixes calibrations: cams[b] indexes the projector of
                                                        sample b; one launch per run of consecutive samples of one camera
                                                        (one per camera when the batch is grouped by camera)
@@ -303,7 +306,7 @@ class SegConfusion:
             self._launch(pred, target.contiguous(), None, 0, 0, target.shape[-1])
         else:
             projs = list(projector) if isinstance(projector, (list, tuple)) else [projector]
-            if target.dim() == 2:
+            if target.dim() == len(projs[0].shape):  # one sample of the projector's plane ([H', W'], or [Npix] on the sphere)
                 target = target[None]
             b = target.shape[0]
             if camera is None:

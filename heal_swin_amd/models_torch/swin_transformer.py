@@ -429,6 +429,13 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
         return ops.flat_pixel_image(rows.float(), H, W, self.config.patch_size[0], self.tile)
 
+    def forward_rows(self, x):
+        """The head rows forward() lays out as NCHW, as the decoder tail leaves them: [B, H * W, f_out] fp32 (the padded rows
+        viewed in place), row = token * p^2 + kh * p + kw with the tokens in tiled Z order.  For consumers that read pixels
+        through a table anyway (flat_evaluation.FlatToHPProjector.for_model / FlatCoverage.for_model: scoring on the sphere),
+        so that the NCHW tensor is never written; ops.flat_pixel_image(rows, H, W, p, self.tile) is forward(x)."""
+        return self._run(x)
+
     def forward_seg_loss(self, x, labels, class_weights=None):
         """nn.CrossEntropyLoss(weight=class_weights)(self(x), labels.long()) as ONE call (models_lightning/segmentation/
         model_lightning_swin.py): the labels are laid out in the logits rows' pixel order by a HIP kernel (ids outside [0, 254]

@@ -674,6 +674,29 @@ int hs_backproject_depth(const void* pred, int kind, int64_t batch, int64_t npix
                          const double* wgt, int64_t n_out, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The flat baseline on the sphere (heal_swin_amd/flat_evaluation.py, csrc/flat_eval.hip): depth predictions of the image plane
+ * sampled at n HEALPix pixels through the tables of FlatToHPProjector (negative Pad, Resize and
+ * project_depth_on_s2.sample_mask(..., s2_bkgd_class=nan) composed on the host; evaluation/flat_depth_pred_writers.py:216-239).
+ * The prediction is read in place: kind HS_F32 / HS_BF16, element (b, channel c, source pixel q) at b*stride_b + c*stride_c +
+ * q*stride_p, q < n_src (an NCHW map: stride_p = 1; the model's head rows: stride_c = 1).  Give EITHER nearest [dev] i32[n], the
+ * source pixel of every HEALPix pixel, OR idx [dev] i32[4][n] (taps y0x0, y0x1, y1x0, y1x1) with wgt [dev] f32[4][n] (h0, h1, w0,
+ * w1); the other pointers NULL.  A HEALPix pixel whose table entry (any tap) lies outside [0, n_src) is uncovered and reads NaN.
+ *   hs_flat_depth_to_hp      out [dev] f32[batch][n]: nearest values copied bit for bit; bilinear values
+ *                            h0*(w0*p00 + w1*p01) + h1*(w0*p10 + w1*p11) in fp32 without contraction (torch's order).
+ *   hs_depth_metrics_gather  hs_depth_metrics with that value as the prediction (the log variance, channel 1, gathered the same
+ *                            way when use_logvar) against target (b, i) at b*t_stride_b + i*t_stride_p (HS_F32 / HS_BF16), ADDING
+ *                            into state; partial [dev] f64[hs_depth_metrics_partials(batch * n)][HS_DEPTH_NSUMS] scratch.  Same
+ *                            per-element rules, lane map and merge order as hs_depth_metrics: the state is bit-identical to
+ *                            hs_depth_metrics on hs_flat_depth_to_hp's output, which is never written here.
+ * ---------------------------------------------------------------------------------------------- */
+int hs_flat_depth_to_hp(const void* pred, int kind, int64_t batch, int64_t n_src, int64_t stride_b, int64_t stride_p, const int32_t* nearest,
+                        const int32_t* idx, const float* wgt, int64_t n, float* out, void* stream);
+int hs_depth_metrics_gather(const void* pred, int pred_kind, int64_t batch, int64_t n_src, int64_t stride_b, int64_t stride_c, int64_t stride_p,
+                            const int32_t* nearest, const int32_t* idx, const float* wgt, int64_t n, const void* target, int target_kind,
+                            int64_t t_stride_b, int64_t t_stride_p, int use_logvar, double total_mean, const float* ranges, int n_ranges,
+                            double* partial, double* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The depth data path (heal_swin_amd/depth_data.py): the per-frame sampling of data/depth_estimation/project_depth_on_s2.py
  * (project_depth_dataset_hp :389-440, against hs_sample_*_u8's coordinate tables), the target transforms of the depth datasets
  * and Lightning module, and compute_depth_stats.py's statistics.
