@@ -21,7 +21,7 @@ HS_EPI_BIAS, HS_EPI_GELU, HS_EPI_DGELU, HS_EPI_RESID = 0, 1, 2, 3
 HS_ACC_DEFER = 2
 HS_MLP_NORM_AFTER = 16
 HS_U8, HS_I32, HS_I64 = 8, 9, 10
-HS_FLAT_PATCH_ROWS, HS_FLAT_PIXEL_ROWS = 0, 1
+HS_FLAT_PATCH_ROWS, HS_FLAT_PIXEL_ROWS, HS_FLAT_IMAGE = 0, 1, 2
 HS_DEPTH_L1, HS_DEPTH_L2, HS_DEPTH_HUBER, HS_DEPTH_LOGVAR = 0, 1, 2, 3
 HS_DT_NONE, HS_DT_LOG, HS_DT_INV = 0, 1, 2
 HS_DT_ZERO_BKG, HS_DT_1000_BKG, HS_DT_AFFINE, HS_DT_INVERSE = 1, 2, 4, 8
@@ -64,6 +64,8 @@ _SIGNATURES = {
     "hs_flat_attn_mask": [c_int, c_int, c_int, c_int, c_ptr],
     "hs_flat_img_to_rows": [c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_ptr],
     "hs_flat_rows_to_img": [c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_ptr],
+    "hs_flat_resize": [c_ptr, c_int, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int,
+                       c_int, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_ptr],
     "hs_rel_bias_gather": [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
     "hs_rel_bias_scatter_grad_sorted_add": [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr],
     "hs_cos_head_scale_fwd": [c_ptr, c_ptr, c_int, c_ptr],
@@ -186,6 +188,7 @@ _OTHER = {
     "hs_depth_points_workspace": ([c_i64, c_i64], c_i64),
     "hs_depth_metrics_partials": ([c_i64], c_i64),
     "hs_depth_stats_partials": ([c_i64], c_i64),
+    "hs_flat_resize_lds_bytes": ([c_int, c_int, c_int, c_int, c_int, c_int], c_i64),
     "hs_ln_head_partials": ([c_i64], c_i64),
     "hs_expand_ln_head_blocks": ([c_i64], c_i64),
     "hs_linear_wgrad_workspace": ([c_i64, c_int, c_int], c_i64),

@@ -21,6 +21,8 @@
 
 #pragma clang fp contract(off)
 
+#include "hs_depth_target.h"
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -67,32 +69,9 @@ __global__ void __launch_bounds__(kThreads) sample_nearest_f32_kernel(const floa
 }
 
 // ------------------------------------------------------------------ target transforms
-struct TargetOp {
-    int flags, transform;
-    float shift, scale;
-};
-
-// inverse_mask (depth_utils.py:60-72): +inf -> 0; x < 1e-3 (0, negatives, -inf) -> +inf; NaN stays; the rest 1 / x
-__device__ __forceinline__ float inverse_mask(float x) {
-    if (x == INFINITY) return 0.f;
-    if (x < 1e-3f) return INFINITY;
-    return (float)(1.0 / (double)x);
-}
-
-__device__ __forceinline__ float target_op(float x, const TargetOp& o) {
-    if (!(o.flags & HS_DT_INVERSE)) {
-        if ((o.flags & HS_DT_ZERO_BKG) && x == 0.f) x = INFINITY;
-        if ((o.flags & HS_DT_1000_BKG) && x == 1000.f) x = INFINITY;
-        if (o.transform == HS_DT_LOG) x = (float)log((double)x);
-        else if (o.transform == HS_DT_INV) x = inverse_mask(x);
-        if (o.flags & HS_DT_AFFINE) x = (x - o.shift) / o.scale;
-    } else {
-        if (o.flags & HS_DT_AFFINE) x = x * o.scale + o.shift;
-        if (o.transform == HS_DT_LOG) x = (float)exp((double)x);
-        else if (o.transform == HS_DT_INV) x = inverse_mask(x);
-    }
-    return x;
-}
+// the per-element rule: hs_depth_target.h (shared with the flat data path's resize kernel)
+using hs::target_op;
+using hs::TargetOp;
 
 // grid (column blocks, rows): element i of row b at in[b * isb + i * isp]; out may be in itself (same element, same thread)
 __global__ void __launch_bounds__(kThreads) depth_target_kernel(const float* in, int64_t isb, int64_t isp, float* out,

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "hs_device.h"
+#include "hs_flat_rows.h"
 
 namespace {
 
@@ -27,14 +28,7 @@ struct Geo {
     int64_t ld, rows_per_img, nrows;  // row pitch (elements), rows of one image, rows of one workgroup's square
 };
 
-__device__ __forceinline__ uint32_t compact(uint32_t v) {
-    v &= 0x55555555u;
-    v = (v | (v >> 1)) & 0x33333333u;
-    v = (v | (v >> 2)) & 0x0F0F0F0Fu;
-    v = (v | (v >> 4)) & 0x00FF00FFu;
-    v = (v | (v >> 8)) & 0x0000FFFFu;
-    return v;
-}
+using hs::flat_rows::compact;
 
 template <typename T, bool LAB>
 __device__ __forceinline__ float cvt_in(T v) {
@@ -78,23 +72,9 @@ __device__ __forceinline__ Square square_of(const Geo& g) {
 
 // element e of the square's rows -> LDS index of its pixel, or -1 for a padding column
 __device__ __forceinline__ int lds_of(const Geo& g, int e) {
-    const int ld = (int)g.ld, pp = g.p * g.p, Sp = g.S * g.p;
-    const int r = e / ld, col = e - r * ld;
-    int t, kk, c;
-    if (g.mode == HS_FLAT_PATCH_ROWS) {
-        if (col >= g.nch * pp) return -1;
-        t = r;
-        c = col / pp;
-        kk = col - c * pp;
-    } else {
-        if (col >= g.nch) return -1;
-        t = r / pp;
-        kk = r - t * pp;
-        c = col;
-    }
-    const int kh = kk / g.p, kw = kk - kh * g.p;
-    const int y = (int)compact((uint32_t)t) * g.p + kh, x = (int)compact((uint32_t)t >> 1) * g.p + kw;
-    return (c * Sp + y) * Sp + x;
+    const int Sp = g.S * g.p;
+    const hs::flat_rows::Pixel q = hs::flat_rows::pixel_of(g.mode, g.nch, g.p, (int)g.ld, e);
+    return q.c < 0 ? -1 : (q.c * Sp + q.y) * Sp + q.x;
 }
 
 template <typename Ti, typename To, bool LAB>

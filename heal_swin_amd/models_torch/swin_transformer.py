@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from .. import _lib, ops
 from ..data_spec import DataSpec
+from ..flat_data import PatchRows, PixelRows
 from . import hp_shifting
 from . import swin_hp_transformer as hp
 from .swin_hp_transformer import DropPath, HSLayerNorm, HSLinear, Mlp, _make_norm  # noqa: F401  (reference names)
@@ -254,13 +255,16 @@ class PatchEmbed(nn.Module):
         self.tile = tile
 
     def forward(self, x, dtype=None):
-        B, C, H, W = x.shape
-        assert H == self.data_spec.dim_in[0] and W == self.data_spec.dim_in[1], \
-            f"Input image size {H}*{W} doesn't match model ({self.data_spec.dim_in[0]}*{self.data_spec.dim_in[1]})."
-        if dtype is None:
-            dtype = x.dtype if x.dtype in (torch.float32, torch.bfloat16) else torch.float32
         p = self.proj.kernel_size[0]
-        rows = ops.flat_patch_rows(x, p, self.tile, dtype)  # B, N0, K (K = C p^2 padded to a multiple of 8)
+        if isinstance(x, PatchRows):  # the rows themselves (flat_data.FlatFrameTransform.frames(layout="rows")), checked by the model
+            rows, C = x.rows, x.channels
+        else:
+            B, C, H, W = x.shape
+            assert H == self.data_spec.dim_in[0] and W == self.data_spec.dim_in[1], \
+                f"Input image size {H}*{W} doesn't match model ({self.data_spec.dim_in[0]}*{self.data_spec.dim_in[1]})."
+            if dtype is None:
+                dtype = x.dtype if x.dtype in (torch.float32, torch.bfloat16) else torch.float32
+            rows = ops.flat_patch_rows(x, p, self.tile, dtype)  # B, N0, K (K = C p^2 padded to a multiple of 8)
         w = self.proj.weight.reshape(self.proj.weight.shape[0], C * p * p)
         pad = rows.shape[-1] - C * p * p
         if pad:
@@ -411,6 +415,10 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         if not x.is_cuda:
             raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
         dt = self._activation_dtype(x)
+        if isinstance(x, PatchRows):
+            x.check_model(self)
+            if x.dtype != dt:
+                raise TypeError(f"the patch rows are {x.dtype}, the model computes in {dt}: make them with frames(x, dtype={dt})")
         prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
         ops.RT.last_cast_cache = ops.RT.cast_cache
         try:
@@ -440,14 +448,18 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         """nn.CrossEntropyLoss(weight=class_weights)(self(x), labels.long()) as ONE call (models_lightning/segmentation/
         model_lightning_swin.py): the labels are laid out in the logits rows' pixel order by a HIP kernel (ids outside [0, 254]
         become 255, ignored), so that the loss rides on the decoder tail's kernels and, in bf16 training, the NCHW logits are never
-        written (the weighted mean does not depend on the pixel order).  labels: [B, H, W] integer class ids."""
+        written (the weighted mean does not depend on the pixel order).  labels: [B, H, W] integer class ids, or the flat_data.PixelRows
+        FlatFrameTransform.masks(layout="rows") made (x then usually being the PatchRows of .frames(layout="rows"))."""
         if not x.is_cuda:
             raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
         if self.data_spec.f_out > 255:
             raise NotImplementedError("forward_seg_loss supports at most 255 classes")
-        if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
-            labels = labels.long()
-        lab = ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
+        if isinstance(labels, PixelRows):
+            lab = self._pixel_rows(labels, x, torch.uint8, "labels")
+        else:
+            if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
+                labels = labels.long()
+            lab = ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
         w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
         return self._run(x, ce=(lab, w))
 
@@ -456,13 +468,26 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         loss_depth_regression.py): the target is laid out in the head rows' pixel order by a HIP kernel (fp32 copied bit for bit:
         infinite and NaN depths survive), so that the loss rides on the decoder tail's kernels and, in bf16 training, the NCHW
         prediction and the head rows are never written (the masked mean does not depend on the pixel order).  target: [B, H, W]
-        depths; the other arguments as SwinHPTransformerSys.forward_depth_loss."""
+        depths, or the flat_data.PixelRows FlatFrameTransform.depth(layout="rows") made; the other arguments as
+        SwinHPTransformerSys.forward_depth_loss."""
         from ..losses import check_depth_channels, depth_loss_spec
         kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
         check_depth_channels(kind, self.data_spec.f_out)
         if not x.is_cuda:
             raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
-        assert tuple(target.shape) == (x.shape[0], H, W), "target [B, H, W]"
-        tgt = ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
+        if isinstance(target, PixelRows):
+            tgt = self._pixel_rows(target, x, torch.float32, "target")
+        else:
+            H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
+            batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
+            assert tuple(target.shape) == (batch, H, W), "target [B, H, W]"
+            tgt = ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
         return self._run(x, depth=(tgt, kind, delta))
+
+    def _pixel_rows(self, rows, x, dtype, what):
+        """The tensor of a PixelRows built for this model, on x's device, one row set per sample of x."""
+        t = rows.check_model(self)
+        batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
+        if t.dtype != dtype or t.device != x.device or t.shape[0] != batch:
+            raise ValueError(f"{what} rows must be {dtype} [{batch}, H * W] on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t

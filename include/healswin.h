@@ -909,6 +909,33 @@ int hs_flat_img_to_rows(const void* img, int in_dtype, void* rows, int out_dtype
 int hs_flat_rows_to_img(const void* rows, int in_dtype, void* img, int out_dtype, int batch, int nch, int H, int W, int p, int T,
                         int mode, int64_t ld, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The flat data path (heal_swin_amd/flat_data.py, csrc/flat_data.hip): the reference's CenterCrop -> Resize -> Pad of a raw frame,
+ * class mask or depth map (data/segmentation/flat_datasets.py:84-125, data/depth_estimation/flat_depth_datasets.py:69-147) and the
+ * flat depth dataset's target chain, one pass per tensor, written EITHER as the NCHW result OR as the model's token rows.
+ *   src       [dev] HS_U8 / HS_F32 [batch][nch][H0][W0], image b at b * src_stride_b (elements), the images themselves contiguous.
+ *   row_idx   [dev] i32[2][H], col_idx [dev] i32[2][W]: per output row / column the two source taps (crop offset included), -1 in
+ *             [0][.] for padding (value 0).  row_wgt [dev] f32[2][H], col_wgt [dev] f32[2][W]: the taps' weights (h0, h1), (w0, w1);
+ *             value = h0*(w0*p00 + w1*p01) + h1*(w0*p10 + w1*p11) in fp32 without contraction, then for a HS_U8 source rounded half to
+ *             even and cast.  Both weight tables NULL: nearest, tap [0][.] copied bit for bit.
+ *   out       [dev] layout HS_FLAT_IMAGE: [batch][nch][H][W]; HS_FLAT_PATCH_ROWS / HS_FLAT_PIXEL_ROWS: the rows hs_flat_img_to_rows
+ *             makes of that image (p, T, ld as there; ignored for HS_FLAT_IMAGE).  out_dtype HS_U8 / HS_F32 / HS_BF16 for a HS_U8
+ *             source (the rounded uint8 value converted), HS_F32 for a HS_F32 source.
+ *   flags, transform, shift, scale   HS_F32 sources: hs_depth_target's forward chain (HS_DT_1000_BKG, HS_DT_LOG / HS_DT_INV,
+ *             HS_DT_AFFINE) applied to the resized, padded value; HS_DT_ZERO_BKG is not taken (the flat datasets keep zeros, so padding
+ *             goes through the transform as 0).
+ *   tile_h, tile_w   pixels of the output tile one workgroup owns (row layouts: S p square, S a power of two <= T); span_h, span_w:
+ *             the most source rows / columns (last tap - first tap + 1) any such tile reads, from the caller's tables.  The tile's
+ *             window is staged in hs_flat_resize_lds_bytes(...) bytes of LDS, at most 65536: HS_ERR_UNSUPPORTED otherwise (take a
+ *             smaller tile).  Taps are clamped into the window and the source: wrong spans give wrong values, not wild accesses.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_FLAT_IMAGE 2 /* beside HS_FLAT_PATCH_ROWS / HS_FLAT_PIXEL_ROWS: the NCHW image itself */
+int64_t hs_flat_resize_lds_bytes(int nch, int src_dtype, int tile_h, int tile_w, int span_h, int span_w);
+int hs_flat_resize(const void* src, int src_dtype, int64_t src_stride_b, int batch, int nch, int H0, int W0, const int32_t* row_idx,
+                   const float* row_wgt, const int32_t* col_idx, const float* col_wgt, void* out, int out_dtype, int H, int W, int layout,
+                   int p, int T, int64_t ld, int tile_h, int tile_w, int span_h, int span_w, int flags, int transform, float shift,
+                   float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
