@@ -60,8 +60,35 @@ struct TailDepth {
     int kind;             // HS_DEPTH_*
     float delta;          // huber delta
 };
+// ... or the segmentation caller's whole `shared_step` (model_lightning_swin_hp.py:104-111: argmax, weighted cross-entropy, IoU /
+// Accuracy on (preds, masks)): TailCe's loss with the same arithmetic in the same order, plus the row's class id
+// (torch.max(logits, 1): the first maximal class, a NaN counts as the maximum -- argmax_step of evaluation.hip) and the confusion
+// matrix behind the metrics (hs_seg_confusion's counting: labels >= n_classes stay out of the matrix and are counted in bad[0]).
+// A separate instantiation: TailCe and TailDepth compile to the code they were.
+struct TailCeStep {
+    const uint8_t* labels;     // as TailCe (never null here)
+    const float* class_w;
+    float* loss_part;
+    int n_classes;
+    uint8_t* preds;            // [rows] class ids, or null; 4-byte aligned (the 4 children of a token leave as one dword)
+    unsigned long long* conf;  // [n_classes][n_classes] (target, prediction) counts, added to; or null
+    unsigned long long* bad;   // [2]; [0] += rows whose label is >= n_classes (with conf)
+};
+constexpr int kHistBins = kKP * kKP;  // per-wave LDS histogram of TailCeStep: 16 x 16 uint32 bins = 1 KB
+
 __device__ __forceinline__ bool has_loss(const TailCe& ce) { return ce.labels != nullptr; }
 __device__ __forceinline__ bool has_loss(const TailDepth&) { return true; }
+__device__ __forceinline__ bool has_loss(const TailCeStep&) { return true; }
+
+// torch.max(logits, 1)'s index over a row split between two lanes: (best, arg) is each lane's own result over its classes in
+// ascending order (argmax_step), `ob`, `oa` the partner's.  The first NaN wins, else the larger value, and on equal values the
+// lower class id: the lanes of a pair hold interleaved ids, so the merge has to compare the indices too.
+__device__ __forceinline__ int argmax_merge(float best, int arg, float ob, int oa) {
+    const bool n0 = best != best, n1 = ob != ob;
+    const int lower = arg < oa ? arg : oa;
+    if (n0 || n1) return n0 && n1 ? lower : (n0 ? arg : oa);
+    return best > ob ? arg : (ob > best ? oa : lower);
+}
 
 template <int NB, typename Loss>
 __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16_t* __restrict__ xn, const uint16_t* __restrict__ xn_lo,
@@ -70,7 +97,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                                                                     uint16_t* __restrict__ y, float* __restrict__ logits,
                                                                     float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                                     int64_t tokens, Loss ce) {
-    constexpr bool kCe = std::is_same<Loss, TailCe>::value;
+    constexpr bool kDepth = std::is_same<Loss, TailDepth>::value, kStep = std::is_same<Loss, TailCeStep>::value;
     constexpr int C = 32 * NB, KS = 2 * NB, NCH = C / 8;  // channels (= input width), 16-deep k-steps, 16-byte chunks per row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* wl = smem;                                  // [kP * C][kRowB], 16-byte chunk ^ (row & 15)
@@ -100,6 +127,12 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
     float bk[8];
 #pragma unroll
     for (int r = 0; r < 8; ++r) bk[r] = bvec[4 * half + (r & 3) + 8 * (r >> 2)];
+    // TailCeStep: one histogram per wave behind the patches (4 x 1 KB: 148 KB of LDS at C = 128), flushed once after the loop
+    uint32_t* hist = (uint32_t*)(smem + kP * C * kRowB + 4 * 32 * kPatchRow);
+    uint32_t bad_rows = 0;  // (wave-uniform: counted with ballots)
+    if constexpr (kStep) {
+        for (int j = tid; j < 4 * kHistBins; j += 256) hist[j] = 0;
+    }
     __syncthreads();
 
     const int sx = l31 & 15;
@@ -115,6 +148,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             const uint4 v = live ? *(const uint4*)(xn + tok * C + 16 * ks + 8 * half) : make_uint4(0, 0, 0, 0);
             xb[ks] = __builtin_bit_cast(bf16x8, v);
         }
+        uint32_t pred4 = 0;  // TailCeStep: the class ids of the token's 4 children, child p in byte p
 #pragma unroll 1
         for (int p = 0; p < kP; ++p) {
             // ------------------------------------------------------------ the child's C channels of 32 tokens: D = Wexp_p xn^T
@@ -217,7 +251,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                     lg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfa[ct][j], __builtin_bit_cast(bf16x8, pack8f(lo)), lg, 0, 0, 0);
                     lg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfl[ct][j], __builtin_bit_cast(bf16x8, hb), lg, 0, 0, 0);
                 }
-            if constexpr (!kCe) {  // depth term of the row: channels 0 and 1 are registers 0 and 1 of half 0
+            if constexpr (kDepth) {  // depth term of the row: channels 0 and 1 are registers 0 and 1 of half 0
                 const float t = live && half == 0 ? ce.target[orow] : INFINITY;
                 if (depth_keep(t)) {
                     ce_num += depth_term(ce.kind, ce.delta, lg[0] + bk[0], lg[1] + bk[1], t);
@@ -248,6 +282,34 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                     ce_num = fmaf(wy, m + __builtin_amdgcn_logf(ssum) * kLn2 - pick, ce_num);
                     ce_den += wy;
                 }
+                if constexpr (kStep) {
+                    float best = -INFINITY;  // (the lowest class wins over -inf by index; a lane without a class loses every tie)
+                    int arg = 4 * half < ce.n_classes ? 4 * half : 64;
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {  // r ascending = class id ascending
+                        const int cls = 4 * half + (r & 3) + 8 * (r >> 2);
+                        if (cls < ce.n_classes && !(best != best) && (v[r] > best || v[r] != v[r])) {
+                            best = v[r];
+                            arg = cls;
+                        }
+                    }
+                    const int pred = argmax_merge(best, arg, __shfl_xor(best, 32, 64), __shfl_xor(arg, 32, 64));
+                    pred4 |= (uint32_t)pred << (8 * p);
+                    if (ce.conf) {  // (wave-uniform) one row per lane pair: half 0 counts it
+                        const bool mine = live && half == 0;
+                        const int bin = mine && yl < ce.n_classes ? yl * ce.n_classes + pred : -1;
+                        bad_rows += (uint32_t)__popcll(__ballot(mine && yl >= ce.n_classes));
+                        // the lanes that share the first lane's bin (most of them in the uniform regions of a mask) add with one atomic
+                        uint32_t* h = hist + (tid >> 6) * kHistBins;
+                        const int lead = __builtin_amdgcn_readfirstlane(bin);
+                        const unsigned long long same = __ballot(bin == lead);
+                        if (bin == lead) {
+                            if (lead >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(&h[lead], (uint32_t)__popcll(same));
+                        } else if (bin >= 0) {
+                            atomicAdd(&h[bin], 1u);
+                        }
+                    }
+                }
             }
             if (live) {
                 // accumulator register r = class 4 half + (r & 3) + 8 (r >> 2) of this lane's row: classes 0..15 are r = 0..7
@@ -260,6 +322,20 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                     rstd_out[orow] = rstd;
                 }
             }
+        }
+        if constexpr (kStep) {
+            if (ce.preds && live && half == 0) *(uint32_t*)(ce.preds + tok * kP) = pred4;  // one 128-byte line per wave and step
+        }
+    }
+    if constexpr (kStep) {
+        if (ce.conf) {  // the workgroup's four histograms as one 64-bit atomic per non-zero bin; integer counts: order-independent
+            __syncthreads();
+            const int bins = ce.n_classes * ce.n_classes;
+            if (tid < bins) {
+                const uint32_t n = hist[tid] + hist[kHistBins + tid] + hist[2 * kHistBins + tid] + hist[3 * kHistBins + tid];
+                if (n) atomicAdd(&ce.conf[tid], (unsigned long long)n);
+            }
+            if (lane == 0 && bad_rows) atomicAdd(&ce.bad[0], (unsigned long long)bad_rows);
         }
     }
     if (has_loss(ce)) {  // every wave writes its pair (zeros if it owned no rows): the host sums the array
@@ -295,8 +371,15 @@ int launch_expand_ln_head(const void* xn, const void* xn_lo, const void* wexp, c
         return fail(HS_ERR_UNSUPPORTED, "%s: bf16, 4 children, C in {64, 96, 128} (got C = %d, children %d): the expand "
                     "weight must fit the LDS", who, width, children);
     const int nb = width / 32;
-    const size_t smem = (size_t)kP * width * kRowB + 4 * 32 * kPatchRow;
+    constexpr bool kStep = std::is_same<Loss, TailCeStep>::value;
+    const size_t smem = (size_t)kP * width * kRowB + 4 * 32 * kPatchRow + (kStep ? 4 * kHistBins * sizeof(uint32_t) : 0);
+    HS_CHECK_ARG(smem <= 160 * 1024, "%s: %zu bytes of LDS", who, smem);  // (148 KB with the histograms at C = 128)
     const dim3 grid((unsigned)hs_expand_ln_head_blocks(tokens)), block(256);
+    if constexpr (kStep) {  // a wave owns every (4 grid)-th group of 32 tokens = 128 rows: its 32-bit bins must hold them all
+        const int64_t groups = (tokens + 31) / 32, waves = (int64_t)grid.x * 4;
+        HS_CHECK_ARG((groups + waves - 1) / waves < (1ll << 25), "%s: %lld tokens on %lld waves overflow the 32-bit histogram bins", who,
+                     (long long)tokens, (long long)waves);
+    }
     hipStream_t s = (hipStream_t)stream;
 #define HS_ELH(NB)                                                                                                                  \
     case NB: {                                                                                                                      \
@@ -340,6 +423,20 @@ int hs_expand_ln_head_ce_fwd(const void* xn, const void* xn_lo, const void* wexp
     HS_CHECK_ARG(n_classes >= 1 && n_classes <= 16, "hs_expand_ln_head_ce_fwd: 1..16 classes");
     return launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream,
                                  hs::TailCe{labels, class_weights, loss_partials, n_classes}, "hs_expand_ln_head_ce_fwd");
+}
+
+int hs_expand_ln_head_ce_step_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec,
+                                  const uint8_t* labels, const float* class_weights, int n_classes, void* y, float* logits, float* mean,
+                                  float* rstd, float* loss_partials, uint8_t* preds, int64_t* confmat, int64_t* bad, int64_t tokens,
+                                  int width, int children, int dtype, void* stream) {
+    HS_CHECK_ARG(labels && loss_partials, "hs_expand_ln_head_ce_step_fwd: null pointer");
+    HS_CHECK_ARG(n_classes >= 1 && n_classes <= 16, "hs_expand_ln_head_ce_step_fwd: 1..16 classes");
+    HS_CHECK_ARG(!confmat || bad, "hs_expand_ln_head_ce_step_fwd: confmat needs bad (the counter of labels >= n_classes)");
+    HS_CHECK_ARG(((uintptr_t)preds & 3) == 0, "hs_expand_ln_head_ce_step_fwd: preds must be 4-byte aligned");
+    return launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream,
+                                 hs::TailCeStep{labels, class_weights, loss_partials, n_classes, preds, (unsigned long long*)confmat,
+                                                (unsigned long long*)bad},
+                                 "hs_expand_ln_head_ce_step_fwd");
 }
 
 int hs_expand_ln_head_depth_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const float* target,

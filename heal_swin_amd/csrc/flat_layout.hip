@@ -7,7 +7,8 @@
 //                         the Conv2d weight (PatchEmbed as one Linear); mode HS_FLAT_PIXEL_ROWS: row = token * p^2 + kh * p + kw
 //                         (the children of FinalPatchExpand_X4, the reference's up_x4 view), column = c.  Columns past the
 //                         valid ones are written as zeros.  uint8 rows are labels: ids outside [0, 254] become 255 (ignored).
-//   hs_flat_rows_to_img   the inverse map (logits rows -> NCHW logits, patch-row gradient -> image gradient).
+//   hs_flat_rows_to_img   the inverse map (logits rows -> NCHW logits, patch-row gradient -> image gradient, uint8 class ids of the
+//                         pixel rows -> a uint8 label image).
 //
 // One workgroup owns an S x S square of tokens that is aligned in Morton order, i.e. S^2 consecutive tokens: its rows are ONE
 // contiguous run of memory, its pixels an (S p) x (S p) square per channel.  The square is staged through LDS (fp32, exact for
@@ -281,6 +282,10 @@ extern "C" int hs_flat_rows_to_img(const void* rows, int in_dtype, void* img, in
     int64_t blocks;
     if (int st = make_geo(batch, nch, H, W, p, T, mode, ld, g, blocks)) return st;
     hipStream_t s = (hipStream_t)stream;
+    if (in_dtype == HS_U8 || out_dtype == HS_U8) {  // class ids (the predictions of forward_seg_step): bytes to bytes
+        if (in_dtype != out_dtype) return hs::fail(HS_ERR_UNSUPPORTED, "uint8 rows go to a uint8 image (got dtypes %d -> %d)", in_dtype, out_dtype);
+        return launch_r2i<uint8_t, uint8_t>(rows, img, g, blocks, 1, 1, s);
+    }
     switch (in_dtype) {
         case HS_F32: return dispatch_r2i_out<float>(rows, img, out_dtype, g, blocks, 4, s);
         case HS_BF16: return dispatch_r2i_out<uint16_t>(rows, img, out_dtype, g, blocks, 2, s);

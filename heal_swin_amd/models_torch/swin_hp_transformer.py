@@ -690,10 +690,11 @@ class UnetDecoder(nn.Module):
         self.output = nn.Conv1d(in_channels=config.embed_dim, out_channels=data_spec.f_out, kernel_size=1, bias=False)
         self.norm_up = _make_norm(config.norm_layer, config.embed_dim)
 
-    def forward(self, x, x_downsample, ce=None, depth=None):
+    def forward(self, x, x_downsample, ce=None, depth=None, step=None):
         """ce = (labels u8 [B, Npix], class weights or None): return the weighted cross-entropy of the logits instead of the logits
         (SwinHPTransformerSys.forward_seg_loss); depth = (target f32 [B, Npix], HS_DEPTH_* kind, huber delta): the depth loss
-        (forward_depth_loss).  Fused into the tail kernels where they apply."""
+        (forward_depth_loss); ce with step = (SegConfusion or None, want_preds): (loss, preds) and the counts (forward_seg_step).
+        Fused into the tail kernels where they apply."""
         dbg = self.config.dev_mode
         for inx, layer_up in enumerate(self.layers_up):
             if inx > 0:
@@ -703,17 +704,20 @@ class UnetDecoder(nn.Module):
             if dbg:
                 print(f"feature shape after decoder layer {inx}: {x.size()}")
         w = self.output.weight  # 1x1 conv without bias (ref :756-761) as the [f_out, C] matrix it is (ops.LinearFn)
-        out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, ce, depth)
+        out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, ce, depth, step)
         return out if ce is not None or depth is not None else out.float().transpose(1, 2)  # B, f_out, Npix (fp32)
 
 
-def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None):
+def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None, step=None):
     """norm_up -> up (Linear C -> children * C, one LayerNorm(C) per child) -> 1x1 head w [f_out, C, ...] on the decoder output
     x [B, N0, C].  Returns the logits rows [B, N0 * children, f_out] (the children of a token consecutive; fp32, or the fallback's
     compute dtype), or with ce = (labels u8 [B, N0 * children] in the same row order, class weights or None) the weighted
     cross-entropy instead (SwinHPTransformerSys.forward_seg_loss), with depth = (target f32 [B, N0 * children] in the same row
     order, HS_DEPTH_* kind, huber delta) the depth-regression loss (forward_depth_loss); fused into the tail kernels where they
-    apply, else the standalone loss kernels on the rows."""
+    apply, else the standalone loss kernels on the rows.  ce with step = (evaluation.SegConfusion or None, want_preds) is the
+    segmentation caller's whole shared_step (forward_seg_step): (loss, preds u8 [B, N0 * children] or None), and the confusion
+    matrix of (labels, preds) added to the SegConfusion -- one launch without logits where the one-launch tail applies, with or
+    without a gradient; else composed from the rows."""
     f_out = w.shape[0]
     if (isinstance(up.norm, HSLayerNorm) and isinstance(up.expand, HSLinear) and up.expand.bias is None and
             ops.expand_ln_head_ok(x, up.dim, children, f_out)):
@@ -725,6 +729,13 @@ def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None):
         else:
             xn = norm_up(x)
         B, N0, _ = xn.shape
+        if step is not None and ce[0].dtype == torch.uint8:
+            # the caller's shared_step in one forward kernel: loss, class ids and confusion matrix; the logits are never written
+            conf, want_preds = step
+            loss, preds = ops.expand_ln_head_ce_step(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
+                                                     ce[0].contiguous(), ce[1], xn_lo, None if conf is None else conf.confmat,
+                                                     None if conf is None else conf._bad, want_preds)
+            return loss, (None if preds is None else preds.view(B, N0 * children))
         if ce is not None and ce[0].dtype == torch.uint8 and torch.is_grad_enabled():
             # training: expand -> LayerNorm -> head -> weighted CE in one forward kernel; the logits are never written
             return ops.expand_ln_head_ce(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
@@ -734,14 +745,14 @@ def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None):
             return ops.expand_ln_head_depth(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
                                             depth[0], depth[1], depth[2], xn_lo)
         lg = ops.expand_ln_head(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w, xn_lo)
-        return _rows_or_loss(ops.pad_slice(lg.view(B, N0 * children, -1), f_out), ce, depth)
+        return _rows_or_loss(ops.pad_slice(lg.view(B, N0 * children, -1), f_out), ce, depth, step)
     if isinstance(up.norm, HSLayerNorm) and ops.ln_head_ok(x, up.dim, f_out):
         # the tail's LayerNorm and the class head in one pass over the expanded rows (hs_ln_head_*): the normalised
         # [B, Npix, C] tensor is neither written nor kept for the backward
         x = up.expand(norm_up(x))  # B, N0, p * C: row (b, n) holds the p children of token n back to back
         B, N0, _ = x.shape
         x = ops.ln_head(x.reshape(B * N0 * children, up.dim), up.norm.weight, up.norm.bias, w)
-        return _rows_or_loss(ops.pad_slice(x.view(B, N0 * children, -1), f_out), ce, depth)
+        return _rows_or_loss(ops.pad_slice(x.view(B, N0 * children, -1), f_out), ce, depth, step)
     x = up(norm_up(x))  # B, Npix, C
     if x.dtype == torch.bfloat16 and f_out % 8 and f_out > 8:
         # 12 classes: rows padded to 16 so that the input gradient (K = 12 -> 16) runs in hs_gemm_nt: 0.33 ms instead of the
@@ -749,17 +760,31 @@ def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None):
         x = ops.pad_slice(ops.linear(x, F.pad(w.reshape(f_out, -1), (0, 0, 0, (-f_out) % 8))), f_out)
     else:
         x = ops.linear(x, w)
-    return _rows_or_loss(x, ce, depth)  # logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
+    return _rows_or_loss(x, ce, depth, step)  # logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
 
 
-def _rows_or_loss(rows, ce, depth=None):
+def check_step_confusion(confusion, f_out):
+    """forward_seg_step's `confusion`: None or a SegConfusion of the model's class count."""
+    if confusion is not None and getattr(confusion, "num_classes", None) != f_out:
+        raise ValueError(f"confusion counts {getattr(confusion, 'num_classes', None)} classes, the model predicts {f_out}")
+
+
+def _rows_or_loss(rows, ce, depth=None, step=None):
     if depth is not None:
         from ..losses import _DepthLossFn
         return _DepthLossFn.apply(rows.float().transpose(1, 2), depth[0], depth[1], depth[2])
     if ce is None:
         return rows
-    from ..losses import seg_loss
-    return seg_loss(rows.float().transpose(1, 2), ce[0], ce[1])
+    from ..losses import seg_loss, seg_predictions
+    logits = rows.float().transpose(1, 2)
+    loss = seg_loss(logits, ce[0], ce[1])
+    if step is None:
+        return loss
+    # the shared_step composed from the written rows: hs_seg_confusion reads them in place (and takes the argmax itself)
+    conf, want_preds = step
+    if conf is not None:
+        conf.update(logits.detach(), ce[0], check=False)
+    return loss, (seg_predictions(logits.detach()).to(torch.uint8) if want_preds else None)
 
 
 @dataclass
@@ -935,6 +960,35 @@ class SwinHPTransformerSys(nn.Module):
                 self._prefetch_attn_params()
                 x, x_downsample = self.forward_features(x.to(dt))
                 return self.decoder(x, x_downsample, ce=(labels, w))
+        finally:
+            self._clear_attn_params()
+            ops.RT.cast_cache = prev
+
+    def forward_seg_step(self, x, labels, class_weights=None, confusion=None, return_preds=True):
+        """The segmentation caller's `shared_step` (models_lightning/segmentation/model_lightning_swin_hp.py:104-111) as ONE call:
+            outputs = self(x); _, preds = torch.max(outputs, 1); loss = CrossEntropyLoss(weight)(outputs, labels.long());
+            iou / acc / acc_ignored (preds, labels)
+        -> (loss, preds): the loss of forward_seg_loss (bit for bit, same gradients), preds uint8 [B, Npix] (None with
+        return_preds=False), and the (label, pred) counts added to `confusion` (an evaluation.SegConfusion; read its iou() /
+        accuracy() when the metric is logged, all_reduce() it under data parallelism).  In bf16 all of it rides on ONE decoder-tail
+        launch (`hs_expand_ln_head_ce_step_fwd`) that reads the labels and writes one byte per pixel, with a gradient (training)
+        and without (validation): the logits are never written.  Elsewhere (fp32, other widths, > 16 classes) the same results are
+        composed from the logits rows.  Labels >= f_out carry no weight and are not counted; the SegConfusion reports them at its
+        next metric read (no synchronisation here, as update(..., check=False))."""
+        check_step_confusion(confusion, self.data_spec.f_out)
+        if not x.is_cuda:
+            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+        if labels.dtype != torch.uint8 and self.data_spec.f_out <= 255:
+            labels = torch.where((labels < 0) | (labels > 254), 255, labels).to(torch.uint8)  # (as forward_seg_loss)
+        w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
+        dt = self._activation_dtype(x)
+        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
+        ops.RT.last_cast_cache = ops.RT.cast_cache
+        try:
+            with torch.autocast(device_type="cuda", enabled=False):
+                self._prefetch_attn_params()
+                x, x_downsample = self.forward_features(x.to(dt))
+                return self.decoder(x, x_downsample, ce=(labels, w), step=(confusion, bool(return_preds)))
         finally:
             self._clear_attn_params()
             ops.RT.cast_cache = prev

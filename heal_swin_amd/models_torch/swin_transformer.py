@@ -411,7 +411,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
             x = layer_up(x)
         return x
 
-    def _run(self, x, ce=None, depth=None):
+    def _run(self, x, ce=None, depth=None, step=None):
         if not x.is_cuda:
             raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
         dt = self._activation_dtype(x)
@@ -427,7 +427,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
                 x, x_downsample = self.forward_features(x, dt)
                 x = self.forward_up_features(x, x_downsample)
                 p = self.config.patch_size[0]
-                return hp.decoder_tail(self.norm_up, self.up, self.output.weight, p * p, x, ce, depth)
+                return hp.decoder_tail(self.norm_up, self.up, self.output.weight, p * p, x, ce, depth, step)
         finally:
             self._clear_attn_params()
             ops.RT.cast_cache = prev
@@ -462,6 +462,30 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
             lab = ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
         w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
         return self._run(x, ce=(lab, w))
+
+    def forward_seg_step(self, x, labels, class_weights=None, confusion=None, return_preds=True):
+        """The flat segmentation caller's `shared_step` (models_lightning/segmentation/model_lightning_swin.py: argmax, weighted
+        cross-entropy, IoU / Accuracy on (preds, masks)) as ONE call, as SwinHPTransformerSys.forward_seg_step: (loss, preds) with
+        forward_seg_loss's loss and gradients, preds uint8 [B, H, W] = self(x).argmax(1) (None with return_preds=False; the class
+        ids of the pixel rows laid out as an image by a HIP kernel), and the (label, pred) counts added to `confusion` (an
+        evaluation.SegConfusion; the counts do not depend on the pixel order).  labels as forward_seg_loss takes them."""
+        hp.check_step_confusion(confusion, self.data_spec.f_out)
+        if not x.is_cuda:
+            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+        if self.data_spec.f_out > 255:
+            raise NotImplementedError("forward_seg_step supports at most 255 classes")
+        if isinstance(labels, PixelRows):
+            lab = self._pixel_rows(labels, x, torch.uint8, "labels")
+        else:
+            if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
+                labels = labels.long()
+            lab = ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
+        w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
+        loss, preds = self._run(x, ce=(lab, w), step=(confusion, bool(return_preds)))
+        if preds is not None:
+            H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
+            preds = ops.flat_label_image(preds.contiguous(), H, W, self.config.patch_size[0], self.tile)
+        return loss, preds
 
     def forward_depth_loss(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
         """get_depth_loss(cfg)(self(x), target) as ONE call (the flat depth baseline's training step, training/

@@ -315,3 +315,13 @@ def flat_labels(labels, p, T):
     B, H, W = labels.shape
     out = torch.empty((B, H * W), dtype=torch.uint8, device=labels.device)
     return _img_to_rows(labels.view(B, 1, H, W), out, p, T, _lib.HS_FLAT_PIXEL_ROWS, 1)
+
+
+def flat_label_image(rows, H, W, p, T):
+    """uint8 class ids [B, H * W] in the pixel order of the logits rows -> the uint8 label image [B, H, W] (the inverse of
+    flat_labels; bytes moved bit for bit)."""
+    _require_gpu(rows)
+    B = rows.shape[0]
+    assert rows.dtype == torch.uint8 and rows.shape == (B, H * W) and rows.is_contiguous(), "class ids: contiguous uint8 [B, H * W]"
+    out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=rows.device)
+    return _rows_to_img(rows, out, p, T, _lib.HS_FLAT_PIXEL_ROWS, 1).view(B, H, W)

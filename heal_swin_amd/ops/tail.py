@@ -179,6 +179,47 @@ def _fold_head_ce(gamma, beta, weight, C, device):
     return wfold[perm64], bvec[perm]  # (advanced indexing: fresh contiguous tensors)
 
 
+def _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo, step=None):
+    """The forward of ExpandLnHeadCeFn, and with step = (preds u8 [rows] or None, confmat i64 [K, K] or None, bad i64 [2] or None)
+    that of ExpandLnHeadCeStepFn: the same launch arguments and saved tensors, `hs_expand_ln_head_ce_step_fwd` instead of
+    `hs_expand_ln_head_ce_fwd`."""
+    _require_gpu(xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo)
+    tokens, C = xn2.shape
+    xn2 = xn2.contiguous()
+    xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
+    P = wexp.shape[0] // C
+    f_out = weight.shape[0]
+    wq = _cast_param(wexp, torch.bfloat16).contiguous()
+    wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
+    need = any(ctx.needs_input_grad[:5])
+    rows = tokens * P
+    labels = labels.reshape(-1)
+    assert labels.dtype == torch.uint8 and labels.numel() == rows and labels.is_contiguous(), "labels: contiguous uint8, one per pixel row"
+    y = torch.empty((rows, C), dtype=torch.bfloat16, device=xn2.device) if need else None
+    mean = torch.empty(rows, dtype=torch.float32, device=xn2.device) if need else None
+    rstd = torch.empty_like(mean) if need else None
+    parts = torch.empty((4 * int(lib.hs_expand_ln_head_blocks(tokens)), 2), dtype=torch.float32, device=xn2.device)
+    # algorithmic traffic: xn in, labels in (+ the expanded rows once in training, + one byte per row of predictions); no logits
+    if step is None:
+        with _timed("expand_ln_head_ce_fwd", xn2.device, 2 * tokens * C + rows * (1 + (2 * C + 8 if need else 0)),
+                    2 * rows * C * C + 4 * rows * C * 32):
+            check(lib.hs_expand_ln_head_ce_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(labels), ptr(class_w), f_out,
+                                               ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), tokens, C, P, _lib.HS_BF16,
+                                               stream_ptr(xn2.device)), "hs_expand_ln_head_ce_fwd")
+    else:
+        preds, confmat, bad = step
+        with _timed("expand_ln_head_ce_step_fwd", xn2.device,
+                    2 * tokens * C + rows * (1 + (preds is not None) + (2 * C + 8 if need else 0)), 2 * rows * C * C + 4 * rows * C * 32):
+            check(lib.hs_expand_ln_head_ce_step_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(labels), ptr(class_w), f_out,
+                                                    ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), ptr(preds), ptr(confmat), ptr(bad),
+                                                    tokens, C, P, _lib.HS_BF16, stream_ptr(xn2.device)), "hs_expand_ln_head_ce_step_fwd")
+    tot = parts.sum(0)
+    ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp, labels, class_w, tot)
+    ctx.w_cast = wq if wq.dtype != wexp.dtype else None
+    ctx.cast_cache = RT.cast_cache
+    return tot[0] / tot[1]
+
+
 class ExpandLnHeadCeFn(torch.autograd.Function):
     """The decoder tail AND the segmentation caller's weighted cross-entropy (reference swin_hp_transformer.py:442-452, :785-788 and
     models_lightning/segmentation/model_lightning_swin_hp.py:39-45, :104-111) as one forward and one backward kernel
@@ -187,33 +228,7 @@ class ExpandLnHeadCeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo):
-        _require_gpu(xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo)
-        tokens, C = xn2.shape
-        xn2 = xn2.contiguous()
-        xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
-        P = wexp.shape[0] // C
-        f_out = weight.shape[0]
-        wq = _cast_param(wexp, torch.bfloat16).contiguous()
-        wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
-        need = any(ctx.needs_input_grad[:5])
-        rows = tokens * P
-        labels = labels.reshape(-1)
-        assert labels.dtype == torch.uint8 and labels.numel() == rows and labels.is_contiguous(), "labels: contiguous uint8, one per pixel row"
-        y = torch.empty((rows, C), dtype=torch.bfloat16, device=xn2.device) if need else None
-        mean = torch.empty(rows, dtype=torch.float32, device=xn2.device) if need else None
-        rstd = torch.empty_like(mean) if need else None
-        parts = torch.empty((4 * int(lib.hs_expand_ln_head_blocks(tokens)), 2), dtype=torch.float32, device=xn2.device)
-        # algorithmic traffic: xn in, labels in (+ the expanded rows once in training); no logits
-        with _timed("expand_ln_head_ce_fwd", xn2.device, 2 * tokens * C + rows * (1 + (2 * C + 8 if need else 0)),
-                    2 * rows * C * C + 4 * rows * C * 32):
-            check(lib.hs_expand_ln_head_ce_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(labels), ptr(class_w), f_out,
-                                               ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), tokens, C, P, _lib.HS_BF16,
-                                               stream_ptr(xn2.device)), "hs_expand_ln_head_ce_fwd")
-        tot = parts.sum(0)
-        ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp, labels, class_w, tot)
-        ctx.w_cast = wq if wq.dtype != wexp.dtype else None
-        ctx.cast_cache = RT.cast_cache
-        return tot[0] / tot[1]
+        return _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo)
 
     @staticmethod
     def backward(ctx, dloss):
@@ -227,6 +242,40 @@ class ExpandLnHeadCeFn(torch.autograd.Function):
         ctx.w_cast = ctx.cast_cache = None
         dwexp, _ = _param_grads(dy2, xn2, wexp, None, ctx.needs_input_grad[1], False)
         return dxn, dwexp, dgamma, dbeta, dw, None, None, None
+
+
+class ExpandLnHeadCeStepFn(torch.autograd.Function):
+    """The segmentation caller's whole `shared_step` on the decoder tail (models_lightning/segmentation/model_lightning_swin_hp.py:
+    104-111: `preds = torch.max(outputs, 1)`, the weighted cross-entropy, IoU / Accuracy on (preds, masks)) as ONE forward kernel
+    (`hs_expand_ln_head_ce_step_fwd`): ExpandLnHeadCeFn's loss bit for bit, plus the class id of every pixel row (uint8) and
+    their confusion matrix with the labels, added to `confmat` (int64 [K, K]; labels >= K are counted in bad[0] instead) in place;
+    still no logits.  The backward is ExpandLnHeadCeFn's.  Runs without a gradient too (nothing saved: validation)."""
+
+    @staticmethod
+    def forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo, confmat, bad, want_preds):
+        f_out = weight.shape[0]
+        if confmat is not None:
+            _require_gpu(confmat, bad)
+            assert bad is not None and bad.dtype == torch.int64 and bad.numel() == 2 and bad.is_contiguous(), "bad: int64 [2]"
+            assert confmat.dtype == torch.int64 and confmat.shape == (f_out, f_out) and confmat.is_contiguous(), \
+                f"confmat: contiguous int64 [{f_out}, {f_out}]"
+        preds = torch.empty(labels.numel(), dtype=torch.uint8, device=xn2.device) if want_preds else None
+        loss = _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo, step=(preds, confmat, bad))
+        if preds is None:
+            return loss, None
+        ctx.mark_non_differentiable(preds)
+        return loss, preds
+
+    @staticmethod
+    def backward(ctx, dloss, _dpreds):
+        return ExpandLnHeadCeFn.backward(ctx, dloss) + (None, None, None)
+
+
+def expand_ln_head_ce_step(xn2, wexp, gamma, beta, weight, labels, class_weights=None, xn_lo=None, confmat=None, bad=None, want_preds=True):
+    """(loss, preds): expand_ln_head_ce's loss (bit for bit) and gradients, with the argmax of every pixel row (uint8 [4 tokens], as
+    torch.max(logits, 1); None unless want_preds) and, with confmat int64 [K, K] + bad int64 [2], their confusion matrix with
+    the labels added in place (evaluation.SegConfusion's `confmat` and `_bad`) -- one launch, no logits (ExpandLnHeadCeStepFn)."""
+    return ExpandLnHeadCeStepFn.apply(xn2, wexp, gamma, beta, weight, labels, class_weights, xn_lo, confmat, bad, bool(want_preds))
 
 
 def expand_ln_head_depth_ok(x, width, children, f_out, kind, delta):

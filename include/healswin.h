@@ -817,6 +817,20 @@ int64_t hs_expand_ln_head_blocks(int64_t tokens);
 int hs_expand_ln_head_ce_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const uint8_t* labels,
                              const float* class_weights, int n_classes, void* y, float* logits, float* mean, float* rstd,
                              float* loss_partials, int64_t tokens, int width, int children, int dtype, void* stream);
+/* ... and WITH the caller's whole shared_step (model_lightning_swin_hp.py:104-111: `preds = torch.max(outputs, 1)`, the loss, IoU /
+ * Accuracy on (preds, masks)): hs_expand_ln_head_ce_fwd's arguments, loss partials and saved tensors (bit for bit: the same
+ * arithmetic in the same order; the backward is hs_ln_head_ce_bwd), plus, each optional (NULL: not produced),
+ *   preds   [dev] u8[4 tokens]: the row's class id as torch.max(logits, 1) gives it on the fp32 logits (first maximal class of
+ *           0..n_classes-1; a NaN counts as the maximum, the first NaN wins); 4-byte aligned;
+ *   confmat [dev] i64[n_classes, n_classes]: confmat[label, pred] += 1 per row (hs_seg_confusion's matrix; integer atomics: exact
+ *           and deterministic); rows whose label is >= n_classes stay out and are counted in
+ *   bad     [dev] i64[2]: bad[0] += their number (required with confmat; [1] is untouched: predictions are always < n_classes).
+ * No logits are needed for any of them (logits == NULL as above); y, mean, rstd NULL is the validation form.  No host
+ * synchronisation, no allocation: capturable in a HIP graph.  HS_ERR_INVALID_ARG if one wavefront could own 2^32 rows. */
+int hs_expand_ln_head_ce_step_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec,
+                                  const uint8_t* labels, const float* class_weights, int n_classes, void* y, float* logits, float* mean,
+                                  float* rstd, float* loss_partials, uint8_t* preds, int64_t* confmat, int64_t* bad, int64_t tokens,
+                                  int width, int children, int dtype, void* stream);
 int hs_ln_head_ce_bwd(const void* y, const float* mean, const float* rstd, const uint8_t* labels, const float* class_weights,
                       const float* scale, int n_classes, const void* wfold, const float* bvec, const void* afold, void* dy, void* dprime,
                       float* partials, int64_t rows, int width, int dtype, void* stream);
@@ -905,7 +919,8 @@ int hs_flat_attn_mask(int Ht, int Wt, int w, int s, float* out);
  * the valid ones are written as zeros.  H and W are multiples of p * T; T is a power of two. */
 int hs_flat_img_to_rows(const void* img, int in_dtype, void* rows, int out_dtype, int batch, int nch, int H, int W, int p, int T,
                         int mode, int64_t ld, void* stream);
-/* the inverse: token rows [dev] (HS_F32 / HS_BF16, padding columns ignored) -> [B, nch, H, W] image [dev] (HS_F32 / HS_BF16). */
+/* the inverse: token rows [dev] (HS_F32 / HS_BF16, padding columns ignored) -> [B, nch, H, W] image [dev] (HS_F32 / HS_BF16);
+ * HS_U8 rows (class ids) go to a HS_U8 image bit for bit. */
 int hs_flat_rows_to_img(const void* rows, int in_dtype, void* img, int out_dtype, int batch, int nch, int H, int W, int p, int T,
                         int mode, int64_t ld, void* stream);
 

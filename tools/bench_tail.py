@@ -4,7 +4,15 @@ channels -> 6 291 456 pixel rows x 12 classes), forward + backward, event-timed:
    fused    ops.expand_ln_head_ce      (hs_expand_ln_head_ce_fwd, hs_ln_head_ce_bwd: no logits tensor)
    unfused  ops.expand_ln_head + losses.seg_loss   (fp32 logits written, CE forward / backward kernels, dlogits read back)
 usage: bench_tail.py [--mode fused|unfused|both] [--iters 5]
-Under `rocprofv3 --pmc WRITE_SIZE --kernel-trace` with one --mode, tools/pmc_db.py sums the bytes the tail's kernels write."""
+Under `rocprofv3 --pmc WRITE_SIZE --kernel-trace` with one --mode, tools/pmc_db.py sums the bytes the tail's kernels write.
+
+--forward times the FORWARD of the segmentation caller's shared_step (loss, class ids, confusion matrix), with a gradient wanted
+(training: the expanded rows are written for the backward) and without (validation), alternating the forms in every round:
+   step      ops.expand_ln_head_ce_step  (hs_expand_ln_head_ce_step_fwd: one launch, labels in, one byte per pixel out)
+   loss      ops.expand_ln_head_ce       (hs_expand_ln_head_ce_fwd: the loss alone)
+   composed  ops.expand_ln_head + losses.seg_loss + losses.seg_predictions + SegConfusion.update (the logits written, read thrice)
+`step` is skipped on a build that lacks it (the parent commit's, for the baseline of the same session); --forms picks a subset
+and --grad train|valid one of the two (one form and one mode per process under rocprofv3 --pmc: tools/collect_tail_step_pmc.sh)."""
 import argparse
 import os
 import sys
@@ -22,6 +30,9 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--tokens", type=int, default=8 * 196608)
     ap.add_argument("--width", type=int, default=128)
+    ap.add_argument("--forward", action="store_true")
+    ap.add_argument("--forms", default="step,loss,composed")
+    ap.add_argument("--grad", default="both", choices=("train", "valid", "both"))
     a = ap.parse_args()
     dev, C, f_out, B = "cuda", a.width, 12, 8
     g = torch.Generator(device=dev).manual_seed(0)
@@ -40,6 +51,9 @@ def main():
         logits = ops.pad_slice(lg.view(B, -1, 16), f_out).transpose(1, 2)
         seg_loss(logits, labels).backward()
 
+    if a.forward:
+        return forward_forms(a, xn, wexp, gamma, beta, w, labels, f_out, B)
+
     for name, fn in (("fused", fused), ("unfused", unfused)):
         if a.mode not in ("both", name):
             continue
@@ -55,6 +69,51 @@ def main():
             if it >= 2:
                 ts.append(e0.elapsed_time(e1))
         print(f"{name:8s} tail fwd + loss + bwd: min {min(ts):.3f} ms  median {sorted(ts)[len(ts) // 2]:.3f} ms  ({a.tokens} tokens x {C})", flush=True)
+
+
+def forward_forms(a, xn, wexp, gamma, beta, w, labels, f_out, B):
+    from heal_swin_amd.evaluation import SegConfusion
+    from heal_swin_amd.losses import seg_predictions
+    conf = SegConfusion(f_out)
+    rows, C = 4 * a.tokens, a.width
+
+    def step():
+        return ops.expand_ln_head_ce_step(xn, wexp, gamma, beta, w, labels, None, confmat=conf.confmat, bad=conf._bad)
+
+    def loss():
+        return ops.expand_ln_head_ce(xn, wexp, gamma, beta, w, labels, None)
+
+    def composed():
+        lg = ops.expand_ln_head(xn, wexp, gamma, beta, w)
+        logits = ops.pad_slice(lg.view(B, -1, 16), f_out).transpose(1, 2)
+        out = seg_loss(logits, labels)
+        conf.update(logits.detach(), labels, check=False)
+        return out, seg_predictions(logits.detach()).to(torch.uint8)
+
+    forms = [(n, f) for n, f in (("step", step), ("loss", loss), ("composed", composed)) if n in a.forms.split(",")]
+    if not hasattr(ops, "expand_ln_head_ce_step"):
+        forms = [(n, f) for n, f in forms if n != "step"]
+    # the bytes the algorithm needs: xn and the labels in (+ the expanded rows, mean, rstd out in training)
+    base = {True: 2 * a.tokens * C + rows * (1 + 2 * C + 8), False: 2 * a.tokens * C + rows}
+    # composed: the padded fp32 logits written once, read by the loss, the argmax and the confusion kernel (which reads the labels
+    # again); the argmax's int64 indices written, read and narrowed to bytes
+    extra = {"step": rows, "loss": 0, "composed": rows * (64 + 3 * 64 + 1 + 8 + 8 + 1)}
+    for grad in [g for g, n in ((True, "train"), (False, "valid")) if a.grad in ("both", n)]:
+        ts = {n: [] for n, _ in forms}
+        with torch.set_grad_enabled(grad):
+            for it in range(a.iters + 2):
+                for n, fn in forms:  # alternating: every round times each form once
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if it >= 2:
+                        ts[n].append(e0.elapsed_time(e1))
+        for n, _ in forms:
+            t = sorted(ts[n])
+            print(f"{'train' if grad else 'valid'} forward {n:9s} min {t[0]:.3f} ms  median {t[len(t) // 2]:.3f} ms  max {t[-1]:.3f} ms  "
+                  f"algorithmic {(base[grad] + extra[n]) / 1e6:.1f} MB  ({a.tokens} tokens x {C}, {len(t)} rounds)", flush=True)
 
 
 if __name__ == "__main__":
