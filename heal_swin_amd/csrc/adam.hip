@@ -40,7 +40,9 @@ __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v,
     m += (g - m) * (1.f - b1);
     v = v * b2 + (1.f - b2) * g * g;
     const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
-    p -= (lr * inv_bc1) * (m / denom);
+    // (m == 0 moves nothing; skipping it keeps the zero alignment gaps of the flat buffers -- p = g = m = v = 0 -- from becoming
+    // 0 / 0 when eps is 0)
+    if (m != 0.f) p -= (lr * inv_bc1) * (m / denom);
     return p;
 }
 
@@ -90,8 +92,8 @@ int hs_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int
     using namespace hs;
     HS_CHECK_ARG(p && g && m && v && step, "hs_adam_step: null pointer");
     HS_CHECK_ARG(n > 0 && n < ((int64_t)1 << 40), "hs_adam_step: bad length");
-    HS_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0 && (uintptr_t)p_bf16 % 8 == 0,
-                 "hs_adam_step: buffers must be 16-byte aligned (bf16 copy: 8)");
+    HS_CHECK_ALIGNED("hs_adam_step", 16, p, g, m, v);
+    HS_CHECK_ALIGNED("hs_adam_step (bf16 copy)", 8, p_bf16);
     HS_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "hs_adam_step: bad hyper-parameters");
     AdamArgs a{p, g, m, v, (uint16_t*)p_bf16, n, lr, lr_dev, beta1, beta2, eps, weight_decay, decoupled, step};
     const int64_t blocks = (n + 1023) / 1024;

@@ -370,6 +370,7 @@ int launch_expand_ln_head(const void* xn, const void* xn_lo, const void* wexp, c
     if (!hs_expand_ln_head_supported(width, children, 1, dtype))
         return fail(HS_ERR_UNSUPPORTED, "%s: bf16, 4 children, C in {64, 96, 128} (got C = %d, children %d): the expand "
                     "weight must fit the LDS", who, width, children);
+    HS_CHECK_ALIGNED(who, 16, xn, xn_lo, wexp, wfold, bvec, y);  // 16-byte row chunks, weights staged into the LDS in 16-byte units
     const int nb = width / 32;
     constexpr bool kStep = std::is_same<Loss, TailCeStep>::value;
     const size_t smem = (size_t)kP * width * kRowB + 4 * 32 * kPatchRow + (kStep ? 4 * kHistBins * sizeof(uint32_t) : 0);

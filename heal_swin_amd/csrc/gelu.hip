@@ -171,7 +171,7 @@ int hs_gelu_fwd(const void* x, void* y, int64_t n, float drop_p, uint64_t seed, 
     HS_CHECK_ARG(x && y && n >= 0, "bad arguments");
     HS_CHECK_ARG(drop_p >= 0.f && drop_p <= 1.f, "drop_p must be in [0, 1]");
     HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
-    HS_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0), "buffers must be 16-byte aligned");
+    HS_CHECK_ALIGNED("hs_gelu_fwd", 16, x, y);
     if (n == 0) return HS_OK;
     hipStream_t s = (hipStream_t)stream;
     const bool drop = drop_p > 0.f;
@@ -191,7 +191,7 @@ int hs_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, float drop_p
     HS_CHECK_ARG(dy && x && dx && n >= 0, "bad arguments");
     HS_CHECK_ARG(drop_p >= 0.f && drop_p <= 1.f, "drop_p must be in [0, 1]");
     HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
-    HS_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0) && ((uintptr_t)dx % 16 == 0), "buffers must be 16-byte aligned");
+    HS_CHECK_ALIGNED("hs_gelu_bwd", 16, x, dy, dx);
     if (n == 0) return HS_OK;
     hipStream_t s = (hipStream_t)stream;
     const bool drop = drop_p > 0.f;
@@ -234,7 +234,7 @@ int hs_residual_drop(const void* x, const void* t, void* out, const float* row_s
     const int v = dtype == HS_BF16 ? 8 : 4;
     HS_CHECK_ARG(n % v == 0 && (!row_scale || (elems_per_sample > 0 && elems_per_sample % v == 0 && n % elems_per_sample == 0)),
                  "n and elems_per_sample must be multiples of the 16-byte vector width");
-    HS_CHECK_ARG(((uintptr_t)t % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((uintptr_t)x % 16 == 0), "buffers must be 16-byte aligned");
+    HS_CHECK_ALIGNED("hs_residual_drop", 16, t, out, x);
     if (n == 0) return HS_OK;
     if (dtype == HS_BF16)
         hipLaunchKernelGGL(residual_drop_kernel<bf16_t>, dim3(grid_for(n, 8)), dim3(256), 0, (hipStream_t)stream, x, t, out, row_scale,

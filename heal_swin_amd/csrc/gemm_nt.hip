@@ -830,6 +830,7 @@ int hs_gemm_nt(const void* a, int64_t lda, const void* b, int64_t ldb, int k, co
     HS_CHECK_ARG(c || (epilogue == EPI_GELU && aux), "hs_gemm_nt: no output");
     HS_CHECK_ARG(epilogue == EPI_BIAS || aux, "hs_gemm_nt: this epilogue needs aux");
     HS_CHECK_ARG(drop_p >= 0.f && drop_p <= 1.f, "hs_gemm_nt: drop_p must be in [0, 1]");
+    HS_CHECK_ALIGNED("hs_gemm_nt", 16, a, b, a2, b2, bias, c, aux);  // operands and bias travel as 16-byte buffer-to-LDS chunks
     // 16-byte operand chunks and 8-byte output groups
     if (k % 8 || k2 % 8 || lda % 8 || ldb % 8 || (k2 && (lda2 % 8 || ldb2 % 8)) || n % 4)
         return fail(HS_ERR_UNSUPPORTED, "hs_gemm_nt: k, k2 and the row strides must be multiples of 8, n a multiple of 4");

@@ -19,6 +19,13 @@ inline int isqrt_pow2_window(int ws) {
     return (side * side == ws) ? side : -1;
 }
 
+// every pointer (NULL included) is a multiple of `bytes`: the 16-byte vector / buffer-to-LDS accesses of the kernels drop or
+// mis-handle the low address bits, so a misaligned operand is refused on the host (include/healswin.h: "Pointer alignment")
+template <typename... P>
+inline bool aligned_to(uintptr_t bytes, P... p) {
+    return ((((uintptr_t)p) | ... | (uintptr_t)0) % bytes) == 0;
+}
+
 inline bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
 // Compute units the persistent / one-resident-round launches may plan for: 256 minus hs_set_reserved_cus(), spread evenly over
@@ -45,4 +52,10 @@ int set_seed_epoch_attn_mfma_f32(const void* counter);
 #define HS_CHECK_ARG(cond, ...)                                        \
     do {                                                               \
         if (!(cond)) return hs::fail(HS_ERR_INVALID_ARG, __VA_ARGS__); \
+    } while (0)
+
+#define HS_CHECK_ALIGNED(entry, bytes, ...)                                                                         \
+    do {                                                                                                            \
+        if (!hs::aligned_to(bytes, __VA_ARGS__))                                                                    \
+            return hs::fail(HS_ERR_MISALIGNED, "%s: operand pointers must be %d-byte aligned", entry, (int)(bytes)); \
     } while (0)

@@ -45,6 +45,7 @@ const char* hs_status_string(int status) {
         case HS_ERR_UNSUPPORTED: return "unsupported shape or dtype";
         case HS_ERR_HIP: return "HIP runtime error";
         case HS_ERR_NOT_PERMUTATION: return "shift is not a permutation";
+        case HS_ERR_MISALIGNED: return "misaligned pointer";
         default: return "unknown status";
     }
 }

@@ -938,6 +938,8 @@ int ln_fwd_impl(const void* x, const void* residual, const float* gamma, const f
     HS_CHECK_ARG((add_in == nullptr) == (sum_out == nullptr), "add_in and sum_out go together");
     HS_CHECK_ARG(rows >= 0 && width > 0, "bad shape");
     HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
+    // rows are moved as uint4, gamma / beta as float4 (the width-1 scalar kernels would take less, the contract is one rule)
+    HS_CHECK_ALIGNED("hs_layernorm_fwd", 16, x, residual, gamma, beta, y, add_in, sum_out, ex.lo_in, ex.lo_out);
     if (int st = check_extra(ex, rows)) return st;
     if (rows == 0) return HS_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -967,6 +969,8 @@ int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const float* 
     HS_CHECK_ARG(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && workspace, "null pointer");
     HS_CHECK_ARG(rows > 0 && width > 0, "bad shape");
     HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
+    // (dgamma / dbeta are written as float4 by the partial-record sum, csrc/reduce_many.hip)
+    HS_CHECK_ALIGNED("hs_layernorm_bwd", 16, dy, x, gamma, dx, dgamma, dbeta, workspace, dres_in, dadd_out);
     if (int st = check_extra(ex, rows)) return st;
     hipStream_t s = (hipStream_t)stream;
     const bool plain = !ex.row_scale && ex.drop_p == 0.f && !dadd_out;

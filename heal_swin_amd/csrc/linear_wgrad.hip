@@ -860,6 +860,8 @@ int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, fl
     using namespace hs;
     HS_CHECK_ARG(dy && x && dw && workspace, "null pointer");
     HS_CHECK_ARG(rows > 0 && n_out > 0 && k_in > 0, "bad shape");
+    // operands: 16-byte buffer-to-LDS chunks; dw / dbias: float4 read-modify-writes of the slice sum (csrc/reduce_many.hip)
+    HS_CHECK_ALIGNED("hs_linear_wgrad", 16, dy, x, dw, dbias, workspace);
     HS_CHECK_ARG(dtype == HS_BF16 || dtype == HS_F32, "dtype must be HS_F32 or HS_BF16");
     // bf16: k_in: 16-byte X rows.  n_out: multiples of 8, or of 4 on the LDS-DMA path (its dword-aligned buffer loads read a
     // narrow dY row -- the 12-class segmentation head -- together with its successors; the surplus columns land in
@@ -920,6 +922,9 @@ int hs_linear_wgrad_group(const hs_wgrad_problem* problems, int count, float* wo
     HS_CHECK_ARG(count >= 1 && count <= kMaxGroup, "hs_linear_wgrad_group: 1 to 4 problems");
     HS_CHECK_ARG(rows > 0, "bad shape");
     HS_CHECK_ARG(dtype == HS_BF16 || dtype == HS_F32, "dtype must be HS_F32 or HS_BF16");
+    HS_CHECK_ALIGNED("hs_linear_wgrad_group", 16, workspace);
+    for (int i = 0; i < count; ++i)  // every member before the first launch
+        HS_CHECK_ALIGNED("hs_linear_wgrad_group", 16, problems[i].dy, problems[i].x, problems[i].dw, problems[i].dbias);
     const GroupPlan pl = plan_group(problems, count, rows, dtype);
     if (!pl.grouped) {  // members that take different kernels when launched alone: one launch each, results as from the single entry points
         for (int i = 0; i < count; ++i) {

@@ -425,6 +425,7 @@ int hs_ln_head_fwd(const void* y, const void* wfold, const float* bvec, void* lo
                    int width, int dtype, int logits_dtype, void* stream) {
     using namespace hs;
     HS_CHECK_ARG(y && wfold && bvec && logits && mean && rstd, "null pointer");
+    HS_CHECK_ALIGNED("hs_ln_head_fwd", 16, y, wfold, bvec);
     HS_CHECK_ARG(rows > 0, "bad shape");
     HS_CHECK_ARG(logits_dtype == HS_BF16 || logits_dtype == HS_F32, "logits_dtype must be HS_BF16 or HS_F32");
     if (!hs_ln_head_supported(width, 1, dtype)) return fail(HS_ERR_UNSUPPORTED, "hs_ln_head: bf16 rows of 64..256 (multiple of 32) columns only");
@@ -449,6 +450,7 @@ int hs_ln_head_bwd(const void* y, const float* mean, const float* rstd, const vo
                    void* dprime, float* partials, int64_t rows, int width, int dtype, int logits_dtype, void* stream) {
     using namespace hs;
     HS_CHECK_ARG(y && mean && rstd && dlogits && afold && dy && dprime && partials, "null pointer");
+    HS_CHECK_ALIGNED("hs_ln_head_bwd", 16, y, afold, dy, dprime);
     HS_CHECK_ARG(rows > 0, "bad shape");
     HS_CHECK_ARG(logits_dtype == HS_BF16 || logits_dtype == HS_F32, "logits_dtype must be HS_BF16 or HS_F32");
     if (!hs_ln_head_supported(width, 1, dtype)) return fail(HS_ERR_UNSUPPORTED, "hs_ln_head: bf16 rows of 64..256 (multiple of 32) columns only");
@@ -474,6 +476,7 @@ int hs_ln_head_ce_bwd(const void* y, const float* mean, const float* rstd, const
                       float* partials, int64_t rows, int width, int dtype, void* stream) {
     using namespace hs;
     HS_CHECK_ARG(y && mean && rstd && labels && scale && wfold && bvec && afold && dy && dprime && partials, "null pointer");
+    HS_CHECK_ALIGNED("hs_ln_head_ce_bwd", 16, y, wfold, bvec, afold, dy, dprime);
     HS_CHECK_ARG(rows > 0, "bad shape");
     HS_CHECK_ARG(n_classes >= 1 && n_classes <= 16, "hs_ln_head_ce_bwd: 1..16 classes");
     if (!hs_ln_head_supported(width, n_classes, dtype) || width > 128)
@@ -498,6 +501,7 @@ int hs_ln_head_depth_bwd(const void* y, const float* mean, const float* rstd, co
                          float* partials, int64_t rows, int width, int dtype, void* stream) {
     using namespace hs;
     HS_CHECK_ARG(y && mean && rstd && target && scale && wfold && bvec && afold && dy && dprime && partials, "null pointer");
+    HS_CHECK_ALIGNED("hs_ln_head_depth_bwd", 16, y, wfold, bvec, afold, dy, dprime);
     HS_CHECK_ARG(rows > 0, "bad shape");
     HS_CHECK_ARG(depth_head_ok(kind, huber_delta, n_out), "hs_ln_head_depth_bwd: kind %d with %d head channels (1 or 2; Huber 1, "
                  "log variance 2; huber delta > 0)", kind, n_out);

@@ -577,6 +577,8 @@ static int mlp_fused_fwd_impl(const void* x, const float* ln_gamma, const float*
                               const float* row_scale, int64_t rows_per_sample, float drop_p, uint64_t seed_h, uint64_t seed_o) {
     using namespace hs;
     HS_CHECK_ARG(x && w1 && w2 && out, "hs_mlp_fused_fwd: null pointer");
+    // the weights go to the registers through 16-byte buffer-to-LDS loads, biases / gamma / beta as float4, rows as 16-byte chunks
+    HS_CHECK_ALIGNED("hs_mlp_fused_fwd", 16, x, ln_gamma, ln_beta, w1, b1, w2, b2, n_out, h_out, act_out, out);
     HS_CHECK_ARG(!(flags & HS_MLP_NORM_AFTER) || ln_gamma, "hs_mlp_fused_fwd: HS_MLP_NORM_AFTER needs ln_gamma / ln_beta");
     HS_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "hs_mlp_fused_fwd: ln_gamma and ln_beta go together");
     HS_CHECK_ARG((mean_out == nullptr) == (rstd_out == nullptr), "hs_mlp_fused_fwd: mean_out and rstd_out go together");
@@ -633,6 +635,7 @@ static int mlp_fused_bwd_impl(const void* dy, const void* h, const void* w2_t, c
                               int64_t rows, int channels, int hidden, int dtype, void* stream, bool drop, float drop_p, uint64_t seed_h) {
     using namespace hs;
     HS_CHECK_ARG(dy && h && w2_t && w1_t && dh && dn, "hs_mlp_fused_bwd: null pointer");
+    HS_CHECK_ALIGNED("hs_mlp_fused_bwd", 16, dy, h, w2_t, w1_t, dres, dh, dn);
     HS_CHECK_ARG(rows > 0 && rows % kT == 0, "hs_mlp_fused_bwd: rows must be a positive multiple of 32");
     if (!hs_mlp_fused_supported(channels, hidden, dtype))
         return fail(HS_ERR_UNSUPPORTED, "hs_mlp_fused_bwd: bf16, C = 96 or 128 and hidden = 4 C only (got C = %d, hidden %d)", channels, hidden);

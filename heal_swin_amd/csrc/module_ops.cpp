@@ -40,6 +40,9 @@ int hs_window_attn_module_bwd_chain(const void* dout, const void* x, const void*
     HS_CHECK_ARG((ln_gamma != nullptr) == (x && xn && mean && rstd && dln_gamma && dln_beta),
                  "hs_window_attn_module_bwd_chain: with a LayerNorm in front pass x, xn, mean, rstd, dln_gamma, dln_beta; without it none of them");
     HS_CHECK_ARG((bias == nullptr) == (dbias == nullptr), "hs_window_attn_module_bwd_chain: bias and dbias go together");
+    // what the chained entry points would refuse is refused here, before the first of them has launched anything
+    HS_CHECK_ALIGNED("hs_window_attn_module_bwd_chain", 16, dout, x, xn, qkv, attn_out, qkv_w_t, proj_w_t, ln_gamma, dx, dqkv_w, dqkv_b, dproj_w,
+                     dproj_b, dln_gamma, dln_beta, workspace);
     if (!hs_window_attn_module_supported(channels, num_heads, window_size, dtype))
         return fail(HS_ERR_UNSUPPORTED, "hs_window_attn_module_bwd_chain: bf16, window 64, head_dim 32 and C = 96 or 128 only");
     const int C = channels;

@@ -29,6 +29,8 @@ int hs_patch_merge_fwd(const void* x, const float* gamma, const float* beta, con
     if (int st = check_common("hs_patch_merge_fwd", rows, dtype)) return st;
     HS_CHECK_ARG(x && gamma && beta && w && normed && out, "hs_patch_merge_fwd: null operand");
     HS_CHECK_ARG(dim > 0 && dim % 2 == 0 && dim_out > 0 && dim_out % 4 == 0, "hs_patch_merge_fwd: dim must be even, dim_out a multiple of 4");
+    // what the chained entry points would refuse is refused here, before the first of them has launched anything
+    HS_CHECK_ALIGNED("hs_patch_merge_fwd", 16, x, gamma, beta, w, normed, out);
     const int width = 4 * dim;  // the merged row of 4 sibling pixels (:385-391)
     if (int st = hs_layernorm_fwd(x, nullptr, gamma, beta, normed, mean, rstd, rows, width, dtype, stream)) return st;  // :391
     return hs_gemm_nt(normed, width, w, width, width, nullptr, 0, nullptr, 0, 0, nullptr, out, nullptr, rows, dim_out, HS_EPI_BIAS, 0.f,
@@ -45,6 +47,7 @@ int hs_patch_merge_bwd(const void* dout, const void* x, const void* normed, cons
     if (int st = check_common("hs_patch_merge_bwd", rows, dtype)) return st;
     HS_CHECK_ARG(dout && x && normed && gamma && mean && rstd && w_t && dnormed && dx && dw && dgamma && dbeta && workspace,
                  "hs_patch_merge_bwd: null operand");
+    HS_CHECK_ALIGNED("hs_patch_merge_bwd", 16, dout, x, normed, gamma, w_t, dnormed, dx, dw, dgamma, dbeta, workspace);
     const int width = 4 * dim;
     // dW[n, k] = sum_rows dout[row, n] * LN(x)[row, k]
     if (int st = hs_linear_wgrad(dout, normed, dw, nullptr, workspace, rows, dim_out, width, accumulate, dtype, stream)) return st;
@@ -61,6 +64,7 @@ int hs_patch_expand_fwd(const void* x, const void* w, const float* gamma, const 
     HS_CHECK_ARG(x && w && gamma && beta && expanded && out, "hs_patch_expand_fwd: null operand");
     HS_CHECK_ARG(children > 0 && dim_exp % children == 0 && dim % 8 == 0 && dim_exp % 4 == 0,
                  "hs_patch_expand_fwd: dim_exp must split into `children` rows; dim a multiple of 8");
+    HS_CHECK_ALIGNED("hs_patch_expand_fwd", 16, x, w, gamma, beta, expanded, out);
     // :425 / :447 (expand, bias=False), then LayerNorm over each child row of the 'b n (p c) -> b (n p) c' view (:427-428, :449-450)
     if (int st = hs_gemm_nt(x, dim, w, dim, dim, nullptr, 0, nullptr, 0, 0, nullptr, expanded, nullptr, rows, dim_exp, HS_EPI_BIAS, 0.f, 0,
                             dtype, stream))
@@ -80,6 +84,7 @@ int hs_patch_expand_bwd(const void* dout, const void* x, const void* expanded, c
     HS_CHECK_ARG(dout && x && expanded && gamma && mean && rstd && w_t && dexpanded && dx && dw && dgamma && dbeta && workspace,
                  "hs_patch_expand_bwd: null operand");
     HS_CHECK_ARG(children > 0 && dim_exp % children == 0, "hs_patch_expand_bwd: dim_exp must split into `children` rows");
+    HS_CHECK_ALIGNED("hs_patch_expand_bwd", 16, dout, x, expanded, gamma, w_t, dexpanded, dx, dw, dgamma, dbeta, workspace);
     if (int st = hs_layernorm_bwd(dout, expanded, gamma, mean, rstd, dexpanded, dgamma, dbeta, workspace, accumulate, rows * children,
                                   dim_exp / children, dtype, stream))
         return st;

@@ -874,6 +874,9 @@ int module_fwd_impl(const char* who, const void* x, void* out, const TrainOut& t
                     int window_size, unsigned flags, int dtype, void* stream) {
     using namespace hs;
     HS_CHECK_ARG(x && out && qkv_w && proj_w && head_scale, "%s: null pointer", who);
+    // weights: 16-byte buffer-to-LDS loads; biases, gamma / beta and the gathered position bias: float4 / float2 fragments
+    HS_CHECK_ALIGNED(who, 16, x, out, qkv_w, qkv_b, proj_w, proj_b, ln_gamma, ln_beta, bias, head_scale, tr.xn, tr.qkv, tr.o, tr.ln2_g,
+                     tr.ln2_b, tr.n2);
     HS_CHECK_ARG(batch > 0 && n_tokens > 0 && n_tokens % kWs == 0, "%s: n_tokens must be a positive multiple of 64", who);
     HS_CHECK_ARG((ln_gamma == nullptr) == (ln_beta == nullptr), "%s: ln_gamma and ln_beta go together", who);
     HS_CHECK_ARG(roll >= 0 && roll < n_tokens, "%s: roll must be in [0, n_tokens)", who);

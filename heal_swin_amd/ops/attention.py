@@ -36,7 +36,7 @@ class RelPosBiasFn(torch.autograd.Function):
         rows, nh, ws = ctx.shape
         dbias = dbias.to(torch.float32).contiguous()
         order, offsets = _rel_idx_groups(rel_idx, rows)
-        buf = _sink_buffer(ctx.table)
+        buf = _sink_buffer(ctx.table, vector=False)
         if buf is not None:  # straight into the gradient sink's buffer (no AccumulateGrad add kernel)
             check(lib.hs_rel_bias_scatter_grad_sorted_add(ptr(dbias), ptr(order), ptr(offsets), ptr(buf), rows, nh, ws,
                                                           stream_ptr(dbias.device)), "hs_rel_bias_scatter_grad_sorted_add")
@@ -66,7 +66,7 @@ class CosHeadScaleFn(torch.autograd.Function):
         p = ctx.param
         ls = p.detach().reshape(-1)
         dscale = dscale.to(torch.float32).contiguous()
-        buf = _sink_buffer(p)
+        buf = _sink_buffer(p, vector=False)
         if buf is not None:
             check(lib.hs_cos_head_scale_bwd(ptr(ls), ptr(dscale), ptr(buf.view(-1)), ls.numel(), 1, stream_ptr(ls.device)), "hs_cos_head_scale_bwd")
             RT.grad_sink.deposited(p)
@@ -122,7 +122,7 @@ class RelPosBiasManyFn(torch.autograd.Function):
             if db is None:
                 continue
             db = db.to(torch.float32).contiguous()
-            buf = _sink_buffer(ctx.tables[j])
+            buf = _sink_buffer(ctx.tables[j], vector=False)
             if buf is not None:
                 sunk.append(ctx.tables[j])
                 out, a = buf, 1
@@ -167,7 +167,7 @@ class CosHeadScaleManyFn(torch.autograd.Function):
             if d is None:
                 continue
             p = ctx.params[j]
-            buf = _sink_buffer(p)
+            buf = _sink_buffer(p, vector=False)
             if buf is not None:
                 sunk.append(p)
                 out, a = buf.view(-1), 1

@@ -8,7 +8,7 @@ import torch
 from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
 from . import runtime
-from .runtime import RT, _cast_param, _defer_flag, _defer_keep, _require_gpu, _sink_buffer, _timed  # noqa: F401
+from .runtime import RT, _aligned, _cast_param, _defer_flag, _defer_keep, _require_gpu, _sink_buffer, _timed  # noqa: F401
 
 
 # ----------------------------------------------------------------------------- hs_gemm_nt (own bf16 GEMM with fused epilogues)
@@ -130,6 +130,9 @@ RESID_EPILOGUE = True
 def gemm_nt(a2d, w, bias=None, epi=0, aux=None, a2=None, w2=None, want_c=True, drop_p=0.0, seed=0):
     """c = epilogue(a2d @ w^T (+ a2 @ w2^T) + bias) through `hs_gemm_nt`; returns (c, aux).  a2d [m, k] bf16 (row stride free),
     w [n, k] bf16 (row stride free), bias fp32 [n] or None."""
+    w, w2, bias = _aligned(w), _aligned(w2), _aligned(bias)  # (views into flat parameter buffers: 16-byte operand chunks)
+    if epi != _lib.HS_EPI_GELU:
+        aux = _aligned(aux)
     m, k = a2d.shape
     n = w.shape[0]
     assert a2d.stride(1) == 1 and w.stride(1) == 1 and a2d.dtype == torch.bfloat16 and w.dtype == torch.bfloat16

@@ -5,7 +5,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
-from .runtime import RT, _defer_flag, _defer_keep, _draw_seed, _extras, _f32, _require_gpu, _sink_buffer  # noqa: F401
+from .runtime import RT, _aligned, _defer_flag, _defer_keep, _draw_seed, _extras, _f32, _require_gpu, _sink_buffer  # noqa: F401
 
 
 def _norm_param_grads(weight, bias, width, device, want):
@@ -40,12 +40,12 @@ class LayerNormFn(torch.autograd.Function):
         # an output nobody differentiates (the alias, or the non-differentiable y_lo) reaches backward as None instead of a
         # zero-filled activation-sized tensor -- which would also select the residual-gradient form of the kernel
         ctx.set_materialize_grads(False)
-        x = x.contiguous()
+        x = _aligned(x.contiguous())  # (a contiguous row slice of a wider tensor may start anywhere)
         width = x.shape[-1]
         rows = x.numel() // width
         dt = _lib.dtype_code(x.dtype)
         g, b = _f32(weight), _f32(bias)
-        res = None if residual is None else residual.contiguous()
+        res = None if residual is None else _aligned(residual.contiguous())
         if res is not None:
             assert res.shape == x.shape and res.dtype == x.dtype
         y_lo = None
@@ -61,7 +61,7 @@ class LayerNormFn(torch.autograd.Function):
             assert not passthrough and (res is not None or res_lo is None)
             y_lo = torch.empty_like(x) if want_lo else None
             rs, rps, p, seed = extras if extras is not None else (None, 1, 0.0, 0)
-            check(lib.hs_layernorm_fwd_ex(ptr(x), ptr(res), None, ptr(None if res_lo is None else res_lo.contiguous()), ptr(g), ptr(b),
+            check(lib.hs_layernorm_fwd_ex(ptr(x), ptr(res), None, ptr(None if res_lo is None else _aligned(res_lo.contiguous())), ptr(g), ptr(b),
                                           ptr(y), None, ptr(y_lo), ptr(mean), ptr(rstd), ptr(rs), rps, p, seed, rows, width, dt,
                                           stream_ptr(x.device)), "hs_layernorm_fwd_ex")
         elif extras is None:
@@ -92,13 +92,13 @@ class LayerNormFn(torch.autograd.Function):
             dx_alias = None
         if dy is None:  # only the alias was used downstream
             return dx_alias, None, None, None, None, None, None, None, None
-        dy = dy.contiguous()
+        dy = _aligned(dy.contiguous())
         dx = torch.empty_like(x)
         dgamma, dbeta, direct = _norm_param_grads(weight, bias, width, x.device, ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
         ws = torch.empty(int(lib.hs_layernorm_bwd_workspace(rows, width)), dtype=torch.float32, device=x.device)
         acc = (1 | _defer_flag(x.device)) if direct else 0
         if dx_alias is not None:
-            check(lib.hs_add_layernorm_bwd(ptr(dy), ptr(dx_alias.contiguous()), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dx),
+            check(lib.hs_add_layernorm_bwd(ptr(dy), ptr(_aligned(dx_alias.contiguous())), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dx),
                                            ptr(dgamma), ptr(dbeta), ptr(ws), acc, rows, width, dt, stream_ptr(x.device)),
                   "hs_add_layernorm_bwd")
         elif extras is None:
@@ -145,7 +145,7 @@ class AddLayerNormFn(torch.autograd.Function):
         """a_lo / want_lo: compensated residual stream (csrc/layernorm.hip): the stream operand is a + a_lo, and with want_lo the
         call returns (s, y, s_lo) with s_lo the rounding remainder of the new stream s (not differentiable)."""
         _require_gpu(a, b, weight, bias)
-        a, b = a.contiguous(), b.contiguous()
+        a, b = _aligned(a.contiguous()), _aligned(b.contiguous())
         assert a.shape == b.shape and a.dtype == b.dtype
         width = a.shape[-1]
         rows = a.numel() // width
@@ -159,7 +159,7 @@ class AddLayerNormFn(torch.autograd.Function):
         if want_lo or a_lo is not None:
             s_lo = torch.empty_like(a) if want_lo else None
             rs, rps, p, seed = extras if extras is not None else (None, 1, 0.0, 0)
-            check(lib.hs_layernorm_fwd_ex(ptr(a), None, ptr(b), ptr(None if a_lo is None else a_lo.contiguous()), ptr(g), ptr(be), ptr(y),
+            check(lib.hs_layernorm_fwd_ex(ptr(a), None, ptr(b), ptr(None if a_lo is None else _aligned(a_lo.contiguous())), ptr(g), ptr(be), ptr(y),
                                           ptr(s), ptr(s_lo), ptr(mean), ptr(rstd), ptr(rs), rps, p, seed, rows, width, dt,
                                           stream_ptr(a.device)), "hs_layernorm_fwd_ex")
         elif extras is None:
@@ -186,8 +186,8 @@ class AddLayerNormFn(torch.autograd.Function):
             if extras is None:
                 return ds, ds, None, None, None, None, None
             dy = torch.zeros_like(s)
-        dy = dy.contiguous()
-        ds_c = None if ds is None else ds.contiguous()
+        dy = _aligned(dy.contiguous())
+        ds_c = None if ds is None else _aligned(ds.contiguous())
         da = torch.empty_like(s)
         dgamma, dbeta, direct = _norm_param_grads(weight, bias, width, s.device, ctx.needs_input_grad[2] and ctx.needs_input_grad[3])
         ws = torch.empty(int(lib.hs_layernorm_bwd_workspace(rows, width)), dtype=torch.float32, device=s.device)
@@ -227,7 +227,7 @@ class GeluDropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed):
         _require_gpu(x)
-        x = x.contiguous()
+        x = _aligned(x.contiguous())
         y = torch.empty_like(x)
         dt = _lib.dtype_code(x.dtype)
         check(lib.hs_gelu_fwd(ptr(x), ptr(y), x.numel(), float(p), int(seed), dt, stream_ptr(x.device)), "hs_gelu_fwd")
@@ -239,7 +239,7 @@ class GeluDropoutFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         p, seed, dt = ctx.meta
-        dy = dy.contiguous()
+        dy = _aligned(dy.contiguous())
         dx = torch.empty_like(x)
         check(lib.hs_gelu_bwd(ptr(dy), ptr(x), ptr(dx), x.numel(), p, seed, dt, stream_ptr(x.device)), "hs_gelu_bwd")
         return dx, None, None
@@ -251,7 +251,7 @@ class ResidualDropFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, t, row_scale, p, seed):
         _require_gpu(x, t, row_scale)
-        x, t = x.contiguous(), t.contiguous()
+        x, t = _aligned(x.contiguous()), _aligned(t.contiguous())
         assert x.shape == t.shape and x.dtype == t.dtype
         rs = None if row_scale is None else row_scale.detach().to(torch.float32).contiguous()
         eps = t.numel() // t.shape[0]
@@ -267,7 +267,7 @@ class ResidualDropFn(torch.autograd.Function):
     def backward(ctx, dy):
         (rs,) = ctx.saved_tensors
         eps, p, seed, dt = ctx.meta
-        dy = dy.contiguous()
+        dy = _aligned(dy.contiguous())
         dtv = torch.empty_like(dy)
         check(lib.hs_residual_drop(None, ptr(dy), ptr(dtv), ptr(rs), eps, dy.numel(), p, seed, dt, stream_ptr(dy.device)),
               "hs_residual_drop (backward)")

@@ -6,7 +6,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
-from .runtime import RT, _cast_param, _f32, _require_gpu, _sink_buffer, _timed  # noqa: F401
+from .runtime import RT, _aligned, _cast_param, _f32, _require_gpu, _sink_buffer, _timed  # noqa: F401
 from .gemm import LinearFn, _cast_param_t, gemm_nt, own_gemm_ok  # noqa: F401
 
 
@@ -98,7 +98,7 @@ class PatchMergeFn(torch.autograd.Function):
         x = x.contiguous()
         rows, dim_out = B * N // 4, weight.shape[0]
         dt = _lib.dtype_code(x.dtype)
-        w = weight.detach().to(x.dtype).contiguous()
+        w = _aligned(weight.detach().to(x.dtype).contiguous())
         g, b = _f32(gamma), _f32(beta)
         normed = torch.empty((rows, 4 * C), dtype=x.dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
@@ -144,7 +144,7 @@ class PatchExpandFn(torch.autograd.Function):
         x = x.contiguous()
         rows, dim_exp = B * N, weight.shape[0]
         dt = _lib.dtype_code(x.dtype)
-        w = weight.detach().to(x.dtype).contiguous()
+        w = _aligned(weight.detach().to(x.dtype).contiguous())
         g, b = _f32(gamma), _f32(beta)
         expanded = torch.empty((rows, dim_exp), dtype=x.dtype, device=x.device)
         mean = torch.empty(rows * children, dtype=torch.float32, device=x.device)

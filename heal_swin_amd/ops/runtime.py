@@ -92,8 +92,17 @@ def _require_gpu(*tensors):
             )
 
 
+ALIGN = 16  # bytes: what the kernels' vector and buffer-to-LDS accesses need of every operand (include/healswin.h, "Pointer alignment")
+
+
+def _aligned(t):
+    """t itself, or a contiguous copy in a fresh allocation when t does not start on a 16-byte boundary (a view into a flat buffer
+    at an odd element offset): the C entry points refuse such a pointer, the ops take the copy instead."""
+    return t if (t is None or t.data_ptr() % ALIGN == 0) else t.clone(memory_format=torch.contiguous_format)
+
+
 def _f32(t):
-    return None if t is None else t.detach().to(torch.float32).contiguous()
+    return None if t is None else _aligned(t.detach().to(torch.float32).contiguous())
 
 
 def _draw_seed():
@@ -119,11 +128,21 @@ def _extras(x, row_scale, drop_p, seed):
     return rs, rps, float(drop_p or 0.0), int(seed or 0)
 
 
-def _sink_buffer(p):
+def _sink_buffer(p, vector=True):
     """fp32 gradient buffer of parameter p that a kernel may ADD into (a view into RT.grad_sink's flat buckets), or None when no
-    sink is installed or p is not registered with it."""
+    sink is installed or p is not registered with it.  vector=False: the depositing kernel addresses single elements (position-bias
+    table, logit_scale) and takes the view at any residue."""
     sink = RT.grad_sink
-    return None if (sink is None or p is None) else sink.grad_buffer(p)
+    buf = None if (sink is None or p is None) else sink.grad_buffer(p)
+    if not vector:
+        return buf
+    if buf is not None and buf.data_ptr() % ALIGN:
+        # parallel.GradBucketAllReduce cannot produce this on a GPU (slots of 8 elements); a sink that does is refused loudly rather
+        # than worked around: the kernels' float4 deposits cannot take the view
+        raise RuntimeError(f"the gradient sink handed out a buffer that is not {ALIGN}-byte aligned (data_ptr % {ALIGN} = "
+                           f"{buf.data_ptr() % ALIGN}) for a parameter of shape {tuple(p.shape)}: direct-deposit kernels need "
+                           f"{ALIGN}-byte aligned gradient views (include/healswin.h, 'Pointer alignment')")
+    return buf
 
 
 # Deferred parameter-gradient reductions (csrc/reduce_many.hip, include/healswin.h: HS_ACC_DEFER).  A kernel that deposits into the
@@ -211,7 +230,9 @@ class ParamCastCache:
         self.params = [p for p in params if p.dtype != dtype]
         self.dtype = dtype
         ext = [None if shadow_of is None else shadow_of(p, dtype) for p in self.params]
-        self.all_external = bool(ext) and all(e is not None and e.shape == p.shape and e.device == p.device for e, p in zip(ext, self.params))
+        # (a shadow that misses the kernels' 16-byte operand alignment is refused like one of the wrong shape: own copies instead)
+        self.all_external = bool(ext) and all(e is not None and e.shape == p.shape and e.device == p.device and e.is_contiguous() and
+                                              e.data_ptr() % ALIGN == 0 for e, p in zip(ext, self.params))
         self.shadows = ext if self.all_external else [torch.empty_like(p, dtype=dtype) for p in self.params]
         self.external_fresh = False
         self.index = {id(p): i for i, p in enumerate(self.params)}
@@ -293,6 +314,6 @@ class ParamCastCache:
 
 def _cast_param(p, dtype):
     if p.dtype == dtype:
-        return p
+        return _aligned(p)
     c = RT.cast_cache.get(p, dtype) if RT.cast_cache is not None else None
-    return p.to(dtype) if c is None else c
+    return _aligned(p.to(dtype)) if c is None else c

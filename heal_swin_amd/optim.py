@@ -46,7 +46,7 @@ class FlatAdam(torch.optim.Optimizer):
         self._lowp_view = {}
         with torch.no_grad():
             for b, g in enumerate(grad_sink.buckets):
-                P = torch.zeros_like(g)  # (alignment gaps between parameters stay finite under the Adam arithmetic)
+                P = torch.zeros_like(g)  # (the sink's alignment gaps: p = g = m = v = 0 stays 0 in csrc/adam.hip, also with eps = 0)
                 M, V = torch.zeros_like(g), torch.zeros_like(g)
                 S = torch.empty_like(g, dtype=self.lowp_dtype) if self.lowp_dtype is not None else None
                 for p in grad_sink.params:

@@ -2,7 +2,8 @@
 (backend "nccl" = RCCL over xGMI on MI355X; "gloo" in the CPU tests).
 
 The reference's only collective is Lightning-DDP's gradient all-reduce (heal_swin/train.py:182-189).  Here:
-  * every parameter's .grad is a VIEW into a few large flat fp32 buckets (no flatten/unflatten copies);
+  * every parameter's .grad is a VIEW into a few large flat fp32 buckets (no flatten/unflatten copies), each in a slot of a
+    multiple of 8 elements so that every view is 32-byte aligned (the gaps stay zero);
   * buckets are filled in reverse parameter order (the order backward produces gradients) and an async
     all-reduce is launched from a post-accumulate-grad hook the moment a bucket's last gradient lands, so
     the exchange overlaps the rest of backward;
@@ -34,14 +35,16 @@ def _graph_task_id():
 
 class GradBucketAllReduce:
     def __init__(self, params, bucket_bytes=64 << 20, process_group=None, async_wgrad=False, direct_wgrad=True,
-                 exchange_single_rank=False, comm_dtype=None, reserved_cus="auto"):
+                 exchange_single_rank=False, comm_dtype=None, reserved_cus="auto", slot=None):
         """comm_dtype: None / torch.float32 exchanges the fp32 buckets themselves; torch.bfloat16 exchanges a bf16 copy of each
         bucket (half the bytes on the xGMI links: 298 instead of 596 MB per step for HEAL-SWIN-B) -- the gradients are still
         ACCUMULATED in the fp32 buckets (kernels' direct deposit, micro-batches under no_sync()); only the wire format and the
         cross-rank sum are bf16, as with DDP's bf16 compression hook.
         reserved_cus: compute units the library's chip-filling launches leave free for RCCL's kernels while this exchange is
         active ("auto": 16 when more than one rank exchanges, else 0; see include/healswin.h:hs_set_reserved_cus and
-        profiles/archive_r01_r04/r03_cu_contention.json)."""
+        profiles/archive_r01_r04/r03_cu_contention.json).
+        slot: every parameter's place in a bucket is rounded up to a multiple of this many fp32 elements (_build).  None: SLOT = 8
+        for parameters on a GPU, where the kernels need aligned views; 1 (packed back to back) on the CPU, where nothing does."""
         self.params = [p for p in params if p.requires_grad]
         self.group = process_group
         self.async_wgrad = None
@@ -53,6 +56,10 @@ class GradBucketAllReduce:
         self._counts = []       # parameters per bucket
         self._where = {}        # param -> bucket id
         self._views = {}        # param -> its .grad view into the bucket
+        on_cuda = bool(self.params) and self.params[0].is_cuda
+        self.slot = int(slot) if slot is not None else (self.SLOT if on_cuda else 1)
+        if self.slot < 1 or (on_cuda and self.slot % self.SLOT):
+            raise ValueError(f"slot must be a positive number of elements, on a GPU a multiple of {self.SLOT} (16-byte aligned bf16 copies)")
         self._build(bucket_bytes)
         self.comm_dtype = None if comm_dtype in (None, torch.float32) else comm_dtype
         self._comm = [torch.empty_like(f, dtype=self.comm_dtype) for f in self.buckets] if self.comm_dtype is not None else None
@@ -91,11 +98,21 @@ class GradBucketAllReduce:
             ops.RT.async_wgrad = self.async_wgrad
 
     # ------------------------------------------------------------------ construction
+    SLOT = 8  # fp32 elements: on a GPU every parameter's slot in a bucket is a multiple of this
+
+    def _slot(self, numel):
+        return -(-numel // self.slot) * self.slot
+
     def _build(self, bucket_bytes):
+        """Slots of whole multiples of 8 fp32 elements, the gaps zero and owned by nobody: every gradient view starts on a 32-byte
+        boundary, and so does every parameter / moment view (and, at 16 bytes, every bf16 copy) that optim.FlatAdam lays out at the
+        same element offsets -- the kernels move their operands in 16-byte units and refuse less (include/healswin.h, "Pointer
+        alignment").  Packed back to back, a 225 x 3 position-bias table or a 3-element logit_scale (HEAL-SWIN-T, heads 3) left
+        everything behind it in its bucket at an odd element offset."""
         order = list(reversed(self.params))
         groups, cur, cur_bytes = [], [], 0
         for p in order:
-            nbytes = p.numel() * 4
+            nbytes = self._slot(p.numel()) * 4
             if cur and (cur_bytes + nbytes > bucket_bytes or cur[0].device != p.device):
                 groups.append(cur)
                 cur, cur_bytes = [], 0
@@ -104,13 +121,13 @@ class GradBucketAllReduce:
         if cur:
             groups.append(cur)
         for b, ps in enumerate(groups):
-            flat = torch.zeros(sum(p.numel() for p in ps), dtype=torch.float32, device=ps[0].device)
+            flat = torch.zeros(sum(self._slot(p.numel()) for p in ps), dtype=torch.float32, device=ps[0].device)
             off = 0
             for p in ps:
                 assert p.dtype == torch.float32, "master parameters are fp32"
                 view = flat[off:off + p.numel()].view_as(p)
                 p.grad = view
-                off += p.numel()
+                off += self._slot(p.numel())
                 self._where[p] = b
                 self._views[p] = view
             self.buckets.append(flat)

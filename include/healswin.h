@@ -16,6 +16,24 @@
  *     softmax, bias and all accumulations are fp32 in both modes.
  *   - "natural order" = the reference's nested HEALPix pixel order; "shifted order" = after
  *     shifter.shift().  Window w of an image covers shifted positions [w*Ws, (w+1)*Ws).
+ *
+ * Pointer alignment
+ *   The kernels move operands in 16-byte units (float4 / 8 x bf16 loads and stores, 16-byte-per-lane buffer loads into LDS), and
+ *   a load whose address is not a multiple of its width does not read what the pointer arithmetic says.  Every [dev] pointer of
+ *   hs_gemm_nt, hs_mlp_fused_*, hs_window_attn_module_*, hs_layernorm_* / hs_add_layernorm_*, hs_ln_head_*,
+ *   hs_expand_ln_head_* (labels, targets, class weights and predictions excepted: single elements), hs_patch_merge_*,
+ *   hs_patch_expand_*, hs_linear_wgrad* (members of a group and the destinations of sums queued for hs_reduce_flush included),
+ *   hs_gelu_*, hs_residual_drop and hs_adam_step (its bf16 copy: 8 bytes) must therefore be 16-byte aligned: activations,
+ *   weights, biases, gamma / beta, workspaces and gradient destinations alike.  They check it before anything is launched and
+ *   return HS_ERR_MISALIGNED; the entry points that chain others check every pointer first.
+ *   Entry points that address single elements take any naturally aligned pointer: hs_rel_bias_*, hs_cos_head_scale_*,
+ *   hs_transpose_many_16 (whose job table lives on the device and cannot be checked), and those that choose between a vector
+ *   and a scalar path from the pointer (hs_gather_rows, the flat / depth data paths, the evaluation kernels).
+ *   The Python layer meets the requirement by construction.  On a GPU parallel.GradBucketAllReduce gives every parameter a slot
+ *   of a multiple of 8 fp32 elements, so each gradient view -- and each parameter, moment and bf16 copy that optim.FlatAdam lays
+ *   out at the same element offsets -- starts on a 32-byte (fp32) or 16-byte (bf16) boundary.  The ops take an aligned copy of
+ *   any other parameter-like INPUT that is not (and of LayerNorm / GELU activations); a gradient sink that hands out a misaligned
+ *   DESTINATION for a vector deposit is an error (RuntimeError), not worked around.
  */
 #ifndef HEALSWIN_H
 #define HEALSWIN_H
@@ -31,7 +49,8 @@ typedef enum {
     HS_ERR_INVALID_ARG = 1,   /* reference: bare `assert` at construction / call time */
     HS_ERR_UNSUPPORTED = 2,   /* shape/dtype outside what the kernels implement */
     HS_ERR_HIP = 3,           /* a HIP runtime call failed (no device, launch failure); see hs_last_error */
-    HS_ERR_NOT_PERMUTATION = 4 /* reference: _validate_shift_result, models_torch/hp_shifting.py:96-99,385-388 */
+    HS_ERR_NOT_PERMUTATION = 4, /* reference: _validate_shift_result, models_torch/hp_shifting.py:96-99,385-388 */
+    HS_ERR_MISALIGNED = 5      /* a device pointer misses the alignment stated under "Pointer alignment" above; nothing was launched */
 } hs_status;
 
 typedef enum { HS_F32 = 0, HS_BF16 = 1 } hs_dtype;

@@ -6,6 +6,8 @@ import copy
 import pytest
 import torch
 
+from _util import GRAD_TOL, TOL, assert_close
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -190,3 +192,164 @@ def test_flat_adam_in_a_captured_training_step():
     finally:
         dpa.remove()
         dpb.remove()
+
+
+def _heads3_run(cos, kind, x, y):
+    """One model of the heads-3 shape family (embed 96, heads [3, 6], window 64: a 225 x 3 position-bias table, a 3-element logit_scale)
+    trained for one step through model(x) + seg_loss (logits and gradients kept) and four more through forward_seg_loss (losses kept).
+    kind: "flat" FlatAdam with its bf16 shadows handed to the model | "own" FlatAdam, the cast cache makes its own copies |
+    "fp32" FlatAdam, fp32 activations | "torch" torch.optim.Adam(fused=True)."""
+    from heal_swin_amd.data_spec import DataSpec
+    from heal_swin_amd.losses import seg_loss
+    from heal_swin_amd.models_torch.swin_hp_transformer import SwinHPTransformerConfig, SwinHPTransformerSys
+    from heal_swin_amd.optim import FlatAdam
+    from heal_swin_amd.parallel import GradBucketAllReduce
+    spec = DataSpec(dim_in=12 * 32 * 32, f_in=3, f_out=12, base_pix=12, class_names=[])
+    cfg = SwinHPTransformerConfig(patch_size=4, window_size=64, shift_size=32, rel_pos_bias="flat", embed_dim=96, depths=[2, 2],
+                                  num_heads=[3, 6], drop_path_rate=0.0, use_cos_attn=cos)
+    torch.manual_seed(0)
+    model = SwinHPTransformerSys(cfg, spec).to(DEV).train()
+    model.compute_dtype = torch.float32 if kind == "fp32" else torch.bfloat16
+    dp = GradBucketAllReduce(model.parameters())
+    out = {}
+    try:
+        if kind == "torch":
+            opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=True)
+        else:
+            opt = FlatAdam(model.parameters(), dp, lr=1e-3, model=model)
+            if kind == "own":
+                model.__dict__.pop("_shadow_provider")
+            named = dict(model.named_parameters())
+            out["offsets"] = {n: (dp._views[p].storage_offset(), opt._lowp_view[id(p)].data_ptr() % 16, p.data_ptr() % 16, p.dim())
+                              for n, p in named.items()}
+            out["gaps"] = sum(f.numel() for f in dp.buckets) - sum(p.numel() for p in dp.params)
+        dp.zero_grad()
+        logits = model(x)
+        loss = seg_loss(logits, y)
+        loss.backward()
+        dp.finish()
+        out["logits"] = logits.detach().float().clone()
+        out["grads"] = {n: p.grad.detach().clone() for n, p in model.named_parameters()}
+        out["losses"] = [float(loss)]
+        opt.step()
+        for _ in range(4):
+            dp.zero_grad()
+            loss = model.forward_seg_loss(x, y)
+            loss.backward()
+            dp.finish()
+            opt.step()
+            out["losses"].append(float(loss))
+        cache = model.__dict__.get("_cast_cache")
+        out["external"] = bool(cache is not None and cache.all_external)
+        if cache is not None and kind != "torch":
+            for p, sh in zip(cache.params, cache.shadows):
+                assert sh.data_ptr() % 16 == 0, "a bf16 weight copy the kernels read must be 16-byte aligned"
+            if out["external"]:
+                for p, sh in zip(cache.params, cache.shadows):
+                    assert torch.equal(sh, p.detach().to(torch.bfloat16))
+        for P in getattr(opt, "_flat_p", []):
+            assert bool(torch.isfinite(P).all())
+    finally:
+        dp.remove()
+    return out
+
+
+@pytest.mark.parametrize("cos", [False, True])
+def test_flat_adam_on_the_heads_3_layout(cos):
+    """The reference's default head counts make odd-sized parameters (675-element position-bias tables, 3-element logit scales).
+    Packed back to back in the gradient buckets they would put Linear weights, their bf16 copies, biases, gamma / beta and the
+    direct-deposit gradient views at odd element offsets (asserted below from the parameter sizes, so that the case cannot pass
+    vacuously); with the slot rule every view FlatAdam hands out is 32-byte (bf16 copies: 16-byte) aligned, the model reads
+    FlatAdam's bf16 copies directly and computes what it computes on copies of its own and in fp32."""
+    g = torch.Generator(device=DEV).manual_seed(3)
+    x = torch.randint(0, 256, (2, 3, 12 * 32 * 32), generator=g, device=DEV).float()
+    y = torch.randint(0, 12, (2, 12 * 32 * 32), generator=g, device=DEV, dtype=torch.uint8)
+    runs = {k: _heads3_run(cos, k, x, y) for k in ("flat", "own", "fp32", "torch")}
+    offs = runs["flat"]["offsets"]
+    # ---- the precondition, from the layout itself: where the same parameters would sit without the slot rule (reversed order,
+    # no padding: a slot offset minus the padding in front of it)
+    packed, pad = {}, 0
+    for n, v in sorted(offs.items(), key=lambda kv: kv[1][0]):
+        packed[n] = v[0] - pad
+        pad += -runs["flat"]["grads"][n].numel() % 8
+    weights = [n for n, v in offs.items() if v[3] == 2 and n.endswith(".weight")]  # the Linear weights
+    if not cos:
+        assert any(packed[n] % 2 for n in weights), "a Linear weight at an odd element offset is what this case is about"
+    else:
+        assert any(packed[n] % 2 for n in offs if n.endswith("logit_scale")), "a logit_scale view at an odd element offset"
+        assert any((2 * packed[n]) % 16 for n in weights), "a bf16 weight copy at a nonzero 16-byte residue"
+    assert pad > 0 and runs["flat"]["gaps"] == pad, "this model has odd-sized parameters: the slot rule must have left gaps"
+    assert all(v[0] % 8 == 0 and v[1] == 0 and v[2] == 0 for v in offs.values()), "every view starts on its slot"
+    assert runs["flat"]["external"], "aligned shadows are taken: no copy pass"
+    assert not runs["own"]["external"]
+    # ---- one step: logits and every parameter gradient, shadows vs own copies vs fp32
+    BF = torch.bfloat16
+    tag = f"heads-3 cos={cos}"
+    assert_close(runs["flat"]["logits"], runs["own"]["logits"], TOL[BF], tag + ": logits, FlatAdam's shadows vs own copies")
+    assert_close(runs["flat"]["logits"], runs["fp32"]["logits"], TOL[BF], tag + ": logits, shadows vs fp32")
+    assert_close(runs["own"]["logits"], runs["fp32"]["logits"], TOL[BF], tag + ": logits, own copies vs fp32")
+    bad = []
+    for n, ref in runs["fp32"]["grads"].items():
+        for a, b, what in ((runs["flat"]["grads"][n], runs["own"]["grads"][n], "shadows vs own copies"),
+                           (runs["flat"]["grads"][n], ref, "shadows vs fp32"), (runs["own"]["grads"][n], ref, "own copies vs fp32")):
+            try:
+                assert_close(a, b, GRAD_TOL[BF], f"{tag}: grad {n}, {what}")
+            except AssertionError as e:
+                bad.append(str(e))
+    assert not bad, "\n".join(bad)
+    # ---- five steps against torch.optim.Adam(fused=True)
+    assert runs["flat"]["losses"][0] == runs["torch"]["losses"][0]
+    for kind in ("flat", "own"):
+        for a, b in zip(runs["torch"]["losses"], runs[kind]["losses"]):
+            assert abs(a - b) <= 2e-3 * abs(a), (kind, runs["torch"]["losses"], runs[kind]["losses"])
+    assert runs["flat"]["losses"][-1] < runs["flat"]["losses"][0]
+
+
+def test_flat_adam_gaps_stay_zero_also_without_eps():
+    """The alignment gaps of the buckets (p = g = m = v = 0) go through the Adam kernel with everything else: they stay exactly zero,
+    for eps > 0 and for eps = 0 (no 0 / 0: the kernel moves nothing where the first moment is zero)."""
+    from heal_swin_amd.optim import FlatAdam
+    from heal_swin_amd.parallel import GradBucketAllReduce
+    for eps in (1e-8, 0.0):
+        a, b = _toy(5), _toy(5)
+        ref = torch.optim.Adam(a, lr=3e-3, eps=eps)
+        dp = GradBucketAllReduce(b, direct_wgrad=False)
+        try:
+            opt = FlatAdam(b, dp, lr=3e-3, eps=eps, lowp_dtype=torch.bfloat16)
+            assert all(p.data_ptr() % 32 == 0 and p.grad.data_ptr() % 32 == 0 for p in b)
+            gaps = []
+            for i, f in enumerate(dp.buckets):
+                owned = torch.zeros(f.numel(), dtype=torch.bool, device=DEV)
+                for p in b:
+                    if dp._where[p] == i:
+                        off = dp._views[p].storage_offset()
+                        owned[off:off + p.numel()] = True
+                gaps.append(~owned)
+            assert sum(int(g.sum()) for g in gaps) > 0
+            gen = torch.Generator(device=DEV).manual_seed(1)
+            for it in range(3):
+                for x, y in zip(a, b):
+                    grad = torch.randn(x.shape, generator=gen, device=DEV) + 0.5  # (no exact zeros: eps = 0 stays finite on real elements)
+                    x.grad = grad.clone()
+                    y.grad.copy_(grad)
+                ref.step()
+                opt.step()
+                for P, M, V, G, gap in zip(opt._flat_p, opt._flat_m, opt._flat_v, dp.buckets, gaps):
+                    assert bool(torch.isfinite(P).all()) and bool(torch.isfinite(M).all()) and bool(torch.isfinite(V).all())
+                    assert not bool(P[gap].any()) and not bool(M[gap].any()) and not bool(V[gap].any()) and not bool(G[gap].any())
+            for x, y in zip(a, b):
+                assert float((x - y).abs().max()) <= 2e-6 * float(x.abs().max()), (eps, tuple(x.shape))
+        finally:
+            dp.remove()
+
+
+def test_a_gpu_sink_cannot_be_packed():
+    """On a GPU the slot is a multiple of 8 elements by construction: no caller can make a sink whose views the kernels would refuse."""
+    from heal_swin_amd.parallel import GradBucketAllReduce
+    with pytest.raises(ValueError, match="multiple of 8"):
+        GradBucketAllReduce(_toy(), slot=1, direct_wgrad=False)
+    dp = GradBucketAllReduce(_toy(), slot=16, direct_wgrad=False)
+    try:
+        assert all(v.data_ptr() % 64 == 0 for v in dp._views.values())
+    finally:
+        dp.remove()

@@ -95,6 +95,55 @@ def test_single_process_is_a_noop_wrapper():
     assert torch.equal(flat, dp.buckets[0])  # .grad tensors are views into the flat bucket
 
 
+def _odd_params():
+    torch.manual_seed(5)
+    # the shapes that put HEAL-SWIN-T (heads 3, window 64) at odd offsets: a 225 x 3 position-bias table, a 3-element logit_scale
+    shapes = [(96, 96), (96,), (225, 3), (3, 1, 1), (288, 96), (1,), (7, 5, 3), (13,), (16, 8)]
+    return [torch.nn.Parameter(torch.randn(s)) for s in shapes]
+
+
+@pytest.mark.parametrize("bucket_bytes", [64 << 20, 4096])
+def test_every_slot_starts_on_a_multiple_of_eight_elements(bucket_bytes):
+    """The slot rule the kernels' 16-byte operand accesses rely on (include/healswin.h, "Pointer alignment"; the default on a GPU,
+    asked for explicitly here -- CPU buckets stay packed, nothing on the CPU needs the alignment): whatever the sizes of
+    the parameters in front of it, a gradient view starts at a multiple of 8 fp32 elements of its bucket (32 bytes; 16 for the bf16
+    copy optim.FlatAdam lays out at the same offsets), views do not overlap, the gaps are counted in the bucket length and stay
+    zero, and a bucket still closes at bucket_bytes."""
+    sys.path.insert(0, ROOT)
+    from heal_swin_amd.parallel import GradBucketAllReduce
+
+    params = _odd_params()
+    dp = GradBucketAllReduce(params, bucket_bytes=bucket_bytes, slot=8)
+    assert dp.slot == 8 and GradBucketAllReduce(_odd_params()).slot == 1
+    assert (len(dp.buckets) == 1) == (bucket_bytes > 1e6)
+    ends = [0] * len(dp.buckets)
+    for p in reversed(params):  # the order the buckets are filled in
+        b, v = dp._where[p], dp._views[p]
+        flat = dp.buckets[b]
+        off = v.storage_offset() - flat.storage_offset()
+        assert v.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr() and v.shape == p.shape and v.is_contiguous()
+        assert off % 8 == 0 and v.data_ptr() % 32 == 0, (tuple(p.shape), off)
+        assert off == ends[b], "slots follow each other with no gap larger than the rounding"
+        ends[b] = off + (p.numel() + 7) // 8 * 8
+    assert [f.numel() for f in dp.buckets] == ends
+    assert all(f.numel() * 4 <= bucket_bytes or n == 1 for f, n in zip(dp.buckets, dp._counts))
+    assert sum(ends) == sum((p.numel() + 7) // 8 * 8 for p in params) > sum(p.numel() for p in params)
+    # gradients land in the views; the gaps stay zero through a backward pass and a zero_grad
+    dp.zero_grad()
+    sum((p * (i + 1.0)).sum() for i, p in enumerate(params)).backward()
+    dp.finish()
+    for i, p in enumerate(params):
+        assert p.grad.data_ptr() == dp._views[p].data_ptr() and torch.equal(p.grad, torch.full_like(p, i + 1.0))
+    owned = [torch.zeros(f.numel(), dtype=torch.bool) for f in dp.buckets]
+    for p in params:
+        off = dp._views[p].storage_offset()
+        owned[dp._where[p]][off:off + p.numel()] = True
+    assert all(bool((f[~o] == 0).all()) and bool((f[o] != 0).all()) for f, o in zip(dp.buckets, owned))
+    dp.zero_grad()
+    assert all(bool((f == 0).all()) for f in dp.buckets)
+    dp.remove()
+
+
 def test_skipped_finish_is_reported():
     """Two backward() calls without finish() in between (easy to do on one GPU, where nothing is exchanged) used to let the
     direct-deposit gradients pile up silently; the second backward now raises."""
