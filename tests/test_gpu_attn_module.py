@@ -34,8 +34,10 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("C,nH,B,nside,strategy,shift,cosine,use_bias,use_ln,residual,qkv_bias", CASES)
-def test_module_kernel_vs_oracle(C, nH, B, nside, strategy, shift, cosine, use_bias, use_ln, residual, qkv_bias):
+def module_kernel_case(C, nH, B, nside, strategy, shift, cosine, use_bias, use_ln, residual, qkv_bias):
+    """One inference-form case: builds the inputs, evaluates the oracle once, runs the kernel and holds it to the oracle.  Returns
+    (y, run): `run()` launches the kernel again on the same device tensors (tests/test_gpu_attn_persistent.py repeats the launch under
+    another slot count)."""
     from heal_swin_amd import ops
     from oracle import tables as T
     N = 8 * nside * nside
@@ -59,15 +61,25 @@ def test_module_kernel_vs_oracle(C, nH, B, nside, strategy, shift, cosine, use_b
 
     d = lambda t: None if t is None else t.to(DEV)  # noqa: E731
     use_roll = strategy == "nest_roll"
-    with torch.no_grad():
-        assert ops.window_attn_module_ok(x.to(DEV).to(torch.bfloat16), nH, 64)
-        y = ops.window_attn_module(x.to(DEV).to(torch.bfloat16), d(wqkv), d(bqkv), d(wp), d(bp), d(bias), d(hscale),
-                                   None if (use_roll or idx is None) else idx.to(torch.int32).to(DEV), shift if use_roll else 0,
-                                   None if labels is None else labels.to(torch.uint8).to(DEV), nH, 64, cosine,
-                                   ln_weight=None if ln is None else d(ln[0]), ln_bias=None if ln is None else d(ln[1]),
-                                   residual=residual)
+    args = (x.to(DEV).to(torch.bfloat16), d(wqkv), d(bqkv), d(wp), d(bp), d(bias), d(hscale),
+            None if (use_roll or idx is None) else idx.to(torch.int32).to(DEV), shift if use_roll else 0,
+            None if labels is None else labels.to(torch.uint8).to(DEV), nH, 64, cosine)
+    kw = dict(ln_weight=None if ln is None else d(ln[0]), ln_bias=None if ln is None else d(ln[1]), residual=residual)
+
+    def run():
+        with torch.no_grad():
+            assert ops.window_attn_module_ok(args[0], nH, 64)
+            return ops.window_attn_module(*args, **kw)
+
+    y = run()
     # bf16 intermediates (normalised x, q / k / v, P, O) inside the kernel: bf16 tolerance
     assert_close(y, ref, 1.5e-2, "module out")
+    return y, run
+
+
+@pytest.mark.parametrize("C,nH,B,nside,strategy,shift,cosine,use_bias,use_ln,residual,qkv_bias", CASES)
+def test_module_kernel_vs_oracle(C, nH, B, nside, strategy, shift, cosine, use_bias, use_ln, residual, qkv_bias):
+    module_kernel_case(C, nH, B, nside, strategy, shift, cosine, use_bias, use_ln, residual, qkv_bias)
 
 
 @pytest.mark.parametrize("cfgkw", [dict(embed_dim=128, num_heads=[4, 8], shift_strategy="nest_roll", shift_size=32, bp=12),
@@ -154,8 +166,7 @@ TRAIN_CASES = [
 ]
 
 
-@pytest.mark.parametrize("C,nH,B,nside,strategy,shift,cosine,use_bias,qkv_bias,v1", TRAIN_CASES)
-def test_module_train_form_vs_oracle_and_composition(C, nH, B, nside, strategy, shift, cosine, use_bias, qkv_bias, v1):
+def module_train_form_case(C, nH, B, nside, strategy, shift, cosine, use_bias, qkv_bias, v1):
     """out = x + proj(attention(qkv(LayerNorm(x)))) by ONE launch that also saves LayerNorm(x), its statistics, qkv, the attention
     output and the log-sum-exp rows; the backward is the composed path's on those tensors.  Output and EVERY gradient (x, norm
     weight / bias, qkv and proj weight / bias, bias table, head scale) against the oracle's autograd on bf16-rounded inputs, and
@@ -244,14 +255,21 @@ def test_module_train_form_vs_oracle_and_composition(C, nH, B, nside, strategy, 
         if k == "hscale" and not cosine:
             continue
         assert_close(G_f[k], G_c[k], 3e-2, f"train-form d{k} vs composition")
+    return out_f, run
 
 
-def test_module_train_form_saved_tensors_equal_the_separate_kernels():
+@pytest.mark.parametrize("C,nH,B,nside,strategy,shift,cosine,use_bias,qkv_bias,v1", TRAIN_CASES)
+def test_module_train_form_vs_oracle_and_composition(C, nH, B, nside, strategy, shift, cosine, use_bias, qkv_bias, v1):
+    module_train_form_case(C, nH, B, nside, strategy, shift, cosine, use_bias, qkv_bias, v1)
+
+
+def module_train_form_saved_tensors_case(B, out_tol=4e-3):
     """C ABI: xn / mean / rstd are those of hs_layernorm_fwd bit for bit (same arithmetic per row), qkv and the attention output
-    those of hs_gemm_nt / hs_window_attn_fwd on them to bf16 rounding, lse to fp32 rounding of the same scores."""
+    those of hs_gemm_nt / hs_window_attn_fwd on them to bf16 rounding, lse to fp32 rounding of the same scores.
+    out_tol: bound on `out` against the proj GEMM on the saved attention output (see tests/test_gpu_attn_persistent.py)."""
     from heal_swin_amd import ops, _lib
     from heal_swin_amd._lib import check, lib, ptr
-    B, N, C, nH = 2, 8 * 16 * 16, 128, 4
+    N, C, nH = 8 * 16 * 16, 128, 4
     g = torch.Generator(device=DEV).manual_seed(5)
     x = (torch.randn(B, N, C, generator=g, device=DEV) * 2 + 0.3).to(torch.bfloat16)
     wq = (torch.randn(3 * C, C, generator=g, device=DEV) * C ** -0.5).to(torch.bfloat16)
@@ -290,7 +308,11 @@ def test_module_train_form_saved_tensors_equal_the_separate_kernels():
         assert_close(o, o2, 4e-3, "attention output")
         assert_close(lse, lse2, 1e-5, "lse")
         out2 = ops.gemm_nt(o.reshape(-1, C), wp, bp, _lib.HS_EPI_RESID, aux=x.reshape(-1, C))[0].view(B, N, C)
-        assert_close(out, out2, 4e-3, "out")
+        assert_close(out, out2, out_tol, "out")
+
+
+def test_module_train_form_saved_tensors_equal_the_separate_kernels():
+    module_train_form_saved_tensors_case(2)
 
 
 def test_model_training_step_uses_the_train_form_and_matches_the_composition():

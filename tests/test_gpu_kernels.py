@@ -131,7 +131,7 @@ def _oracle_core(qkv, bias, hscale, idx, labels, nH, Ws, cosine):
     o = (OM.softmax_lastdim(s) @ v).permute(0, 1, 3, 2, 4).reshape(B, N, C)
     if idx is not None:
         inv = torch.empty_like(idx)
-        inv[idx] = torch.arange(N)
+        inv[idx] = torch.arange(N, device=idx.device)
         o = o[:, inv]
     return o
 
