@@ -796,6 +796,19 @@ int launch_tile(GemmParams& p, int epi, int wgs_per_cu, hipStream_t s) {
 }
 
 }  // namespace
+
+int gemm_nt_check_shape(const char* who, int64_t lda, int64_t ldb, int k, int64_t lda2, int64_t ldb2, int k2, int64_t m, int n) {
+    HS_CHECK_ARG(m > 0 && n > 0 && k > 0 && k2 >= 0, "%s: empty shape", who);
+    // 16-byte operand chunks and 8-byte output groups
+    if (k % 8 || k2 % 8 || lda % 8 || ldb % 8 || (k2 && (lda2 % 8 || ldb2 % 8)) || n % 4)
+        return fail(HS_ERR_UNSUPPORTED, "%s: k, k2 and the row strides must be multiples of 8, n a multiple of 4", who);
+    if (lda * 2 * 256 > kMaxRecords || ldb * 2 * 256 > kMaxRecords || (int64_t)n * 2 * 256 > kMaxRecords)
+        return fail(HS_ERR_UNSUPPORTED, "%s: row stride too large", who);
+    // (the 128 x 128 tile has the most tiles; launch_tile counts those of the tile it launches)
+    if (((m + 127) / 128) * (((int64_t)n + 127) / 128) > 0x7fffffff) return fail(HS_ERR_UNSUPPORTED, "%s: too many output tiles", who);
+    return HS_OK;
+}
+
 }  // namespace hs
 
 namespace {
@@ -831,11 +844,7 @@ int hs_gemm_nt(const void* a, int64_t lda, const void* b, int64_t ldb, int k, co
     HS_CHECK_ARG(epilogue == EPI_BIAS || aux, "hs_gemm_nt: this epilogue needs aux");
     HS_CHECK_ARG(drop_p >= 0.f && drop_p <= 1.f, "hs_gemm_nt: drop_p must be in [0, 1]");
     HS_CHECK_ALIGNED("hs_gemm_nt", 16, a, b, a2, b2, bias, c, aux);  // operands and bias travel as 16-byte buffer-to-LDS chunks
-    // 16-byte operand chunks and 8-byte output groups
-    if (k % 8 || k2 % 8 || lda % 8 || ldb % 8 || (k2 && (lda2 % 8 || ldb2 % 8)) || n % 4)
-        return fail(HS_ERR_UNSUPPORTED, "hs_gemm_nt: k, k2 and the row strides must be multiples of 8, n a multiple of 4");
-    if (lda * 2 * 256 > kMaxRecords || ldb * 2 * 256 > kMaxRecords || (int64_t)n * 2 * 256 > kMaxRecords)
-        return fail(HS_ERR_UNSUPPORTED, "hs_gemm_nt: row stride too large");
+    if (int st = gemm_nt_check_shape("hs_gemm_nt", lda, ldb, k, lda2, ldb2, k2, m, n)) return st;
     GemmParams p{};
     p.a = (const uint16_t*)a; p.b = (const uint16_t*)b; p.lda = lda; p.ldb = ldb; p.k = k;
     p.a2 = (const uint16_t*)a2; p.b2 = (const uint16_t*)b2; p.lda2 = lda2; p.ldb2 = ldb2; p.k2 = k2;

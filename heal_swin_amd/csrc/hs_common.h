@@ -47,6 +47,16 @@ int set_seed_epoch_attn_generic(const void* counter);
 int set_seed_epoch_attn_mfma(const void* counter);
 int set_seed_epoch_attn_mfma_f32(const void* counter);
 
+// The shape halves of the argument checks of hs_gemm_nt, hs_linear_wgrad*, hs_layernorm_* and hs_window_attn_fwd / _bwd: no
+// pointer is read and nothing is launched.  Each entry point runs its own; the operators that chain several of them
+// (patch_ops.cpp, module_ops.cpp) run those of every link before their first launch, so that a call one link would refuse
+// has deposited nothing by then.  `who` prefixes the message.  Defined next to the entry point concerned.
+int gemm_nt_check_shape(const char* who, int64_t lda, int64_t ldb, int k, int64_t lda2, int64_t ldb2, int k2, int64_t m, int n);
+int linear_wgrad_check_shape(const char* who, int64_t rows, int n_out, int k_in, int dtype);
+int layernorm_check_shape(const char* who, int64_t rows, int width, int dtype);
+int window_attn_check_shape(const char* who, int batch, int64_t n_tokens, int channels, int num_heads, int window_size, int64_t roll,
+                            int dtype);
+
 }  // namespace hs
 
 #define HS_CHECK_ARG(cond, ...)                                        \

@@ -920,6 +920,16 @@ int with_shape(int width, F&& f) {
 }
 
 }  // namespace
+
+// what with_shape can place: 512 chunks of 8 (bf16) / 4 (fp32) elements per row, 1024 single elements where the width has no such chunks
+int layernorm_check_shape(const char* who, int64_t rows, int width, int dtype) {
+    HS_CHECK_ARG(rows >= 0 && width > 0, "%s: bad shape", who);
+    HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "%s: dtype must be HS_F32 or HS_BF16", who);
+    const int vec = dtype == HS_BF16 ? 8 : 4;
+    if (width > (width % vec == 0 ? 512 * vec : 1024)) return fail(HS_ERR_UNSUPPORTED, "%s: layernorm width %d too large", who, width);
+    return HS_OK;
+}
+
 }  // namespace hs
 
 namespace {
@@ -936,8 +946,7 @@ int ln_fwd_impl(const void* x, const void* residual, const float* gamma, const f
     HS_CHECK_ARG(x && gamma && beta && y, "null pointer");
     HS_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "mean and rstd must both be given or both be null");
     HS_CHECK_ARG((add_in == nullptr) == (sum_out == nullptr), "add_in and sum_out go together");
-    HS_CHECK_ARG(rows >= 0 && width > 0, "bad shape");
-    HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
+    if (int st = layernorm_check_shape("hs_layernorm_fwd", rows, width, dtype)) return st;
     // rows are moved as uint4, gamma / beta as float4 (the width-1 scalar kernels would take less, the contract is one rule)
     HS_CHECK_ALIGNED("hs_layernorm_fwd", 16, x, residual, gamma, beta, y, add_in, sum_out, ex.lo_in, ex.lo_out);
     if (int st = check_extra(ex, rows)) return st;
@@ -967,8 +976,8 @@ int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const float* 
                 void* dadd_out, const hs::LnExtra& ex, int v1_mode, int accumulate) {
     using namespace hs;
     HS_CHECK_ARG(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && workspace, "null pointer");
-    HS_CHECK_ARG(rows > 0 && width > 0, "bad shape");
-    HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
+    HS_CHECK_ARG(rows > 0, "bad shape");
+    if (int st = layernorm_check_shape("hs_layernorm_bwd", rows, width, dtype)) return st;
     // (dgamma / dbeta are written as float4 by the partial-record sum, csrc/reduce_many.hip)
     HS_CHECK_ALIGNED("hs_layernorm_bwd", 16, dy, x, gamma, dx, dgamma, dbeta, workspace, dres_in, dadd_out);
     if (int st = check_extra(ex, rows)) return st;

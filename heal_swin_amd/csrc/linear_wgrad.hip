@@ -812,6 +812,23 @@ inline GroupPlan plan_group(const hs_wgrad_problem* p, int count, int64_t rows, 
 }
 
 }  // namespace
+
+int linear_wgrad_check_shape(const char* who, int64_t rows, int n_out, int k_in, int dtype) {
+    HS_CHECK_ARG(rows > 0 && n_out > 0 && k_in > 0, "%s: bad shape", who);
+    HS_CHECK_ARG(dtype == HS_BF16 || dtype == HS_F32, "%s: dtype must be HS_F32 or HS_BF16", who);
+    // bf16: k_in: 16-byte X rows.  n_out: multiples of 8, or of 4 on the LDS-DMA path (its dword-aligned buffer loads read a
+    // narrow dY row -- the 12-class segmentation head -- together with its successors; the surplus columns land in
+    // accumulators that are never stored).  fp32: multiples of 4 (16-byte rows); LDS-DMA path only.
+    if (dtype == HS_BF16 && (n_out % 4 || k_in % 8))
+        return fail(HS_ERR_UNSUPPORTED, "%s: bf16: n_out must be a multiple of 4 and k_in a multiple of 8", who);
+    if (dtype == HS_F32 && (n_out % 4 || k_in % 4)) return fail(HS_ERR_UNSUPPORTED, "%s: fp32: n_out and k_in must be multiples of 4", who);
+    const Geometry g = dtype == HS_F32 ? make_geometry_f32(rows, n_out, k_in) : make_geometry(rows, n_out, k_in);
+    if (dtype == HS_BF16 && n_out % 8 && !g.dma)
+        return fail(HS_ERR_UNSUPPORTED, "%s: n_out must be a multiple of 8 for slices beyond 2 GiB", who);
+    if (dtype == HS_F32 && !g.dma) return fail(HS_ERR_UNSUPPORTED, "%s: fp32: a token slice exceeds the 2 GiB buffer-offset range", who);
+    return HS_OK;
+}
+
 }  // namespace hs
 
 extern "C" {
@@ -859,16 +876,9 @@ int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, fl
                       int accumulate, int dtype, void* stream, int ldy, int ldx, int yc0, int xc0, bool gelu_x) {
     using namespace hs;
     HS_CHECK_ARG(dy && x && dw && workspace, "null pointer");
-    HS_CHECK_ARG(rows > 0 && n_out > 0 && k_in > 0, "bad shape");
     // operands: 16-byte buffer-to-LDS chunks; dw / dbias: float4 read-modify-writes of the slice sum (csrc/reduce_many.hip)
     HS_CHECK_ALIGNED("hs_linear_wgrad", 16, dy, x, dw, dbias, workspace);
-    HS_CHECK_ARG(dtype == HS_BF16 || dtype == HS_F32, "dtype must be HS_F32 or HS_BF16");
-    // bf16: k_in: 16-byte X rows.  n_out: multiples of 8, or of 4 on the LDS-DMA path (its dword-aligned buffer loads read a
-    // narrow dY row -- the 12-class segmentation head -- together with its successors; the surplus columns land in
-    // accumulators that are never stored).  fp32: multiples of 4 (16-byte rows); LDS-DMA path only.
-    if (dtype == HS_BF16 && (n_out % 4 || k_in % 8))
-        return fail(HS_ERR_UNSUPPORTED, "bf16: n_out must be a multiple of 4 and k_in a multiple of 8");
-    if (dtype == HS_F32 && (n_out % 4 || k_in % 4)) return fail(HS_ERR_UNSUPPORTED, "fp32: n_out and k_in must be multiples of 4");
+    if (int st = linear_wgrad_check_shape("hs_linear_wgrad", rows, n_out, k_in, dtype)) return st;
     Geometry g = dtype == HS_F32 ? make_geometry_f32(rows, n_out, k_in) : make_geometry(rows, n_out, k_in);
     if (gelu_x && !(dtype == HS_BF16 && g.dma && g.tile_k != 256 && g.tile_n != 256))
         return fail(HS_ERR_UNSUPPORTED, "hs_linear_wgrad_gelu: bf16 and the 128 x 128 LDS-DMA tile only (n_out <= 128-class shapes)");
@@ -877,8 +887,6 @@ int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, fl
         if (!g.dma || g.rows_per_slice * (int64_t)(ldy > ldx ? ldy : ldx) * 2 >= ((int64_t)1 << 31))
             return fail(HS_ERR_UNSUPPORTED, "hs_linear_wgrad_ld: a token slice exceeds the 2 GiB buffer-offset range");
     }
-    if (dtype == HS_BF16 && n_out % 8 && !g.dma) return fail(HS_ERR_UNSUPPORTED, "n_out must be a multiple of 8 for slices beyond 2 GiB");
-    if (dtype == HS_F32 && !g.dma) return fail(HS_ERR_UNSUPPORTED, "fp32: a token slice exceeds the 2 GiB buffer-offset range");
     const int64_t n = (int64_t)n_out * k_in, rec = n + n_out;
     float* part_w = workspace;
     float* part_b = dbias ? workspace + n : nullptr;  // bias partials live behind each slice's weight partial

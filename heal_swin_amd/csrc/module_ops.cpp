@@ -40,11 +40,29 @@ int hs_window_attn_module_bwd_chain(const void* dout, const void* x, const void*
     HS_CHECK_ARG((ln_gamma != nullptr) == (x && xn && mean && rstd && dln_gamma && dln_beta),
                  "hs_window_attn_module_bwd_chain: with a LayerNorm in front pass x, xn, mean, rstd, dln_gamma, dln_beta; without it none of them");
     HS_CHECK_ARG((bias == nullptr) == (dbias == nullptr), "hs_window_attn_module_bwd_chain: bias and dbias go together");
+    // qkv's input: LayerNorm(x) (v1 placement) or x itself
+    HS_CHECK_ARG(ln_gamma || x, "hs_window_attn_module_bwd_chain: x (the qkv Linear's input) is needed for its weight gradient");
+    // The chained kernels take turns in ONE workspace region (its size is a max over them, not a sum), and a deferred sum
+    // (HS_ACC_DEFER) must find its partial records untouched at the flush: overwrite (0) or add (1), nothing else.
+    HS_CHECK_ARG(accumulate == 0 || accumulate == 1,
+                 "hs_window_attn_module_bwd_chain: accumulate must be 0 (overwrite) or 1 (add); HS_ACC_DEFER is not taken here: the chained "
+                 "kernels share one workspace");
     // what the chained entry points would refuse is refused here, before the first of them has launched anything
-    HS_CHECK_ALIGNED("hs_window_attn_module_bwd_chain", 16, dout, x, xn, qkv, attn_out, qkv_w_t, proj_w_t, ln_gamma, dx, dqkv_w, dqkv_b, dproj_w,
-                     dproj_b, dln_gamma, dln_beta, workspace);
     if (!hs_window_attn_module_supported(channels, num_heads, window_size, dtype))
         return fail(HS_ERR_UNSUPPORTED, "hs_window_attn_module_bwd_chain: bf16, window 64, head_dim 32 and C = 96 or 128 only");
+    {
+        const char* who = "hs_window_attn_module_bwd_chain";
+        if (int st = window_attn_check_shape(who, batch, n_tokens, channels, num_heads, window_size, roll, dtype)) return st;
+        const int64_t m = (int64_t)batch * n_tokens;
+        const int c = channels;
+        if (int st = linear_wgrad_check_shape(who, m, c, c, dtype)) return st;                   // proj
+        if (int st = gemm_nt_check_shape(who, c, c, c, 0, 0, 0, m, c)) return st;
+        if (int st = linear_wgrad_check_shape(who, m, 3 * c, c, dtype)) return st;               // qkv
+        if (int st = gemm_nt_check_shape(who, 3 * c, 3 * c, 3 * c, 0, 0, 0, m, c)) return st;
+        if (int st = layernorm_check_shape(who, m, c, dtype)) return st;                         // norm1
+    }
+    HS_CHECK_ALIGNED("hs_window_attn_module_bwd_chain", 16, dout, x, xn, qkv, attn_out, qkv_w_t, proj_w_t, ln_gamma, dx, dqkv_w, dqkv_b, dproj_w,
+                     dproj_b, dln_gamma, dln_beta, workspace);
     const int C = channels;
     const int64_t rows = (int64_t)batch * n_tokens;
     // activation scratch in front of the kernels' workspace
@@ -64,7 +82,6 @@ int hs_window_attn_module_bwd_chain(const void* dout, const void* x, const void*
         return st;
     // ---- qkv (:136); its input is LayerNorm(x) (v1 placement) or x itself
     const void* qkv_in = v1 ? xn : x;
-    if (!v1 && !x) return fail(HS_ERR_INVALID_ARG, "hs_window_attn_module_bwd_chain: x (the qkv Linear's input) is needed for its weight gradient");
     if (int st = hs_linear_wgrad(dqkv, qkv_in, dqkv_w, dqkv_b, ws, rows, 3 * C, C, accumulate, dtype, stream)) return st;
     if (!v1)  // dx = dqkv W_q: the caller adds the block's own residual path (v2 placement: x + norm(branch))
         return hs_gemm_nt(dqkv, 3 * C, qkv_w_t, 3 * C, 3 * C, nullptr, 0, nullptr, 0, 0, nullptr, dx, nullptr, rows, C, HS_EPI_BIAS, 0.f, 0, dtype,

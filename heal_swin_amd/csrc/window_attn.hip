@@ -2,25 +2,31 @@
 // between the MFMA paths (Ws = 64, head_dim = 32; bf16 and fp32) and the fp32-VALU path (everything else).
 #include "window_attn.h"
 
+int hs::window_attn_check_shape(const char* who, int batch, int64_t n_tokens, int channels, int num_heads, int window_size, int64_t roll,
+                                int dtype) {
+    HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "%s: dtype must be HS_F32 or HS_BF16", who);
+    HS_CHECK_ARG(batch > 0 && n_tokens > 0 && channels > 0 && num_heads > 0, "%s: non-positive size", who);
+    HS_CHECK_ARG(n_tokens < (1ll << 31), "%s: n_tokens must fit int32 (gather table is int32)", who);
+    HS_CHECK_ARG((int64_t)batch * n_tokens < (1ll << 31), "%s: batch * n_tokens must fit int32 (token rows are carried as 32-bit indices)", who);
+    HS_CHECK_ARG(channels % num_heads == 0, "%s: channels %d not divisible by num_heads %d", who, channels, num_heads);
+    // hp_windowing.py:16 asserts a power of two.  Square nested blocks (4^k) are only needed by the relative-position index
+    // and the grid shift, which are validated where those tables are built; the kernels take any power of two
+    // (e.g. a last stage clamped to 8 * 4^k tokens with 8 base pixels, swin_hp_transformer.py:243-246)
+    HS_CHECK_ARG((window_size & (window_size - 1)) == 0, "%s: window_size must be a power of two, got %d", who, window_size);
+    HS_CHECK_ARG(window_size <= 256, "%s: window_size %d > 256 is not supported", who, window_size);
+    HS_CHECK_ARG(n_tokens % window_size == 0, "%s: n_tokens %lld not divisible by window_size %d", who, (long long)n_tokens, window_size);
+    HS_CHECK_ARG(window_size >= 4, "%s: window_size must be at least 4", who);
+    HS_CHECK_ARG(roll >= 0 && roll < n_tokens, "%s: roll must be in [0, n_tokens)", who);
+    return HS_OK;
+}
+
 namespace {
 
 int fill_params(hs::AttnParams& p, const void* qkv, void* out, float* lse, const float* bias, const float* head_scale,
                 const int32_t* idx, int64_t roll, const uint8_t* labels, int batch, int64_t n_tokens, int channels,
                 int num_heads, int window_size, unsigned flags, float attn_drop, uint64_t seed, int dtype) {
     HS_CHECK_ARG(qkv && out && head_scale, "qkv, out and head_scale must not be null");
-    HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
-    HS_CHECK_ARG(batch > 0 && n_tokens > 0 && channels > 0 && num_heads > 0, "non-positive size");
-    HS_CHECK_ARG(n_tokens < (1ll << 31), "n_tokens must fit int32 (gather table is int32)");
-    HS_CHECK_ARG((int64_t)batch * n_tokens < (1ll << 31), "batch * n_tokens must fit int32 (token rows are carried as 32-bit indices)");
-    HS_CHECK_ARG(channels % num_heads == 0, "channels %d not divisible by num_heads %d", channels, num_heads);
-    // hp_windowing.py:16 asserts a power of two.  Square nested blocks (4^k) are only needed by the relative-position index
-    // and the grid shift, which are validated where those tables are built; the kernels take any power of two
-    // (e.g. a last stage clamped to 8 * 4^k tokens with 8 base pixels, swin_hp_transformer.py:243-246)
-    HS_CHECK_ARG((window_size & (window_size - 1)) == 0, "window_size must be a power of two, got %d", window_size);
-    HS_CHECK_ARG(window_size <= 256, "window_size %d > 256 is not supported", window_size);
-    HS_CHECK_ARG(n_tokens % window_size == 0, "n_tokens %lld not divisible by window_size %d", (long long)n_tokens, window_size);
-    HS_CHECK_ARG(window_size >= 4, "window_size must be at least 4");
-    HS_CHECK_ARG(roll >= 0 && roll < n_tokens, "roll must be in [0, n_tokens)");
+    if (int st = hs::window_attn_check_shape("hs_window_attn", batch, n_tokens, channels, num_heads, window_size, roll, dtype)) return st;
     HS_CHECK_ARG(attn_drop >= 0.f && attn_drop <= 1.f, "attn_drop must be in [0, 1]");
     p = hs::AttnParams{};
     p.drop_p = attn_drop;

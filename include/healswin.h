@@ -531,9 +531,17 @@ int hs_window_attn_module_fwd_train(const void* x, void* out, void* xn_out, floa
  *   qkv_w_t [dev] bf16 [C, 3C], proj_w_t [dev] bf16 [C, C]: the TRANSPOSED weight copies (input-gradient products)
  *   ln_gamma NULL (v2 placement): x is the qkv Linear's input, xn / mean / rstd / dln_* are NULL, dx = dqkv W_q only
  *   dx [dev] bf16 [batch, n_tokens, C]; dqkv_w f32 [3C, C], dqkv_b f32 [3C] or NULL, dproj_w f32 [C, C], dproj_b f32 [C] or NULL,
- *   dln_gamma / dln_beta f32 [C], dbias f32 [nH, Ws, Ws] (NULL iff bias is), dhead_scale f32 [nH]: overwritten, or added to when
- *   accumulate != 0;  workspace [dev] f32 [hs_window_attn_module_bwd_chain_workspace(...)]
- *   flags: HS_ATTN_COSINE, HS_ATTN_RESIDUAL as in the forward call. */
+ *   dln_gamma / dln_beta f32 [C], dbias f32 [nH, Ws, Ws] (NULL iff bias is), dhead_scale f32 [nH]: overwritten
+ *   (accumulate == 0: every element is written, the buffers may hold anything) or added to (accumulate == 1: the callers' .grad
+ *   buffers; micro-batches may reuse one workspace, the calls are ordered by the stream).  dx is written either way.
+ *   accumulate takes 0 and 1 ONLY: the chained kernels take turns in one workspace region, so a sum deferred with HS_ACC_DEFER would
+ *   find its partial records overwritten at the flush -- any other value returns HS_ERR_INVALID_ARG.
+ *   workspace [dev] f32 [hs_window_attn_module_bwd_chain_workspace(...)]
+ *   flags: HS_ATTN_COSINE, HS_ATTN_RESIDUAL as in the forward call.
+ * Shapes: those of hs_window_attn_module_supported (bf16, window 64, head_dim 32, C = 96 or 128), n_tokens a positive multiple of 64,
+ *   roll in [0, n_tokens), batch * n_tokens < 2^31.  REFUSED MEANS UNTOUCHED: every argument, alignment and shape condition of every
+ *   chained kernel is checked before the first launch; a call that returns HS_ERR_INVALID_ARG / _UNSUPPORTED / _MISALIGNED has
+ *   launched nothing, written no output and queued nothing for hs_reduce_flush. */
 int64_t hs_window_attn_module_bwd_chain_workspace(int batch, int64_t n_tokens, int channels, int num_heads, int window_size);
 int hs_window_attn_module_bwd_chain(const void* dout, const void* x, const void* xn, const float* mean, const float* rstd, const void* qkv,
                               const void* attn_out, const float* lse, const void* qkv_w_t, const void* proj_w_t, const float* ln_gamma,
@@ -883,15 +891,27 @@ int hs_ln_head_depth_bwd(const void* y, const float* mean, const float* rstd, co
  *   x [dev] bf16[rows, 4 dim] = the stage output [B, N, dim] viewed as [B N/4, 4 dim]; gamma, beta [dev] f32[4 dim];
  *   w [dev] bf16[dim_out, 4 dim] (nn.Linear layout; the reference has dim_out = 2 dim); normed [dev] bf16[rows, 4 dim],
  *   mean, rstd [dev] f32[rows]: saved for the backward; out [dev] bf16[rows, dim_out].
+ *   Shapes (both directions): dim even, dim_out a multiple of 8, 4 dim <= 4096.
  * hs_patch_merge_bwd   its autograd: dx [dev] bf16[rows, 4 dim]; dw f32[dim_out, 4 dim], dgamma, dbeta f32[4 dim] overwritten
- *   (accumulate == 0) or added to (the callers' .grad buffers); w_t [dev] bf16[4 dim, dim_out] = the transposed weight;
- *   dnormed [dev] bf16[rows, 4 dim] scratch; workspace [dev] f32[hs_patch_merge_bwd_workspace(...)].
+ *   (accumulate == 0) or added to (accumulate == 1: the callers' .grad buffers); w_t [dev] bf16[4 dim, dim_out] = the transposed
+ *   weight; dnormed [dev] bf16[rows, 4 dim] scratch; workspace [dev] f32[hs_patch_merge_bwd_workspace(...)].
  * hs_patch_expand_fwd  replaces PatchExpand.forward (:418-430; children = 4, dim_exp = 2 dim) and FinalPatchExpand_X4.forward
  *   (:441-452; children = patch_size, dim_exp = patch_size dim):  out = LN_{dim_exp / children}( view(x W^T) )
  *   x [dev] bf16[rows, dim]; w [dev] bf16[dim_exp, dim]; gamma, beta f32[dim_exp / children]; expanded [dev] bf16[rows, dim_exp],
  *   mean, rstd [dev] f32[rows children]: saved; out [dev] bf16[rows children, dim_exp / children].
+ *   Shapes (both directions): dim and dim_exp multiples of 8, children dividing dim_exp; the LayerNorm width dim_exp / children at
+ *   most 4096 where it is a multiple of 8, at most 1024 otherwise.
  * hs_patch_expand_bwd  its autograd: w_t [dev] bf16[dim, dim_exp]; dexpanded [dev] bf16[rows, dim_exp] scratch; dx [dev]
- *   bf16[rows, dim]; dw f32[dim_exp, dim]; dgamma, dbeta f32[dim_exp / children]; workspace as sized by the _workspace call.
+ *   bf16[rows, dim]; dw f32[dim_exp, dim]; dgamma, dbeta f32[dim_exp / children]: overwritten or added to as for the merge;
+ *   workspace as sized by the _workspace call.
+ * accumulate (both backward operators) takes 0 and 1 ONLY.  With 0 every element of dw / dgamma / dbeta is written (the buffers may
+ *   hold anything); with 1 the gradient is added once, and micro-batches may reuse one workspace (the calls are ordered by the
+ *   stream).  dx is written either way.  HS_ACC_DEFER is not taken: the chained kernels take turns in one workspace (its size is the
+ *   largest of theirs), so a deferred sum would find its partial records overwritten at the flush -- any other value returns
+ *   HS_ERR_INVALID_ARG.
+ * REFUSED MEANS UNTOUCHED: a forward and its backward accept the same shapes, and every argument, alignment and shape condition of
+ *   every chained kernel is checked before the first launch; a call that returns HS_ERR_INVALID_ARG / _UNSUPPORTED / _MISALIGNED
+ *   has launched nothing, written no output and queued nothing for hs_reduce_flush.
  * ---------------------------------------------------------------------------------------------- */
 int hs_patch_merge_fwd(const void* x, const float* gamma, const float* beta, const void* w, void* normed, float* mean, float* rstd,
                        void* out, int64_t rows, int dim, int dim_out, int dtype, void* stream);

@@ -95,6 +95,62 @@ def test_error_conventions(L):
     assert st != 0 and L.lib.hs_last_error()
 
 
+def _scratch(L, nbytes=4 << 20):
+    """(keep-alive, address) of 4 MiB every pointer of a refused call may name: on the device where there is one, else on the host
+    (16-byte aligned either way).  A refusal reads none of it."""
+    if L.device_count() > 0:
+        import torch
+        t = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        return t, t.data_ptr()
+    buf = ctypes.create_string_buffer(nbytes + 16)
+    return buf, (ctypes.addressof(buf) + 15) & ~15
+
+
+def _patch_calls(L, p, shape, kind, accumulate=0):
+    """(forward status, backward status) of a patch operator with every pointer at `p`"""
+    P = ctypes.c_void_p(p)
+    if kind == "merge":
+        return (L.lib.hs_patch_merge_fwd(*[P] * 8, *shape, L.HS_BF16, None), L.lib.hs_patch_merge_bwd(*[P] * 13, accumulate, *shape, L.HS_BF16, None))
+    return (L.lib.hs_patch_expand_fwd(*[P] * 8, *shape, L.HS_BF16, None), L.lib.hs_patch_expand_bwd(*[P] * 13, accumulate, *shape, L.HS_BF16, None))
+
+
+def _chain_call(L, p, accumulate=0, n_tokens=128, roll=0, C=96):
+    P = ctypes.c_void_p(p)
+    return L.lib.hs_window_attn_module_bwd_chain(*[P] * 14, roll, *[P] * 11, accumulate, 1, n_tokens, C, C // 32, 64, L.HS_ATTN_RESIDUAL, L.HS_BF16, None)
+
+
+def test_operator_backwards_refuse_a_deferring_accumulate(L):
+    """hs_patch_merge_bwd, hs_patch_expand_bwd and hs_window_attn_module_bwd_chain chain kernels that share one workspace, so they
+    take accumulate = 0 / 1 only: HS_ACC_DEFER (2, 3) and anything else is HS_ERR_INVALID_ARG, decided on the host."""
+    keep, p = _scratch(L)
+    for accumulate in (2, 3, -1, 4):
+        for st in (_patch_calls(L, p, (64, 32, 64), "merge", accumulate)[1], _patch_calls(L, p, (64, 64, 128, 4), "expand", accumulate)[1],
+                   _chain_call(L, p, accumulate)):
+            msg = L.lib.hs_last_error().decode()
+            assert st == 1 and "accumulate must be 0" in msg and "HS_ACC_DEFER" in msg, (accumulate, st, msg)
+    assert L.lib.hs_reduce_pending(None) == 0
+    del keep
+
+
+def test_operator_forward_and_backward_refuse_the_same_shapes(L):
+    """What one chained kernel would refuse is refused by both directions, with one status, before the first launch."""
+    keep, p = _scratch(L)
+    for kind, shape in (("merge", (16, 6, 12)),        # backward hs_gemm_nt: k = dim_out = 12
+                        ("merge", (16, 8, 20)),
+                        ("merge", (16, 7, 16)),        # odd dim (the reference's 4-sibling view needs none, the 16-byte rows do)
+                        ("merge", (4, 1026, 16)),      # LayerNorm over 4104 > 4096 columns
+                        ("expand", (16, 8, 12, 4)),    # backward hs_gemm_nt: k = dim_exp = 12
+                        ("expand", (16, 12, 24, 4)),   # forward hs_gemm_nt: k = dim = 12
+                        ("expand", (16, 8, 24, 5)),    # children does not divide dim_exp
+                        ("expand", (4, 8, 8240, 8))):  # LayerNorm over 1030 columns: no multiple of 8 and > 1024
+        for accumulate in (0, 1):
+            st_f, st_b = _patch_calls(L, p, shape, kind, accumulate)
+            assert st_f == st_b and st_f in (1, 2), (kind, shape, st_f, st_b, L.lib.hs_last_error())
+    for kw in (dict(n_tokens=96), dict(roll=128), dict(roll=-1), dict(n_tokens=0), dict(C=64)):
+        assert _chain_call(L, p, **kw) in (1, 2), kw
+    del keep
+
+
 def test_model_mirrors_reference_surface(L):
     import torch
     from heal_swin_amd.data_spec import DataSpec
