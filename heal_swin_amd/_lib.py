@@ -91,6 +91,9 @@ _SIGNATURES = {
     "hs_ln_head_ce_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr],
     "hs_expand_ln_head_depth_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_float, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
                                     c_int, c_int, c_int, c_ptr],
+    "hs_expand_ln_head_depth_step_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_float, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                         c_int, c_int, c_float, c_float, c_int, ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
+                                         c_i64, c_int, c_int, c_int, c_ptr],
     "hs_ln_head_depth_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_float, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int,
                              c_int, c_ptr],
     "hs_ln_head_fwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr],

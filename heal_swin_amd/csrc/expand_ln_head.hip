@@ -23,6 +23,13 @@
 #include "hs_device.h"
 #include "hs_depth_loss.h"
 
+// the target transform and the metric rules of TailDepthStep form their values unfused (their headers say why); everything else in
+// this file keeps the default contraction
+#pragma clang fp contract(off)
+#include "hs_depth_target.h"
+#include "hs_depth_metrics.h"
+#pragma clang fp contract(fast)
+
 namespace hs {
 namespace {
 
@@ -74,11 +81,31 @@ struct TailCeStep {
     unsigned long long* conf;  // [n_classes][n_classes] (target, prediction) counts, added to; or null
     unsigned long long* bad;   // [2]; [0] += rows whose label is >= n_classes (with conf)
 };
+// ... or the depth caller's whole `shared_step` (models_lightning/depth_estimation/model_lightning_depth_swin_hp.py:132-159: the loss
+// in the normalised space, unnormalize_and_retransform of prediction and target, DepthMSE / MeanSTD on them): TailDepth's loss with
+// the same arithmetic in the same order, plus the row's prediction in metres (target_op's inverse chain, hs_depth_target.h), the
+// HS_DEPTH_NSUMS float64 sums of hs_depth_metrics over (metres, target in metres, log variance) as per-lane sums that leave as one
+// record per workgroup (merged in a fixed order by depth_metrics::reduce_kernel: no float atomics), and the prediction itself.
+// A separate instantiation: the other three compile to the code they were.
+struct TailDepthStep {
+    const float* target;  // as TailDepth: the normalised target
+    float* loss_part;
+    int kind;
+    float delta;
+    int n_out;            // head channels: 1 or 2 (channel 1 = the log variance)
+    TargetOp inv;         // the inverse chain (HS_DT_INVERSE set)
+    depth_metrics::Rule rule;
+    double* partial;      // [gridDim.x][HS_DEPTH_NSUMS] or null (no metrics)
+    float* preds;         // [n_out][rows] fp32: channel 0 in metres, channel 1 the raw log variance; or null; 16-byte aligned
+    float* logvar_out;    // [rows]: channel 1 alone (read when preds is null); or null
+    int64_t rows;
+};
 constexpr int kHistBins = kKP * kKP;  // per-wave LDS histogram of TailCeStep: 16 x 16 uint32 bins = 1 KB
 
 __device__ __forceinline__ bool has_loss(const TailCe& ce) { return ce.labels != nullptr; }
 __device__ __forceinline__ bool has_loss(const TailDepth&) { return true; }
 __device__ __forceinline__ bool has_loss(const TailCeStep&) { return true; }
+__device__ __forceinline__ bool has_loss(const TailDepthStep&) { return true; }
 
 // torch.max(logits, 1)'s index over a row split between two lanes: (best, arg) is each lane's own result over its classes in
 // ascending order (argmax_step), `ob`, `oa` the partner's.  The first NaN wins, else the larger value, and on equal values the
@@ -98,6 +125,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                                                                     float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                                     int64_t tokens, Loss ce) {
     constexpr bool kDepth = std::is_same<Loss, TailDepth>::value, kStep = std::is_same<Loss, TailCeStep>::value;
+    constexpr bool kDStep = std::is_same<Loss, TailDepthStep>::value;
     constexpr int C = 32 * NB, KS = 2 * NB, NCH = C / 8;  // channels (= input width), 16-deep k-steps, 16-byte chunks per row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* wl = smem;                                  // [kP * C][kRowB], 16-byte chunk ^ (row & 15)
@@ -133,6 +161,11 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
     if constexpr (kStep) {
         for (int j = tid; j < 4 * kHistBins; j += 256) hist[j] = 0;
     }
+    double dsum[kDStep ? depth_metrics::kNSums : 1];  // TailDepthStep: the lane's metric sums (half 0 lanes add, one row each)
+    if constexpr (kDStep) {
+#pragma unroll
+        for (int k = 0; k < depth_metrics::kNSums; ++k) dsum[k] = 0.0;
+    }
     __syncthreads();
 
     const int sx = l31 & 15;
@@ -149,6 +182,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             xb[ks] = __builtin_bit_cast(bf16x8, v);
         }
         uint32_t pred4 = 0;  // TailCeStep: the class ids of the token's 4 children, child p in byte p
+        float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), lv4 = m4;  // TailDepthStep: metres and log variance of the 4 children
 #pragma unroll 1
         for (int p = 0; p < kP; ++p) {
             // ------------------------------------------------------------ the child's C channels of 32 tokens: D = Wexp_p xn^T
@@ -257,6 +291,27 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                     ce_num += depth_term(ce.kind, ce.delta, lg[0] + bk[0], lg[1] + bk[1], t);
                     ce_den += 1.f;
                 }
+            } else if constexpr (kDStep) {
+                const float t = live && half == 0 ? ce.target[orow] : INFINITY;
+                const float p0 = lg[0] + bk[0], p1 = lg[1] + bk[1];
+                if (depth_keep(t)) {  // (TailDepth's lines)
+                    ce_num += depth_term(ce.kind, ce.delta, p0, p1, t);
+                    ce_den += 1.f;
+                }
+                if (ce.partial || ce.preds) {  // (uniform) back to metres, as unnormalize_and_retransform on prediction and target
+#pragma clang fp contract(off)
+                    const float m = target_op(p0, ce.inv);
+                    if (ce.partial && live && half == 0)
+                        depth_metrics::accumulate<float, float>(dsum, ce.rule, m, target_op(t, ce.inv), [&] { return p1; });
+                    m4.x = p == 0 ? m : m4.x;  // (selects: an index would put the four values into scratch)
+                    m4.y = p == 1 ? m : m4.y;
+                    m4.z = p == 2 ? m : m4.z;
+                    m4.w = p == 3 ? m : m4.w;
+                }
+                lv4.x = p == 0 ? p1 : lv4.x;
+                lv4.y = p == 1 ? p1 : lv4.y;
+                lv4.z = p == 2 ? p1 : lv4.z;
+                lv4.w = p == 3 ? p1 : lv4.w;
             } else if (ce.labels) {  // weighted cross-entropy of the row, from the fp32 logits in registers
                 constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
                 float v[8];
@@ -325,6 +380,34 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
         }
         if constexpr (kStep) {
             if (ce.preds && live && half == 0) *(uint32_t*)(ce.preds + tok * kP) = pred4;  // one 128-byte line per wave and step
+        }
+        if constexpr (kDStep) {  // the token's 4 children as one 16-byte store per channel: 512 contiguous bytes per wave and step
+            if (live && half == 0) {
+                if (ce.preds) *(float4*)(ce.preds + tok * kP) = m4;
+                float* lv = ce.preds ? (ce.n_out > 1 ? ce.preds + ce.rows : nullptr) : ce.logvar_out;
+                if (lv) *(float4*)(lv + tok * kP) = lv4;
+            }
+        }
+    }
+    if constexpr (kDStep) {
+        if (ce.partial) {
+            // partial[blockIdx.x][k] = depth_metrics::store_partials' tree over the lanes (h = 128, 64, .., 1), all sums at once: the
+            // loop is over, so the weights' LDS holds the [HS_DEPTH_NSUMS][256] lane sums (58 KB of the >= 80 KB)
+            constexpr int NS = depth_metrics::kNSums;
+            static_assert(NS * 256 * sizeof(double) <= kP * 64 * kRowB + 4 * 32 * kPatchRow, "lane sums must fit the LDS at C = 64");
+            double* red = (double*)smem;
+            __syncthreads();  // (every wave has left the weights and its patch)
+#pragma unroll
+            for (int k = 0; k < NS; ++k) red[k * 256 + tid] = dsum[k];
+            __syncthreads();
+            for (int h = 128; h > 0; h >>= 1) {
+                for (int q = tid; q < NS * h; q += 256) {
+                    const int k = q / h, j = q - k * h;
+                    red[k * 256 + j] += red[k * 256 + j + h];
+                }
+                __syncthreads();
+            }
+            if (tid < NS) ce.partial[(int64_t)blockIdx.x * NS + tid] = red[tid * 256];
         }
     }
     if constexpr (kStep) {
@@ -438,6 +521,35 @@ int hs_expand_ln_head_ce_step_fwd(const void* xn, const void* xn_lo, const void*
                                  hs::TailCeStep{labels, class_weights, loss_partials, n_classes, preds, (unsigned long long*)confmat,
                                                 (unsigned long long*)bad},
                                  "hs_expand_ln_head_ce_step_fwd");
+}
+
+int hs_expand_ln_head_depth_step_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec,
+                                     const float* target, int kind, float huber_delta, int n_out, void* y, float* logits, float* mean,
+                                     float* rstd, float* loss_partials, int flags, int transform, float shift, float scale, int use_logvar,
+                                     double total_mean, const float* ranges, int n_ranges, double* metric_partials, double* metric_state,
+                                     float* preds, float* logvar_out, int64_t tokens, int width, int children, int dtype, void* stream) {
+    const char* who = "hs_expand_ln_head_depth_step_fwd";
+    HS_CHECK_ARG(target && loss_partials, "%s: null pointer", who);
+    HS_CHECK_ARG(hs::depth_head_ok(kind, huber_delta, n_out), "%s: kind %d with %d head channels (1 or 2; Huber 1, log variance 2; "
+                 "huber delta > 0)", who, kind, n_out);
+    HS_CHECK_ARG(transform == HS_DT_NONE || transform == HS_DT_LOG || transform == HS_DT_INV, "%s: transform %d", who, transform);
+    HS_CHECK_ARG((flags & ~(HS_DT_AFFINE | HS_DT_INVERSE)) == 0, "%s: flags %d (HS_DT_AFFINE or 0: the inverse chain is applied)", who, flags);
+    HS_CHECK_ARG((metric_partials == nullptr) == (metric_state == nullptr), "%s: metric_partials and metric_state go together", who);
+    HS_CHECK_ARG(n_out == 2 || !(logvar_out || (use_logvar && metric_state)), "%s: the log variance needs a two-channel head", who);
+    hs::TailDepthStep st{target, loss_partials, kind, huber_delta, n_out, hs::TargetOp{flags | HS_DT_INVERSE, transform, shift, scale}, {},
+                         metric_partials, preds, logvar_out, tokens * hs::kP};
+    if (int e = hs::depth_metrics::fill_rule(st.rule, use_logvar, total_mean, ranges, n_ranges)) return e;
+    HS_CHECK_ALIGNED(who, 16, preds, logvar_out);  // the 4 children of a token leave as one 16-byte store
+    HS_CHECK_ALIGNED(who, 8, metric_partials, metric_state);
+    HS_CHECK_ALIGNED(who, 4, target, loss_partials);
+    if (int e = launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream, st, who))
+        return e;
+    if (metric_state) {  // the ordered merge of hs_depth_metrics: state[k] += sum over workgroups of partial[blk][k]
+        hipLaunchKernelGGL(hs::depth_metrics::reduce_kernel, dim3(1), dim3(hs::depth_metrics::kThreads), 0, (hipStream_t)stream,
+                           metric_partials, (int)hs_expand_ln_head_blocks(tokens), metric_state);
+        HS_LAUNCH_CHECK("expand_ln_head_depth_step_reduce");
+    }
+    return HS_OK;
 }
 
 int hs_expand_ln_head_depth_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const float* target,

@@ -244,6 +244,12 @@ class DepthTargetTransform:
                                   self._transform, shift, scale, stream_ptr(x.device)), "hs_depth_target")
         return out
 
+    def inverse_op(self):
+        """(flags, transform, shift, scale) of unnormalize_and_retransform as hs_depth_target takes them: what a kernel that applies
+        the chain itself (the decoder tail's depth step, csrc/hs_depth_target.h) is given."""
+        shift, scale = self._affine if self._affine is not None else (0.0, 1.0)
+        return HS_DT_INVERSE | (HS_DT_AFFINE if self._affine is not None else 0), self._transform, shift, scale
+
     def prepare(self, depth, out=None):
         flags = (HS_DT_ZERO_BKG if self.zero_is_background else 0) | (HS_DT_1000_BKG if self.mask_background else 0)
         return self._run(depth, out, flags)

@@ -383,6 +383,13 @@ class DepthMetrics:
             self.median[0] += stds.median(1).values.double().sum()
             self.median[1] += b
 
+    def add_median(self, log_var):
+        """MeanSTDMedian's part of update() alone, for a caller whose kernel has already added the sums to `state` (the decoder
+        tail's depth step): log_var fp32 [B, n], one lower median of sqrt(exp(.)) per sample."""
+        stds = torch.sqrt(torch.exp(log_var.float()))
+        self.median[0] += stds.median(1).values.double().sum()
+        self.median[1] += log_var.shape[0]
+
     def all_reduce(self, group=None):
         """Sum the states of all ranks (torchmetrics' dist_reduce_fx='sum')."""
         import torch.distributed as dist

@@ -205,6 +205,27 @@ class _DepthLossFn(torch.autograd.Function):
         return dp, None, None, None
 
 
+def depth_step_from_rows(pred, target, kind, delta, transform=None, metrics=None, want_preds=True):
+    """The depth caller's shared_step composed from WRITTEN head outputs (where the one-launch tail does not apply; the route
+    models' forward_depth_step is tested against): pred [B, C, Npix] fp32 / bf16 (any strides), target fp32 [B, Npix] in the
+    normalised space, kind / delta as depth_loss_spec gives them -> (loss by `hs_depth_loss_*`, preds fp32 [B, C, Npix] with
+    channel 0 = transform.unnormalize_and_retransform(pred[:, 0]) or None), and metrics.update(preds,
+    transform.unnormalize_and_retransform(target)).  transform None is the identity."""
+    loss = _DepthLossFn.apply(pred, target, kind, delta)
+    if metrics is None and not want_preds:
+        return loss, None
+    with torch.no_grad():
+        preds = pred.detach().float()
+        metres = target
+        if transform is not None:
+            preds = preds.clone() if preds.data_ptr() == pred.data_ptr() else preds
+            transform.unnormalize_and_retransform(preds[:, 0], out=preds[:, 0])
+            metres = transform.unnormalize_and_retransform(target)
+        if metrics is not None:
+            metrics.update(preds, metres)
+    return loss, (preds if want_preds else None)
+
+
 def depth_loss(pred, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
     """The depth losses above (get_depth_loss's selection: `use_logvar` first, then loss 'l1' | 'l2' | 'huber'; `loss` may be a
     CommonDepthConfig-like object) by the fused HIP kernels `hs_depth_loss_*`: one pass over pred [B, C, Npix] (fp32 or bf16,

@@ -693,8 +693,9 @@ class UnetDecoder(nn.Module):
     def forward(self, x, x_downsample, ce=None, depth=None, step=None):
         """ce = (labels u8 [B, Npix], class weights or None): return the weighted cross-entropy of the logits instead of the logits
         (SwinHPTransformerSys.forward_seg_loss); depth = (target f32 [B, Npix], HS_DEPTH_* kind, huber delta): the depth loss
-        (forward_depth_loss); ce with step = (SegConfusion or None, want_preds): (loss, preds) and the counts (forward_seg_step).
-        Fused into the tail kernels where they apply."""
+        (forward_depth_loss); ce with step = (SegConfusion or None, want_preds): (loss, preds) and the counts (forward_seg_step);
+        depth with step = (DepthTargetTransform or None, DepthMetrics or None, want_preds): (loss, preds) and the metric sums
+        (forward_depth_step).  Fused into the tail kernels where they apply."""
         dbg = self.config.dev_mode
         for inx, layer_up in enumerate(self.layers_up):
             if inx > 0:
@@ -717,7 +718,10 @@ def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None, step=None):
     apply, else the standalone loss kernels on the rows.  ce with step = (evaluation.SegConfusion or None, want_preds) is the
     segmentation caller's whole shared_step (forward_seg_step): (loss, preds u8 [B, N0 * children] or None), and the confusion
     matrix of (labels, preds) added to the SegConfusion -- one launch without logits where the one-launch tail applies, with or
-    without a gradient; else composed from the rows."""
+    without a gradient; else composed from the rows.  depth with step = (depth_data.DepthTargetTransform or None,
+    depth_evaluation.DepthMetrics or None, want_preds) is the depth caller's whole shared_step (forward_depth_step): (loss, preds
+    f32 [B, f_out, N0 * children] or None: channel 0 in metres), and the metrics updated on (preds, target in metres) -- one tail
+    launch plus the merge of the metric records where ops.expand_ln_head_depth_ok, else losses.depth_step_from_rows."""
     f_out = w.shape[0]
     if (isinstance(up.norm, HSLayerNorm) and isinstance(up.expand, HSLinear) and up.expand.bias is None and
             ops.expand_ln_head_ok(x, up.dim, children, f_out)):
@@ -729,7 +733,13 @@ def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None, step=None):
         else:
             xn = norm_up(x)
         B, N0, _ = xn.shape
-        if step is not None and ce[0].dtype == torch.uint8:
+        if depth is not None and step is not None and ops.expand_ln_head_depth_ok(x, up.dim, children, f_out, depth[1], depth[2]):
+            # the depth caller's shared_step in one forward kernel: loss, metres and metric sums; the head rows are never written
+            transform, metrics, want_preds = step
+            loss, preds = ops.expand_ln_head_depth_step(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
+                                                        depth[0], depth[1], depth[2], xn_lo, transform, metrics, want_preds, batch=B)
+            return loss, (None if preds is None else preds.view(f_out, B, N0 * children).transpose(0, 1))
+        if step is not None and ce is not None and ce[0].dtype == torch.uint8:
             # the caller's shared_step in one forward kernel: loss, class ids and confusion matrix; the logits are never written
             conf, want_preds = step
             loss, preds = ops.expand_ln_head_ce_step(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
@@ -769,9 +779,27 @@ def check_step_confusion(confusion, f_out):
         raise ValueError(f"confusion counts {getattr(confusion, 'num_classes', None)} classes, the model predicts {f_out}")
 
 
+def check_depth_step_args(transform, metrics, f_out, device):
+    """forward_depth_step's `transform` and `metrics`, checked on the host before any device work."""
+    from ..depth_data import DepthTargetTransform
+    from ..depth_evaluation import DepthMetrics
+    if transform is not None and not isinstance(transform, DepthTargetTransform):
+        raise TypeError(f"transform must be a depth_data.DepthTargetTransform or None, got {type(transform).__name__}")
+    if metrics is None:
+        return
+    if not isinstance(metrics, DepthMetrics):
+        raise TypeError(f"metrics must be a depth_evaluation.DepthMetrics or None, got {type(metrics).__name__}")
+    if metrics.use_logvar and f_out < 2:
+        raise ValueError(f"metrics.use_logvar needs a two-channel head (mean, log variance), the model predicts {f_out}")
+    if metrics.state.device != torch.device(device):
+        raise ValueError(f"metrics live on {metrics.state.device}, the input on {device}")
+
+
 def _rows_or_loss(rows, ce, depth=None, step=None):
     if depth is not None:
-        from ..losses import _DepthLossFn
+        from ..losses import _DepthLossFn, depth_step_from_rows
+        if step is not None:
+            return depth_step_from_rows(rows.float().transpose(1, 2), depth[0], depth[1], depth[2], *step)
         return _DepthLossFn.apply(rows.float().transpose(1, 2), depth[0], depth[1], depth[2])
     if ce is None:
         return rows
@@ -1015,6 +1043,43 @@ class SwinHPTransformerSys(nn.Module):
                 self._prefetch_attn_params()
                 x, x_downsample = self.forward_features(x.to(dt))
                 return self.decoder(x, x_downsample, depth=(target, kind, delta))
+        finally:
+            self._clear_attn_params()
+            ops.RT.cast_cache = prev
+
+    def forward_depth_step(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, transform=None, metrics=None, return_preds=True,
+                           mask_background=False):
+        """The depth caller's `shared_step` (models_lightning/depth_estimation/model_lightning_depth_swin_hp.py:132-159) as ONE call:
+            outputs = self(x); loss in the normalised space; unnormalize_and_retransform(outputs[:, 0]), (target);
+            metrics.update(outputs, target)
+        -> (loss, preds): the loss of forward_depth_loss (bit for bit, same gradients), preds fp32 [B, f_out, Npix] with channel 0 in
+        metres and channel 1 the raw log variance (None with return_preds=False), and `metrics` (a depth_evaluation.DepthMetrics or
+        None) updated on (preds, transform.unnormalize_and_retransform(target)).  target [B, Npix] is what the dataset delivers,
+        transform.prepare(depth); transform is a depth_data.DepthTargetTransform or None (the identity); the other arguments as
+        forward_depth_loss.  Where ops.expand_ln_head_depth_ok (bf16, C in {64, 96, 128}, a head the loss kind accepts) all of it
+        is ONE decoder-tail launch (`hs_expand_ln_head_depth_step_fwd`) plus the one-workgroup merge of the metric records, with a
+        gradient and without: the head rows are never written; median_std (metrics.use_logvar) takes torch.median on the written
+        log variance (preds[:, 1], or 4 bytes per pixel of scratch).  Elsewhere the same results are composed from the head rows
+        (losses.depth_step_from_rows).  No synchronisation with the host.
+        Deviation from the reference (as forward_depth_loss): it takes the loss on transform_and_normalize(
+        unnormalize_and_retransform(outputs[:, 0])), this takes it on outputs[:, 0]; the two agree to rounding wherever the
+        prediction stays inside the transform's domain ('inv': metres >= 1e-3)."""
+        from ..losses import check_depth_channels, depth_loss_spec
+        kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
+        check_depth_channels(kind, self.data_spec.f_out)
+        check_depth_step_args(transform, metrics, self.data_spec.f_out, x.device)
+        if not x.is_cuda:
+            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+        assert target.shape == (x.shape[0], x.shape[-1]), "target [B, Npix]"
+        target = target.to(device=x.device, dtype=torch.float32).contiguous()
+        dt = self._activation_dtype(x)
+        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
+        ops.RT.last_cast_cache = ops.RT.cast_cache
+        try:
+            with torch.autocast(device_type="cuda", enabled=False):
+                self._prefetch_attn_params()
+                x, x_downsample = self.forward_features(x.to(dt))
+                return self.decoder(x, x_downsample, depth=(target, kind, delta), step=(transform, metrics, bool(return_preds)))
         finally:
             self._clear_attn_params()
             ops.RT.cast_cache = prev

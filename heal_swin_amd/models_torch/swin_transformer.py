@@ -508,6 +508,34 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
             tgt = ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
         return self._run(x, depth=(tgt, kind, delta))
 
+    def forward_depth_step(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, transform=None, metrics=None, return_preds=True,
+                           mask_background=False):
+        """The flat depth caller's `shared_step` (loss in the normalised space, unnormalize_and_retransform of prediction and target,
+        the metrics' update) as ONE call, as SwinHPTransformerSys.forward_depth_step: (loss, preds) with forward_depth_loss's loss
+        and gradients, preds fp32 [B, f_out, H, W] = self(x) with channel 0 in metres (None with return_preds=False; the pixel rows
+        laid out as an image by a HIP kernel), and `metrics` updated on (preds, target in metres) (the sums do not depend on the
+        pixel order; median_std is the median over the sample's pixels in either order).  target as forward_depth_loss takes it,
+        in the normalised space; the same stated deviation from the reference's loss."""
+        from ..losses import check_depth_channels, depth_loss_spec
+        kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
+        f_out = self.data_spec.f_out
+        check_depth_channels(kind, f_out)
+        hp.check_depth_step_args(transform, metrics, f_out, x.device)
+        if not x.is_cuda:
+            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+        H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
+        if isinstance(target, PixelRows):
+            tgt = self._pixel_rows(target, x, torch.float32, "target")
+        else:
+            batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
+            assert tuple(target.shape) == (batch, H, W), "target [B, H, W]"
+            tgt = ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
+        loss, preds = self._run(x, depth=(tgt, kind, delta), step=(transform, metrics, bool(return_preds)))
+        if preds is not None:  # [B, f_out, Npix] in the rows' pixel order (any strides) -> the image, one channel at a time
+            p = self.config.patch_size[0]
+            preds = torch.cat([ops.flat_pixel_image(preds[:, c].contiguous().unsqueeze(2), H, W, p, self.tile) for c in range(f_out)], 1)
+        return loss, preds
+
     def _pixel_rows(self, rows, x, dtype, what):
         """The tensor of a PixelRows built for this model, on x's device, one row set per sample of x."""
         t = rows.check_model(self)

@@ -289,6 +289,68 @@ def expand_ln_head_depth_ok(x, width, children, f_out, kind, delta):
     return f_out in heads and delta > 0 and expand_ln_head_ok(x, width, children, f_out)
 
 
+def _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, step=None):
+    """The forward of ExpandLnHeadDepthFn, and with step = (transform or None, DepthMetrics or None, want_preds, batch) that of
+    ExpandLnHeadDepthStepFn: the same launch arguments and saved tensors, `hs_expand_ln_head_depth_step_fwd` instead of
+    `hs_expand_ln_head_depth_fwd`; then returns (loss, preds f32 [f_out, rows] or None)."""
+    _require_gpu(xn2, wexp, gamma, beta, weight, target, xn_lo)
+    tokens, C = xn2.shape
+    xn2 = xn2.contiguous()
+    xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
+    P = wexp.shape[0] // C
+    f_out = weight.shape[0]
+    wq = _cast_param(wexp, torch.bfloat16).contiguous()
+    wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
+    need = any(ctx.needs_input_grad[:5])
+    rows = tokens * P
+    target = target.reshape(-1)
+    assert target.dtype == torch.float32 and target.numel() == rows and target.is_contiguous(), "target: contiguous fp32, one per pixel row"
+    dev = xn2.device
+    y = torch.empty((rows, C), dtype=torch.bfloat16, device=dev) if need else None
+    mean = torch.empty(rows, dtype=torch.float32, device=dev) if need else None
+    rstd = torch.empty_like(mean) if need else None
+    blocks = int(lib.hs_expand_ln_head_blocks(tokens))
+    parts = torch.empty((4 * blocks, 2), dtype=torch.float32, device=dev)
+    preds = None
+    # algorithmic traffic: xn in, target in (+ the expanded rows once in training, + the predictions); no head rows
+    if step is None:
+        with _timed("expand_ln_head_depth_fwd", dev, 2 * tokens * C + rows * (4 + (2 * C + 8 if need else 0)),
+                    2 * rows * C * C + 4 * rows * C * 32):
+            check(lib.hs_expand_ln_head_depth_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(target), kind, delta, f_out,
+                                                  ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), tokens, C, P, _lib.HS_BF16,
+                                                  stream_ptr(dev)), "hs_expand_ln_head_depth_fwd")
+    else:
+        transform, metrics, want_preds, batch = step
+        flags, tcode, shift, scale = (0, _lib.HS_DT_NONE, 0.0, 1.0) if transform is None else transform.inverse_op()
+        use_logvar = metrics is not None and metrics.use_logvar
+        preds = torch.empty((f_out, rows), dtype=torch.float32, device=dev) if want_preds else None
+        # MeanSTDMedian reads the log variance itself: channel 1 of the predictions, or 4 bytes per row of scratch
+        logvar = torch.empty(rows, dtype=torch.float32, device=dev) if use_logvar and preds is None else None
+        state = mparts = rng = None
+        n_ranges, total_mean = 0, 0.0
+        if metrics is not None:
+            state, rng, n_ranges = metrics.state, metrics._ranges, len(metrics.distance_ranges)
+            total_mean = 0.0 if metrics.total_mean is None else metrics.total_mean
+            mparts = torch.empty((blocks, state.numel()), dtype=torch.float64, device=dev)
+        written = (0 if preds is None else 4 * f_out) + (0 if logvar is None else 4)
+        with _timed("expand_ln_head_depth_step_fwd", dev, 2 * tokens * C + rows * (4 + written + (2 * C + 8 if need else 0)),
+                    2 * rows * C * C + 4 * rows * C * 32):
+            check(lib.hs_expand_ln_head_depth_step_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(target), kind, delta, f_out,
+                                                       ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), flags, tcode, shift, scale,
+                                                       int(use_logvar), total_mean, _lib.np_ptr(rng) if n_ranges else None, n_ranges,
+                                                       ptr(mparts), ptr(state), ptr(preds), ptr(logvar), tokens, C, P, _lib.HS_BF16,
+                                                       stream_ptr(dev)), "hs_expand_ln_head_depth_step_fwd")
+        if use_logvar:
+            metrics.add_median((preds[1] if preds is not None else logvar).view(batch, -1))
+    tot = parts.sum(0)
+    ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp, target, tot)
+    ctx.kind, ctx.delta = kind, delta
+    ctx.w_cast = wq if wq.dtype != wexp.dtype else None
+    ctx.cast_cache = RT.cast_cache
+    loss = tot[0] / tot[1]
+    return loss if step is None else (loss, preds)
+
+
 class ExpandLnHeadDepthFn(torch.autograd.Function):
     """The decoder tail AND the depth caller's regression loss (losses.depth_loss's kinds; reference
     training/loss_depth_regression.py) as one forward and one backward kernel (`hs_expand_ln_head_depth_fwd`,
@@ -297,34 +359,7 @@ class ExpandLnHeadDepthFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo):
-        _require_gpu(xn2, wexp, gamma, beta, weight, target, xn_lo)
-        tokens, C = xn2.shape
-        xn2 = xn2.contiguous()
-        xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
-        P = wexp.shape[0] // C
-        f_out = weight.shape[0]
-        wq = _cast_param(wexp, torch.bfloat16).contiguous()
-        wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
-        need = any(ctx.needs_input_grad[:5])
-        rows = tokens * P
-        target = target.reshape(-1)
-        assert target.dtype == torch.float32 and target.numel() == rows and target.is_contiguous(), "target: contiguous fp32, one per pixel row"
-        y = torch.empty((rows, C), dtype=torch.bfloat16, device=xn2.device) if need else None
-        mean = torch.empty(rows, dtype=torch.float32, device=xn2.device) if need else None
-        rstd = torch.empty_like(mean) if need else None
-        parts = torch.empty((4 * int(lib.hs_expand_ln_head_blocks(tokens)), 2), dtype=torch.float32, device=xn2.device)
-        # algorithmic traffic: xn in, target in (+ the expanded rows once in training); no head rows
-        with _timed("expand_ln_head_depth_fwd", xn2.device, 2 * tokens * C + rows * (4 + (2 * C + 8 if need else 0)),
-                    2 * rows * C * C + 4 * rows * C * 32):
-            check(lib.hs_expand_ln_head_depth_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(target), kind, delta, f_out,
-                                                  ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), tokens, C, P, _lib.HS_BF16,
-                                                  stream_ptr(xn2.device)), "hs_expand_ln_head_depth_fwd")
-        tot = parts.sum(0)
-        ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp, target, tot)
-        ctx.kind, ctx.delta = kind, delta
-        ctx.w_cast = wq if wq.dtype != wexp.dtype else None
-        ctx.cast_cache = RT.cast_cache
-        return tot[0] / tot[1]
+        return _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo)
 
     @staticmethod
     def backward(ctx, dloss):
@@ -344,6 +379,42 @@ def expand_ln_head_depth(xn2, wexp, gamma, beta, weight, target, kind, delta=1.0
     """Depth-regression loss (HS_DEPTH_* kind, losses.DEPTH_KINDS) of head(LayerNorm(expand(xn2 [+ xn_lo]) viewed per child))
     against an fp32 per-pixel-row target, without the head rows (ExpandLnHeadDepthFn)."""
     return ExpandLnHeadDepthFn.apply(xn2, wexp, gamma, beta, weight, target, int(kind), float(delta), xn_lo)
+
+
+class ExpandLnHeadDepthStepFn(torch.autograd.Function):
+    """The depth caller's whole `shared_step` on the decoder tail (models_lightning/depth_estimation/model_lightning_depth_swin_hp.py:
+    132-159: the loss in the normalised space, `unnormalize_and_retransform` of prediction and target, the metrics' update) as ONE
+    forward kernel plus the one-workgroup merge of the metric records (`hs_expand_ln_head_depth_step_fwd`): ExpandLnHeadDepthFn's
+    loss bit for bit, the sums of `hs_depth_metrics` on (metres, target in metres) added to a DepthMetrics' state, and the
+    prediction fp32 [f_out, rows] (channel 0 in metres, channel 1 the log variance); still no head rows.  The backward is
+    ExpandLnHeadDepthFn's.  Runs without a gradient too (nothing saved: validation).  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, step):
+        loss, preds = _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, step=step)
+        if preds is None:
+            return loss, None
+        ctx.mark_non_differentiable(preds)
+        return loss, preds
+
+    @staticmethod
+    def backward(ctx, dloss, _dpreds):
+        return ExpandLnHeadDepthFn.backward(ctx, dloss) + (None,)
+
+
+def expand_ln_head_depth_step(xn2, wexp, gamma, beta, weight, target, kind, delta=1.0, xn_lo=None, transform=None, metrics=None,
+                              want_preds=True, batch=1):
+    """(loss, preds): expand_ln_head_depth's loss (bit for bit) and gradients against the NORMALISED fp32 target, with the
+    prediction fp32 [f_out, 4 tokens] (channel 0 = transform.unnormalize_and_retransform of the head's channel 0: metres; channel 1
+    the raw log variance; None unless want_preds) and, with metrics (a depth_evaluation.DepthMetrics on the same device), its update
+    on (preds, transform.unnormalize_and_retransform(target)) -- rows split into `batch` samples for median_std -- in one launch
+    without the head rows (ExpandLnHeadDepthStepFn).  transform: a depth_data.DepthTargetTransform or None (the identity)."""
+    if metrics is not None and metrics.use_logvar and weight.shape[0] < 2:
+        raise ValueError("metrics.use_logvar needs a two-channel head (mean, log variance)")
+    if metrics is not None and metrics.state.device != xn2.device:
+        raise ValueError(f"metrics live on {metrics.state.device}, the rows on {xn2.device}")
+    return ExpandLnHeadDepthStepFn.apply(xn2, wexp, gamma, beta, weight, target, int(kind), float(delta), xn_lo,
+                                         (transform, metrics, bool(want_preds), int(batch)))
 
 
 def expand_ln_head_ce(xn2, wexp, gamma, beta, weight, labels, class_weights=None, xn_lo=None):

@@ -875,6 +875,26 @@ int hs_ln_head_ce_bwd(const void* y, const float* mean, const float* rstd, const
 int hs_expand_ln_head_depth_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const float* target,
                                 int kind, float huber_delta, int n_out, void* y, float* logits, float* mean, float* rstd, float* loss_partials,
                                 int64_t tokens, int width, int children, int dtype, void* stream);
+/* ... and WITH the depth caller's whole shared_step (models_lightning/depth_estimation/model_lightning_depth_swin_hp.py:132-159: the
+ * loss in the normalised space, unnormalize_and_retransform of prediction and target, the depth metrics on them):
+ * hs_expand_ln_head_depth_fwd's arguments, loss partials and saved tensors (bit for bit: the same arithmetic in the same order; the
+ * backward is hs_ln_head_depth_bwd), plus
+ *   flags, transform, shift, scale   hs_depth_target's INVERSE chain (flags: HS_DT_AFFINE or 0; HS_DT_INVERSE is implied), applied to
+ *           channel 0 and to the target: both back in metres, the bits hs_depth_target gives;
+ *   use_logvar, total_mean, ranges [host], n_ranges   the metric rule, as hs_depth_metrics takes it (n_ranges <= 8);
+ *   metric_partials [dev] f64[hs_expand_ln_head_blocks(tokens)][HS_DEPTH_NSUMS] scratch and metric_state [dev] f64[HS_DEPTH_NSUMS]
+ *           (both or neither): the HS_DS_* sums of hs_depth_metrics over (metres, target in metres, channel 1) ADDED into the state:
+ *           float64 per-lane sums, one record per workgroup, one ordered merge (a second, one-workgroup launch): no float
+ *           atomics, the result depends on the grid only;
+ *   preds   [dev] f32[n_out][4 tokens] or NULL: channel 0 in metres, channel 1 the raw log variance; 16-byte aligned;
+ *   logvar_out [dev] f32[4 tokens] or NULL: channel 1 alone, written when preds is NULL (MeanSTDMedian's input); 16-byte aligned.
+ * The log variance (use_logvar with a state, logvar_out) needs n_out == 2.  No head rows are needed for any of it (logits == NULL); y,
+ * mean, rstd NULL is the validation form.  No host synchronisation, no allocation. */
+int hs_expand_ln_head_depth_step_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec,
+                                     const float* target, int kind, float huber_delta, int n_out, void* y, float* logits, float* mean,
+                                     float* rstd, float* loss_partials, int flags, int transform, float shift, float scale, int use_logvar,
+                                     double total_mean, const float* ranges, int n_ranges, double* metric_partials, double* metric_state,
+                                     float* preds, float* logvar_out, int64_t tokens, int width, int children, int dtype, void* stream);
 int hs_ln_head_depth_bwd(const void* y, const float* mean, const float* rstd, const float* target, int kind, float huber_delta,
                          const float* scale, int n_out, const void* wfold, const float* bvec, const void* afold, void* dy, void* dprime,
                          float* partials, int64_t rows, int width, int dtype, void* stream);
