@@ -19,6 +19,7 @@ computation is organised differently:
 Reference line numbers in comments refer to heal_swin/models_torch/swin_hp_transformer.py.
 """
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import List, Literal, Optional
 
@@ -690,12 +691,8 @@ class UnetDecoder(nn.Module):
         self.output = nn.Conv1d(in_channels=config.embed_dim, out_channels=data_spec.f_out, kernel_size=1, bias=False)
         self.norm_up = _make_norm(config.norm_layer, config.embed_dim)
 
-    def forward(self, x, x_downsample, ce=None, depth=None, step=None):
-        """ce = (labels u8 [B, Npix], class weights or None): return the weighted cross-entropy of the logits instead of the logits
-        (SwinHPTransformerSys.forward_seg_loss); depth = (target f32 [B, Npix], HS_DEPTH_* kind, huber delta): the depth loss
-        (forward_depth_loss); ce with step = (SegConfusion or None, want_preds): (loss, preds) and the counts (forward_seg_step);
-        depth with step = (DepthTargetTransform or None, DepthMetrics or None, want_preds): (loss, preds) and the metric sums
-        (forward_depth_step).  Fused into the tail kernels where they apply."""
+    def forward(self, x, x_downsample, task=None):
+        """task: None for the logits, or the SegTask / DepthTask of decoder_tail, whose result is returned instead."""
         dbg = self.config.dev_mode
         for inx, layer_up in enumerate(self.layers_up):
             if inx > 0:
@@ -705,23 +702,90 @@ class UnetDecoder(nn.Module):
             if dbg:
                 print(f"feature shape after decoder layer {inx}: {x.size()}")
         w = self.output.weight  # 1x1 conv without bias (ref :756-761) as the [f_out, C] matrix it is (ops.LinearFn)
-        out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, ce, depth, step)
-        return out if ce is not None or depth is not None else out.float().transpose(1, 2)  # B, f_out, Npix (fp32)
+        out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, task)
+        return out if task is not None else out.float().transpose(1, 2)  # B, f_out, Npix (fp32)
 
 
-def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None, step=None):
+@dataclass
+class SegTask:
+    """decoder_tail's segmentation request: the weighted cross-entropy (class_weights f32 [f_out] or None) of the logits rows against
+    labels [B, rows] in the rows' order (forward_seg_loss); with `step` the caller's whole shared_step (forward_seg_step): (loss,
+    preds u8 [B, rows] or None), and the counts of (labels, preds) added to `confusion` (an evaluation.SegConfusion or None)."""
+
+    labels: torch.Tensor
+    class_weights: Optional[torch.Tensor] = None
+    step: bool = False
+    confusion: Optional[object] = None
+    want_preds: bool = True
+
+    def fused(self, xn2, up, w, xn_lo, B):
+        """The result in one launch on norm_up's output xn2 [B * N0, C] (+ xn_lo), or None: not uint8 labels, a loss without gradient."""
+        if self.labels.dtype != torch.uint8 or not (self.step or torch.is_grad_enabled()):
+            return None
+        args = (xn2, up.expand.weight, up.norm.weight, up.norm.bias, w, self.labels.contiguous(), self.class_weights, xn_lo)
+        if not self.step:
+            # training: expand -> LayerNorm -> head -> weighted CE in one forward kernel; the logits are never written
+            return ops.expand_ln_head_ce(*args)
+        # the caller's shared_step in one forward kernel: loss, class ids and confusion matrix; the logits are never written
+        confmat, bad = (None, None) if self.confusion is None else (self.confusion.confmat, self.confusion._bad)
+        loss, preds = ops.expand_ln_head_ce_step(*args, confmat, bad, self.want_preds)
+        return loss, (None if preds is None else preds.view(B, -1))
+
+    def from_rows(self, logits):
+        """The same result composed from the written logits (the rows seen as [B, f_out, rows] fp32) by the standalone kernels."""
+        from ..losses import seg_loss, seg_predictions
+        loss = seg_loss(logits, self.labels, self.class_weights)
+        if not self.step:
+            return loss
+        # the shared_step composed from the written rows: hs_seg_confusion reads them in place (and takes the argmax itself)
+        if self.confusion is not None:
+            self.confusion.update(logits.detach(), self.labels, check=False)
+        return loss, (seg_predictions(logits.detach()).to(torch.uint8) if self.want_preds else None)
+
+
+@dataclass
+class DepthTask:
+    """decoder_tail's depth request: the depth-regression loss (HS_DEPTH_* kind, huber delta) of the head rows against target f32
+    [B, rows] in the rows' order (forward_depth_loss); with `step` the caller's whole shared_step (forward_depth_step): (loss, preds
+    f32 [B, f_out, rows] or None: channel 0 in metres), and `metrics` (a depth_evaluation.DepthMetrics or None) updated on (preds,
+    target in metres) through `transform` (a depth_data.DepthTargetTransform or None)."""
+
+    target: torch.Tensor
+    kind: int
+    delta: float
+    step: bool = False
+    transform: Optional[object] = None
+    metrics: Optional[object] = None
+    want_preds: bool = True
+
+    def fused(self, xn2, up, w, xn_lo, B):
+        """As SegTask.fused; None: outside ops.expand_ln_head_depth_ok, a loss without gradient."""
+        f_out = w.shape[0]
+        if not ((self.step or torch.is_grad_enabled()) and
+                ops.expand_ln_head_depth_ok(xn2, up.dim, up.expand.weight.shape[0] // up.dim, f_out, self.kind, self.delta)):
+            return None
+        args = (xn2, up.expand.weight, up.norm.weight, up.norm.bias, w, self.target, self.kind, self.delta, xn_lo)
+        if not self.step:
+            # training: expand -> LayerNorm -> head -> depth loss in one forward kernel; the head rows are never written
+            return ops.expand_ln_head_depth(*args)
+        # the depth caller's shared_step in one forward kernel: loss, metres and metric sums; the head rows are never written
+        loss, preds = ops.expand_ln_head_depth_step(*args, self.transform, self.metrics, self.want_preds, batch=B)
+        return loss, (None if preds is None else preds.view(f_out, B, -1).transpose(0, 1))
+
+    def from_rows(self, pred):
+        """The same result composed from the written head rows (seen as [B, f_out, rows] fp32) by the standalone kernels."""
+        from ..losses import _DepthLossFn, depth_step_from_rows
+        if self.step:
+            return depth_step_from_rows(pred, self.target, self.kind, self.delta, self.transform, self.metrics, self.want_preds)
+        return _DepthLossFn.apply(pred, self.target, self.kind, self.delta)
+
+
+def decoder_tail(norm_up, up, w, children, x, task=None):
     """norm_up -> up (Linear C -> children * C, one LayerNorm(C) per child) -> 1x1 head w [f_out, C, ...] on the decoder output
     x [B, N0, C].  Returns the logits rows [B, N0 * children, f_out] (the children of a token consecutive; fp32, or the fallback's
-    compute dtype), or with ce = (labels u8 [B, N0 * children] in the same row order, class weights or None) the weighted
-    cross-entropy instead (SwinHPTransformerSys.forward_seg_loss), with depth = (target f32 [B, N0 * children] in the same row
-    order, HS_DEPTH_* kind, huber delta) the depth-regression loss (forward_depth_loss); fused into the tail kernels where they
-    apply, else the standalone loss kernels on the rows.  ce with step = (evaluation.SegConfusion or None, want_preds) is the
-    segmentation caller's whole shared_step (forward_seg_step): (loss, preds u8 [B, N0 * children] or None), and the confusion
-    matrix of (labels, preds) added to the SegConfusion -- one launch without logits where the one-launch tail applies, with or
-    without a gradient; else composed from the rows.  depth with step = (depth_data.DepthTargetTransform or None,
-    depth_evaluation.DepthMetrics or None, want_preds) is the depth caller's whole shared_step (forward_depth_step): (loss, preds
-    f32 [B, f_out, N0 * children] or None: channel 0 in metres), and the metrics updated on (preds, target in metres) -- one tail
-    launch plus the merge of the metric records where ops.expand_ln_head_depth_ok, else losses.depth_step_from_rows."""
+    compute dtype), or with a task (SegTask, DepthTask: labels / target [B, N0 * children] in the same row order) what the task
+    asks for instead: in one launch without the rows where the one-launch tail applies and the task can take it (task.fused), else
+    composed from the rows by the standalone kernels (task.from_rows)."""
     f_out = w.shape[0]
     if (isinstance(up.norm, HSLayerNorm) and isinstance(up.expand, HSLinear) and up.expand.bias is None and
             ops.expand_ln_head_ok(x, up.dim, children, f_out)):
@@ -733,44 +797,29 @@ def decoder_tail(norm_up, up, w, children, x, ce=None, depth=None, step=None):
         else:
             xn = norm_up(x)
         B, N0, _ = xn.shape
-        if depth is not None and step is not None and ops.expand_ln_head_depth_ok(x, up.dim, children, f_out, depth[1], depth[2]):
-            # the depth caller's shared_step in one forward kernel: loss, metres and metric sums; the head rows are never written
-            transform, metrics, want_preds = step
-            loss, preds = ops.expand_ln_head_depth_step(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
-                                                        depth[0], depth[1], depth[2], xn_lo, transform, metrics, want_preds, batch=B)
-            return loss, (None if preds is None else preds.view(f_out, B, N0 * children).transpose(0, 1))
-        if step is not None and ce is not None and ce[0].dtype == torch.uint8:
-            # the caller's shared_step in one forward kernel: loss, class ids and confusion matrix; the logits are never written
-            conf, want_preds = step
-            loss, preds = ops.expand_ln_head_ce_step(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
-                                                     ce[0].contiguous(), ce[1], xn_lo, None if conf is None else conf.confmat,
-                                                     None if conf is None else conf._bad, want_preds)
-            return loss, (None if preds is None else preds.view(B, N0 * children))
-        if ce is not None and ce[0].dtype == torch.uint8 and torch.is_grad_enabled():
-            # training: expand -> LayerNorm -> head -> weighted CE in one forward kernel; the logits are never written
-            return ops.expand_ln_head_ce(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
-                                         ce[0].contiguous(), ce[1], xn_lo)
-        if depth is not None and torch.is_grad_enabled() and ops.expand_ln_head_depth_ok(x, up.dim, children, f_out, depth[1], depth[2]):
-            # training: expand -> LayerNorm -> head -> depth loss in one forward kernel; the head rows are never written
-            return ops.expand_ln_head_depth(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w,
-                                            depth[0], depth[1], depth[2], xn_lo)
-        lg = ops.expand_ln_head(xn.reshape(B * N0, up.dim), up.expand.weight, up.norm.weight, up.norm.bias, w, xn_lo)
-        return _rows_or_loss(ops.pad_slice(lg.view(B, N0 * children, -1), f_out), ce, depth, step)
-    if isinstance(up.norm, HSLayerNorm) and ops.ln_head_ok(x, up.dim, f_out):
+        xn2 = xn.reshape(B * N0, up.dim)
+        out = None if task is None else task.fused(xn2, up, w, xn_lo, B)
+        if out is not None:
+            return out
+        lg = ops.expand_ln_head(xn2, up.expand.weight, up.norm.weight, up.norm.bias, w, xn_lo)
+        rows = ops.pad_slice(lg.view(B, N0 * children, -1), f_out)
+    elif isinstance(up.norm, HSLayerNorm) and ops.ln_head_ok(x, up.dim, f_out):
         # the tail's LayerNorm and the class head in one pass over the expanded rows (hs_ln_head_*): the normalised
         # [B, Npix, C] tensor is neither written nor kept for the backward
         x = up.expand(norm_up(x))  # B, N0, p * C: row (b, n) holds the p children of token n back to back
         B, N0, _ = x.shape
         x = ops.ln_head(x.reshape(B * N0 * children, up.dim), up.norm.weight, up.norm.bias, w)
-        return _rows_or_loss(ops.pad_slice(x.view(B, N0 * children, -1), f_out), ce, depth, step)
-    x = up(norm_up(x))  # B, Npix, C
-    if x.dtype == torch.bfloat16 and f_out % 8 and f_out > 8:
-        # 12 classes: rows padded to 16 so that the input gradient (K = 12 -> 16) runs in hs_gemm_nt: 0.33 ms instead of the
-        # library's 0.85 ms; the caller sees the [.., :f_out] view (the loss kernels read logits through their strides)
-        x = ops.pad_slice(ops.linear(x, F.pad(w.reshape(f_out, -1), (0, 0, 0, (-f_out) % 8))), f_out)
+        rows = ops.pad_slice(x.view(B, N0 * children, -1), f_out)
     else:
-        x = ops.linear(x, w)
-    return _rows_or_loss(x, ce, depth, step)  # logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
+        x = up(norm_up(x))  # B, Npix, C
+        if x.dtype == torch.bfloat16 and f_out % 8 and f_out > 8:
+            # 12 classes: rows padded to 16 so that the input gradient (K = 12 -> 16) runs in hs_gemm_nt: 0.33 ms instead of the
+            # library's 0.85 ms; the caller sees the [.., :f_out] view (the loss kernels read logits through their strides)
+            rows = ops.pad_slice(ops.linear(x, F.pad(w.reshape(f_out, -1), (0, 0, 0, (-f_out) % 8))), f_out)
+        else:
+            rows = ops.linear(x, w)
+    # logits leave the model in fp32 whatever the compute dtype (see ops.LnHeadFn)
+    return rows if task is None else task.from_rows(rows.float().transpose(1, 2))
 
 
 def check_step_confusion(confusion, f_out):
@@ -793,26 +842,6 @@ def check_depth_step_args(transform, metrics, f_out, device):
         raise ValueError(f"metrics.use_logvar needs a two-channel head (mean, log variance), the model predicts {f_out}")
     if metrics.state.device != torch.device(device):
         raise ValueError(f"metrics live on {metrics.state.device}, the input on {device}")
-
-
-def _rows_or_loss(rows, ce, depth=None, step=None):
-    if depth is not None:
-        from ..losses import _DepthLossFn, depth_step_from_rows
-        if step is not None:
-            return depth_step_from_rows(rows.float().transpose(1, 2), depth[0], depth[1], depth[2], *step)
-        return _DepthLossFn.apply(rows.float().transpose(1, 2), depth[0], depth[1], depth[2])
-    if ce is None:
-        return rows
-    from ..losses import seg_loss, seg_predictions
-    logits = rows.float().transpose(1, 2)
-    loss = seg_loss(logits, ce[0], ce[1])
-    if step is None:
-        return loss
-    # the shared_step composed from the written rows: hs_seg_confusion reads them in place (and takes the argmax itself)
-    conf, want_preds = step
-    if conf is not None:
-        conf.update(logits.detach(), ce[0], check=False)
-    return loss, (seg_predictions(logits.detach()).to(torch.uint8) if want_preds else None)
 
 
 @dataclass
@@ -952,20 +981,50 @@ class SwinHPTransformerSys(nn.Module):
                 print(f"feature shape after basic layer {k}: {x.size()}")
         return self.norm(x), x_downsample
 
-    def forward(self, x):
+    def _require_device(self, x):
         if not x.is_cuda:
-            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        dt = self._activation_dtype(x)
+            raise RuntimeError(f"{type(self).__name__} (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+
+    @contextmanager
+    def _run_scope(self, dt):
+        """What every run of the model in compute dtype dt happens inside: the bf16 parameter copies as ops.RT.cast_cache, autocast
+        off, the attention parameters of all blocks prefetched; restored and cleared on every way out."""
         prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
         ops.RT.last_cast_cache = ops.RT.cast_cache
         try:
             with torch.autocast(device_type="cuda", enabled=False):
                 self._prefetch_attn_params()
-                x, x_downsample = self.forward_features(x.to(dt))
-                return self.decoder(x, x_downsample)
+                yield
         finally:
             self._clear_attn_params()
             ops.RT.cast_cache = prev
+
+    def _run(self, x, task=None):
+        """The logits [B, f_out, Npix] of x, or what `task` (a SegTask / DepthTask in the decoder's row order) asks for instead."""
+        self._require_device(x)
+        dt = self._activation_dtype(x)
+        with self._run_scope(dt):
+            x, x_downsample = self.forward_features(x.to(dt))
+            return self.decoder(x, x_downsample) if task is None else self.decoder(x, x_downsample, task)
+
+    def _seg_labels(self, x, labels):
+        self._require_device(x)
+        if labels.dtype != torch.uint8 and self.data_spec.f_out <= 255:
+            # the kernels read one byte per pixel and ignore ids >= f_out.  A plain cast would WRAP (256 -> class 0, and
+            # CrossEntropyLoss' ignore_index -100 -> 156): out-of-range ids are mapped to 255 (ignored) before narrowing
+            labels = torch.where((labels < 0) | (labels > 254), 255, labels).to(torch.uint8)
+        return labels
+
+    def _class_weights(self, x, class_weights):
+        return None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
+
+    def _depth_target(self, x, target):
+        self._require_device(x)
+        assert target.shape == (x.shape[0], x.shape[-1]), "target [B, Npix]"
+        return target.to(device=x.device, dtype=torch.float32).contiguous()
+
+    def forward(self, x):
+        return self._run(x)
 
     def forward_seg_loss(self, x, labels, class_weights=None):
         """nn.CrossEntropyLoss(weight=class_weights)(self(x), labels.long()) -- the segmentation caller's training step
@@ -973,24 +1032,7 @@ class SwinHPTransformerSys(nn.Module):
         decoder tail's kernels: in bf16 training the [B, f_out, Npix] logits and their gradient are never written (SURVEY 8f N2;
         csrc/expand_ln_head.hip, csrc/ln_head.hip).  Where the fused tail does not apply (fp32, other widths, no gradient) this is
         exactly losses.seg_loss(self(x), labels, class_weights).  labels: [B, Npix] integer class ids."""
-        if not x.is_cuda:
-            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        if labels.dtype != torch.uint8 and self.data_spec.f_out <= 255:
-            # the kernels read one byte per pixel and ignore ids >= f_out.  A plain cast would WRAP (256 -> class 0, and
-            # CrossEntropyLoss' ignore_index -100 -> 156): out-of-range ids are mapped to 255 (ignored) before narrowing
-            labels = torch.where((labels < 0) | (labels > 254), 255, labels).to(torch.uint8)
-        w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
-        dt = self._activation_dtype(x)
-        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
-        ops.RT.last_cast_cache = ops.RT.cast_cache
-        try:
-            with torch.autocast(device_type="cuda", enabled=False):
-                self._prefetch_attn_params()
-                x, x_downsample = self.forward_features(x.to(dt))
-                return self.decoder(x, x_downsample, ce=(labels, w))
-        finally:
-            self._clear_attn_params()
-            ops.RT.cast_cache = prev
+        return self._run(x, SegTask(self._seg_labels(x, labels), self._class_weights(x, class_weights)))
 
     def forward_seg_step(self, x, labels, class_weights=None, confusion=None, return_preds=True):
         """The segmentation caller's `shared_step` (models_lightning/segmentation/model_lightning_swin_hp.py:104-111) as ONE call:
@@ -1004,22 +1046,7 @@ class SwinHPTransformerSys(nn.Module):
         composed from the logits rows.  Labels >= f_out carry no weight and are not counted; the SegConfusion reports them at its
         next metric read (no synchronisation here, as update(..., check=False))."""
         check_step_confusion(confusion, self.data_spec.f_out)
-        if not x.is_cuda:
-            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        if labels.dtype != torch.uint8 and self.data_spec.f_out <= 255:
-            labels = torch.where((labels < 0) | (labels > 254), 255, labels).to(torch.uint8)  # (as forward_seg_loss)
-        w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
-        dt = self._activation_dtype(x)
-        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
-        ops.RT.last_cast_cache = ops.RT.cast_cache
-        try:
-            with torch.autocast(device_type="cuda", enabled=False):
-                self._prefetch_attn_params()
-                x, x_downsample = self.forward_features(x.to(dt))
-                return self.decoder(x, x_downsample, ce=(labels, w), step=(confusion, bool(return_preds)))
-        finally:
-            self._clear_attn_params()
-            ops.RT.cast_cache = prev
+        return self._run(x, SegTask(self._seg_labels(x, labels), self._class_weights(x, class_weights), True, confusion, bool(return_preds)))
 
     def forward_depth_loss(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
         """get_depth_loss(cfg)(self(x), target) -- the depth caller's training step (training/loss_depth_regression.py) -- as ONE
@@ -1031,21 +1058,7 @@ class SwinHPTransformerSys(nn.Module):
         from ..losses import check_depth_channels, depth_loss_spec
         kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
         check_depth_channels(kind, self.data_spec.f_out)
-        if not x.is_cuda:
-            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        assert target.shape == (x.shape[0], x.shape[-1]), "target [B, Npix]"
-        target = target.to(device=x.device, dtype=torch.float32).contiguous()
-        dt = self._activation_dtype(x)
-        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
-        ops.RT.last_cast_cache = ops.RT.cast_cache
-        try:
-            with torch.autocast(device_type="cuda", enabled=False):
-                self._prefetch_attn_params()
-                x, x_downsample = self.forward_features(x.to(dt))
-                return self.decoder(x, x_downsample, depth=(target, kind, delta))
-        finally:
-            self._clear_attn_params()
-            ops.RT.cast_cache = prev
+        return self._run(x, DepthTask(self._depth_target(x, target), kind, delta))
 
     def forward_depth_step(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, transform=None, metrics=None, return_preds=True,
                            mask_background=False):
@@ -1068,21 +1081,7 @@ class SwinHPTransformerSys(nn.Module):
         kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
         check_depth_channels(kind, self.data_spec.f_out)
         check_depth_step_args(transform, metrics, self.data_spec.f_out, x.device)
-        if not x.is_cuda:
-            raise RuntimeError("SwinHPTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        assert target.shape == (x.shape[0], x.shape[-1]), "target [B, Npix]"
-        target = target.to(device=x.device, dtype=torch.float32).contiguous()
-        dt = self._activation_dtype(x)
-        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
-        ops.RT.last_cast_cache = ops.RT.cast_cache
-        try:
-            with torch.autocast(device_type="cuda", enabled=False):
-                self._prefetch_attn_params()
-                x, x_downsample = self.forward_features(x.to(dt))
-                return self.decoder(x, x_downsample, depth=(target, kind, delta), step=(transform, metrics, bool(return_preds)))
-        finally:
-            self._clear_attn_params()
-            ops.RT.cast_cache = prev
+        return self._run(x, DepthTask(self._depth_target(x, target), kind, delta, True, transform, metrics, bool(return_preds)))
 
     def _param_casts(self, dt):
         """bf16 copies of the Linear parameters, re-made in one multi-tensor kernel after each optimizer step (ops.ParamCastCache)."""

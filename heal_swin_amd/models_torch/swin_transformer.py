@@ -411,26 +411,18 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
             x = layer_up(x)
         return x
 
-    def _run(self, x, ce=None, depth=None, step=None):
-        if not x.is_cuda:
-            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
+    def _run(self, x, task=None):
+        self._require_device(x)
         dt = self._activation_dtype(x)
-        if isinstance(x, PatchRows):
+        if isinstance(x, PatchRows):  # (before the scope: its _param_casts counts the forward, ops.note_forward)
             x.check_model(self)
             if x.dtype != dt:
                 raise TypeError(f"the patch rows are {x.dtype}, the model computes in {dt}: make them with frames(x, dtype={dt})")
-        prev, ops.RT.cast_cache = ops.RT.cast_cache, self._param_casts(dt)
-        ops.RT.last_cast_cache = ops.RT.cast_cache
-        try:
-            with torch.autocast(device_type="cuda", enabled=False):
-                self._prefetch_attn_params()
-                x, x_downsample = self.forward_features(x, dt)
-                x = self.forward_up_features(x, x_downsample)
-                p = self.config.patch_size[0]
-                return hp.decoder_tail(self.norm_up, self.up, self.output.weight, p * p, x, ce, depth, step)
-        finally:
-            self._clear_attn_params()
-            ops.RT.cast_cache = prev
+        with self._run_scope(dt):
+            x, x_downsample = self.forward_features(x, dt)
+            x = self.forward_up_features(x, x_downsample)
+            p = self.config.patch_size[0]
+            return hp.decoder_tail(self.norm_up, self.up, self.output.weight, p * p, x, task)
 
     def forward(self, x):
         rows = self._run(x)  # B, Npix, f_out logits rows (children of a token consecutive)
@@ -450,18 +442,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         become 255, ignored), so that the loss rides on the decoder tail's kernels and, in bf16 training, the NCHW logits are never
         written (the weighted mean does not depend on the pixel order).  labels: [B, H, W] integer class ids, or the flat_data.PixelRows
         FlatFrameTransform.masks(layout="rows") made (x then usually being the PatchRows of .frames(layout="rows"))."""
-        if not x.is_cuda:
-            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        if self.data_spec.f_out > 255:
-            raise NotImplementedError("forward_seg_loss supports at most 255 classes")
-        if isinstance(labels, PixelRows):
-            lab = self._pixel_rows(labels, x, torch.uint8, "labels")
-        else:
-            if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
-                labels = labels.long()
-            lab = ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
-        w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
-        return self._run(x, ce=(lab, w))
+        return self._run(x, hp.SegTask(self._seg_labels(x, labels, "forward_seg_loss"), self._class_weights(x, class_weights)))
 
     def forward_seg_step(self, x, labels, class_weights=None, confusion=None, return_preds=True):
         """The flat segmentation caller's `shared_step` (models_lightning/segmentation/model_lightning_swin.py: argmax, weighted
@@ -470,18 +451,8 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         ids of the pixel rows laid out as an image by a HIP kernel), and the (label, pred) counts added to `confusion` (an
         evaluation.SegConfusion; the counts do not depend on the pixel order).  labels as forward_seg_loss takes them."""
         hp.check_step_confusion(confusion, self.data_spec.f_out)
-        if not x.is_cuda:
-            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        if self.data_spec.f_out > 255:
-            raise NotImplementedError("forward_seg_step supports at most 255 classes")
-        if isinstance(labels, PixelRows):
-            lab = self._pixel_rows(labels, x, torch.uint8, "labels")
-        else:
-            if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
-                labels = labels.long()
-            lab = ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
-        w = None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
-        loss, preds = self._run(x, ce=(lab, w), step=(confusion, bool(return_preds)))
+        lab = self._seg_labels(x, labels, "forward_seg_step")
+        loss, preds = self._run(x, hp.SegTask(lab, self._class_weights(x, class_weights), True, confusion, bool(return_preds)))
         if preds is not None:
             H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
             preds = ops.flat_label_image(preds.contiguous(), H, W, self.config.patch_size[0], self.tile)
@@ -497,16 +468,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         from ..losses import check_depth_channels, depth_loss_spec
         kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
         check_depth_channels(kind, self.data_spec.f_out)
-        if not x.is_cuda:
-            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        if isinstance(target, PixelRows):
-            tgt = self._pixel_rows(target, x, torch.float32, "target")
-        else:
-            H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
-            batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
-            assert tuple(target.shape) == (batch, H, W), "target [B, H, W]"
-            tgt = ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
-        return self._run(x, depth=(tgt, kind, delta))
+        return self._run(x, hp.DepthTask(self._depth_target(x, target), kind, delta))
 
     def forward_depth_step(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, transform=None, metrics=None, return_preds=True,
                            mask_background=False):
@@ -521,20 +483,33 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         f_out = self.data_spec.f_out
         check_depth_channels(kind, f_out)
         hp.check_depth_step_args(transform, metrics, f_out, x.device)
-        if not x.is_cuda:
-            raise RuntimeError("SwinTransformerSys (heal_swin_amd) runs only on an MI355X (HIP) device; there is no CPU path")
-        H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
-        if isinstance(target, PixelRows):
-            tgt = self._pixel_rows(target, x, torch.float32, "target")
-        else:
-            batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
-            assert tuple(target.shape) == (batch, H, W), "target [B, H, W]"
-            tgt = ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
-        loss, preds = self._run(x, depth=(tgt, kind, delta), step=(transform, metrics, bool(return_preds)))
+        tgt = self._depth_target(x, target)
+        loss, preds = self._run(x, hp.DepthTask(tgt, kind, delta, True, transform, metrics, bool(return_preds)))
         if preds is not None:  # [B, f_out, Npix] in the rows' pixel order (any strides) -> the image, one channel at a time
+            H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
             p = self.config.patch_size[0]
             preds = torch.cat([ops.flat_pixel_image(preds[:, c].contiguous().unsqueeze(2), H, W, p, self.tile) for c in range(f_out)], 1)
         return loss, preds
+
+    def _seg_labels(self, x, labels, caller):
+        """uint8 labels [B, H * W] in the logits rows' pixel order, on x's device (ids outside [0, 254] become 255)."""
+        self._require_device(x)
+        if self.data_spec.f_out > 255:
+            raise NotImplementedError(f"{caller} supports at most 255 classes")
+        if isinstance(labels, PixelRows):
+            return self._pixel_rows(labels, x, torch.uint8, "labels")
+        if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
+            labels = labels.long()
+        return ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
+
+    def _depth_target(self, x, target):
+        """The fp32 target [B, H * W] in the head rows' pixel order, on x's device."""
+        self._require_device(x)
+        if isinstance(target, PixelRows):
+            return self._pixel_rows(target, x, torch.float32, "target")
+        batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
+        assert tuple(target.shape) == (batch,) + tuple(self.data_spec.dim_in[:2]), "target [B, H, W]"
+        return ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
 
     def _pixel_rows(self, rows, x, dtype, what):
         """The tensor of a PixelRows built for this model, on x's device, one row set per sample of x."""

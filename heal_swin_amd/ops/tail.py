@@ -121,6 +121,38 @@ def expand_ln_head_ok(x, width, children, n_classes):
                 lib.hs_expand_ln_head_supported(int(width), int(children), int(n_classes), _lib.HS_BF16))
 
 
+def _tail_prelude(ctx, xn2, wexp, gamma, beta, weight, xn_lo):
+    """The common start of the one-launch tail forwards (ExpandLnHeadFn, _tail_ce_forward, _tail_depth_forward): the operands as
+    the kernels take them and the buffers a backward needs.  Returns (xn2, xn_lo [tokens, C] or None, wq: wexp in bf16, wfold, bvec,
+    need: whether one of the five differentiable inputs wants a gradient, y [rows, C] bf16, mean, rstd f32 [rows]: None without
+    `need`) and records on ctx what _tail_backward's input gradient reads (w_cast, cast_cache)."""
+    tokens, C = xn2.shape
+    xn2 = xn2.contiguous()
+    xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
+    wq = _cast_param(wexp, torch.bfloat16).contiguous()
+    wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
+    need = any(ctx.needs_input_grad[:5])
+    rows = tokens * (wexp.shape[0] // C)
+    y = torch.empty((rows, C), dtype=torch.bfloat16, device=xn2.device) if need else None
+    mean = torch.empty(rows, dtype=torch.float32, device=xn2.device) if need else None
+    rstd = torch.empty_like(mean) if need else None
+    ctx.w_cast = wq if wq.dtype != wexp.dtype else None
+    ctx.cast_cache = RT.cast_cache
+    return xn2, xn_lo, wq, wfold, bvec, need, y, mean, rstd
+
+
+def _tail_backward(ctx, dy, dgamma, dbeta, dw):
+    """The common end of the tail backwards: from `_ln_head_backward`'s results on the expanded rows, the gradients (dxn, dWexpand,
+    dgamma, dbeta, dWhead) of the five differentiable inputs.  ctx: saved by a forward that began with _tail_prelude (xn2 first,
+    wexp eighth)."""
+    xn2, wexp = ctx.saved_tensors[0], ctx.saved_tensors[7]
+    dy2 = dy.view(xn2.shape[0], wexp.shape[0])  # 'b (n p) c -> b n (p c)': the children of a token are consecutive rows
+    dxn = _input_grad(dy2, wexp, ctx.w_cast, None, ctx.cast_cache) if ctx.needs_input_grad[0] else None
+    ctx.w_cast = ctx.cast_cache = None
+    dwexp, _ = _param_grads(dy2, xn2, wexp, None, ctx.needs_input_grad[1], False)
+    return dxn, dwexp, dgamma, dbeta, dw
+
+
 class ExpandLnHeadFn(torch.autograd.Function):
     """FinalPatchExpand_X4 (Linear C -> 4 C, view, LayerNorm(C)) + the 1x1 head as ONE forward kernel (reference
     swin_hp_transformer.py:442-452, :785-788; csrc/expand_ln_head.hip).  xn2 [tokens, C] bf16 -> padded fp32 logits [4 tokens, 16].
@@ -130,38 +162,23 @@ class ExpandLnHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xn2, wexp, gamma, beta, weight, xn_lo=None):
         _require_gpu(xn2, wexp, gamma, beta, weight, xn_lo)
-        tokens, C = xn2.shape
-        xn2 = xn2.contiguous()
-        xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
-        P = wexp.shape[0] // C
-        wq = _cast_param(wexp, torch.bfloat16).contiguous()
-        wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
-        need = any(ctx.needs_input_grad)
+        xn2, xn_lo, wq, wfold, bvec, need, y, mean, rstd = _tail_prelude(ctx, xn2, wexp, gamma, beta, weight, xn_lo)
+        (tokens, C), P = xn2.shape, wexp.shape[0] // xn2.shape[1]
         rows = tokens * P
         logits = torch.empty((rows, LnHeadFn.KP), dtype=torch.float32, device=xn2.device)
-        y = torch.empty((rows, C), dtype=torch.bfloat16, device=xn2.device) if need else None
-        mean = torch.empty(rows, dtype=torch.float32, device=xn2.device) if need else None
-        rstd = torch.empty_like(mean) if need else None
         # algorithmic traffic: xn in, logits out (+ the expanded rows once in training); flops: expand + head (hi + lo)
         with _timed("expand_ln_head_fwd", xn2.device, 2 * tokens * C + rows * (4 * LnHeadFn.KP + (2 * C + 8 if need else 0)),
                     2 * rows * C * C + 4 * rows * C * 32):
             check(lib.hs_expand_ln_head_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(y), ptr(logits), ptr(mean), ptr(rstd),
                                             tokens, C, P, _lib.HS_BF16, stream_ptr(xn2.device)), "hs_expand_ln_head_fwd")
         ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp)
-        ctx.w_cast = wq if wq.dtype != wexp.dtype else None
-        ctx.cast_cache = RT.cast_cache
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        xn2, y, mean, rstd, gamma, beta, weight, wexp = ctx.saved_tensors
-        tokens, C = xn2.shape
-        dy, dgamma, dbeta, dw = _ln_head_backward(y, mean, rstd, gamma, beta, weight, dlogits, any(ctx.needs_input_grad[2:]))
-        dy2 = dy.view(tokens, wexp.shape[0])  # 'b (n p) c -> b n (p c)': the children of a token are consecutive rows
-        dxn = _input_grad(dy2, wexp, ctx.w_cast, None, ctx.cast_cache) if ctx.needs_input_grad[0] else None
-        ctx.w_cast = ctx.cast_cache = None
-        dwexp, _ = _param_grads(dy2, xn2, wexp, None, ctx.needs_input_grad[1], False)
-        return dxn, dwexp, dgamma, dbeta, dw, None
+        _, y, mean, rstd, gamma, beta, weight, _ = ctx.saved_tensors
+        grads = _ln_head_backward(y, mean, rstd, gamma, beta, weight, dlogits, any(ctx.needs_input_grad[2:5]))
+        return _tail_backward(ctx, *grads) + (None,)
 
 
 _CE_PERM = {}
@@ -179,35 +196,25 @@ def _fold_head_ce(gamma, beta, weight, C, device):
     return wfold[perm64], bvec[perm]  # (advanced indexing: fresh contiguous tensors)
 
 
-def _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo, step=None):
-    """The forward of ExpandLnHeadCeFn, and with step = (preds u8 [rows] or None, confmat i64 [K, K] or None, bad i64 [2] or None)
+def _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo, step=False, preds=None, confmat=None, bad=None):
+    """The forward of ExpandLnHeadCeFn, and with `step` (preds u8 [rows] or None, confmat i64 [K, K] or None, bad i64 [2] or None)
     that of ExpandLnHeadCeStepFn: the same launch arguments and saved tensors, `hs_expand_ln_head_ce_step_fwd` instead of
     `hs_expand_ln_head_ce_fwd`."""
     _require_gpu(xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo)
-    tokens, C = xn2.shape
-    xn2 = xn2.contiguous()
-    xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
-    P = wexp.shape[0] // C
-    f_out = weight.shape[0]
-    wq = _cast_param(wexp, torch.bfloat16).contiguous()
-    wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
-    need = any(ctx.needs_input_grad[:5])
+    xn2, xn_lo, wq, wfold, bvec, need, y, mean, rstd = _tail_prelude(ctx, xn2, wexp, gamma, beta, weight, xn_lo)
+    (tokens, C), P, f_out = xn2.shape, wexp.shape[0] // xn2.shape[1], weight.shape[0]
     rows = tokens * P
     labels = labels.reshape(-1)
     assert labels.dtype == torch.uint8 and labels.numel() == rows and labels.is_contiguous(), "labels: contiguous uint8, one per pixel row"
-    y = torch.empty((rows, C), dtype=torch.bfloat16, device=xn2.device) if need else None
-    mean = torch.empty(rows, dtype=torch.float32, device=xn2.device) if need else None
-    rstd = torch.empty_like(mean) if need else None
     parts = torch.empty((4 * int(lib.hs_expand_ln_head_blocks(tokens)), 2), dtype=torch.float32, device=xn2.device)
     # algorithmic traffic: xn in, labels in (+ the expanded rows once in training, + one byte per row of predictions); no logits
-    if step is None:
+    if not step:
         with _timed("expand_ln_head_ce_fwd", xn2.device, 2 * tokens * C + rows * (1 + (2 * C + 8 if need else 0)),
                     2 * rows * C * C + 4 * rows * C * 32):
             check(lib.hs_expand_ln_head_ce_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(labels), ptr(class_w), f_out,
                                                ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), tokens, C, P, _lib.HS_BF16,
                                                stream_ptr(xn2.device)), "hs_expand_ln_head_ce_fwd")
     else:
-        preds, confmat, bad = step
         with _timed("expand_ln_head_ce_step_fwd", xn2.device,
                     2 * tokens * C + rows * (1 + (preds is not None) + (2 * C + 8 if need else 0)), 2 * rows * C * C + 4 * rows * C * 32):
             check(lib.hs_expand_ln_head_ce_step_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(labels), ptr(class_w), f_out,
@@ -215,8 +222,6 @@ def _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo
                                                     tokens, C, P, _lib.HS_BF16, stream_ptr(xn2.device)), "hs_expand_ln_head_ce_step_fwd")
     tot = parts.sum(0)
     ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp, labels, class_w, tot)
-    ctx.w_cast = wq if wq.dtype != wexp.dtype else None
-    ctx.cast_cache = RT.cast_cache
     return tot[0] / tot[1]
 
 
@@ -232,16 +237,10 @@ class ExpandLnHeadCeFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        xn2, y, mean, rstd, gamma, beta, weight, wexp, labels, class_w, tot = ctx.saved_tensors
-        tokens, C = xn2.shape
+        _, y, mean, rstd, gamma, beta, weight, _, labels, class_w, tot = ctx.saved_tensors
         scale = (dloss.to(torch.float32) / tot[1]).reshape(1)
-        dy, dgamma, dbeta, dw = _ln_head_backward(y, mean, rstd, gamma, beta, weight, None, any(ctx.needs_input_grad[2:5]),
-                                                  ce=(labels, class_w, scale))
-        dy2 = dy.view(tokens, wexp.shape[0])
-        dxn = _input_grad(dy2, wexp, ctx.w_cast, None, ctx.cast_cache) if ctx.needs_input_grad[0] else None
-        ctx.w_cast = ctx.cast_cache = None
-        dwexp, _ = _param_grads(dy2, xn2, wexp, None, ctx.needs_input_grad[1], False)
-        return dxn, dwexp, dgamma, dbeta, dw, None, None, None
+        grads = _ln_head_backward(y, mean, rstd, gamma, beta, weight, None, any(ctx.needs_input_grad[2:5]), ce=(labels, class_w, scale))
+        return _tail_backward(ctx, *grads) + (None, None, None)
 
 
 class ExpandLnHeadCeStepFn(torch.autograd.Function):
@@ -260,7 +259,7 @@ class ExpandLnHeadCeStepFn(torch.autograd.Function):
             assert confmat.dtype == torch.int64 and confmat.shape == (f_out, f_out) and confmat.is_contiguous(), \
                 f"confmat: contiguous int64 [{f_out}, {f_out}]"
         preds = torch.empty(labels.numel(), dtype=torch.uint8, device=xn2.device) if want_preds else None
-        loss = _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo, step=(preds, confmat, bad))
+        loss = _tail_ce_forward(ctx, xn2, wexp, gamma, beta, weight, labels, class_w, xn_lo, True, preds, confmat, bad)
         if preds is None:
             return loss, None
         ctx.mark_non_differentiable(preds)
@@ -289,38 +288,28 @@ def expand_ln_head_depth_ok(x, width, children, f_out, kind, delta):
     return f_out in heads and delta > 0 and expand_ln_head_ok(x, width, children, f_out)
 
 
-def _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, step=None):
-    """The forward of ExpandLnHeadDepthFn, and with step = (transform or None, DepthMetrics or None, want_preds, batch) that of
+def _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, step=False, transform=None, metrics=None,
+                        want_preds=False, batch=1):
+    """The forward of ExpandLnHeadDepthFn, and with `step` (transform or None, DepthMetrics or None, want_preds, batch) that of
     ExpandLnHeadDepthStepFn: the same launch arguments and saved tensors, `hs_expand_ln_head_depth_step_fwd` instead of
     `hs_expand_ln_head_depth_fwd`; then returns (loss, preds f32 [f_out, rows] or None)."""
     _require_gpu(xn2, wexp, gamma, beta, weight, target, xn_lo)
-    tokens, C = xn2.shape
-    xn2 = xn2.contiguous()
-    xn_lo = None if xn_lo is None else xn_lo.reshape(tokens, C).contiguous()
-    P = wexp.shape[0] // C
-    f_out = weight.shape[0]
-    wq = _cast_param(wexp, torch.bfloat16).contiguous()
-    wfold, bvec = _fold_head(gamma, beta, weight, C, xn2.device)
-    need = any(ctx.needs_input_grad[:5])
+    xn2, xn_lo, wq, wfold, bvec, need, y, mean, rstd = _tail_prelude(ctx, xn2, wexp, gamma, beta, weight, xn_lo)
+    (tokens, C), P, f_out, dev = xn2.shape, wexp.shape[0] // xn2.shape[1], weight.shape[0], xn2.device
     rows = tokens * P
     target = target.reshape(-1)
     assert target.dtype == torch.float32 and target.numel() == rows and target.is_contiguous(), "target: contiguous fp32, one per pixel row"
-    dev = xn2.device
-    y = torch.empty((rows, C), dtype=torch.bfloat16, device=dev) if need else None
-    mean = torch.empty(rows, dtype=torch.float32, device=dev) if need else None
-    rstd = torch.empty_like(mean) if need else None
     blocks = int(lib.hs_expand_ln_head_blocks(tokens))
     parts = torch.empty((4 * blocks, 2), dtype=torch.float32, device=dev)
     preds = None
     # algorithmic traffic: xn in, target in (+ the expanded rows once in training, + the predictions); no head rows
-    if step is None:
+    if not step:
         with _timed("expand_ln_head_depth_fwd", dev, 2 * tokens * C + rows * (4 + (2 * C + 8 if need else 0)),
                     2 * rows * C * C + 4 * rows * C * 32):
             check(lib.hs_expand_ln_head_depth_fwd(ptr(xn2), ptr(xn_lo), ptr(wq), ptr(wfold), ptr(bvec), ptr(target), kind, delta, f_out,
                                                   ptr(y), None, ptr(mean), ptr(rstd), ptr(parts), tokens, C, P, _lib.HS_BF16,
                                                   stream_ptr(dev)), "hs_expand_ln_head_depth_fwd")
     else:
-        transform, metrics, want_preds, batch = step
         flags, tcode, shift, scale = (0, _lib.HS_DT_NONE, 0.0, 1.0) if transform is None else transform.inverse_op()
         use_logvar = metrics is not None and metrics.use_logvar
         preds = torch.empty((f_out, rows), dtype=torch.float32, device=dev) if want_preds else None
@@ -345,10 +334,8 @@ def _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta
     tot = parts.sum(0)
     ctx.save_for_backward(xn2, y, mean, rstd, gamma, beta, weight, wexp, target, tot)
     ctx.kind, ctx.delta = kind, delta
-    ctx.w_cast = wq if wq.dtype != wexp.dtype else None
-    ctx.cast_cache = RT.cast_cache
     loss = tot[0] / tot[1]
-    return loss if step is None else (loss, preds)
+    return (loss, preds) if step else loss
 
 
 class ExpandLnHeadDepthFn(torch.autograd.Function):
@@ -363,16 +350,11 @@ class ExpandLnHeadDepthFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        xn2, y, mean, rstd, gamma, beta, weight, wexp, target, tot = ctx.saved_tensors
-        tokens, C = xn2.shape
+        _, y, mean, rstd, gamma, beta, weight, _, target, tot = ctx.saved_tensors
         scale = (dloss.to(torch.float32) / tot[1]).reshape(1)
-        dy, dgamma, dbeta, dw = _ln_head_backward(y, mean, rstd, gamma, beta, weight, None, any(ctx.needs_input_grad[2:5]),
-                                                  depth=(target, ctx.kind, ctx.delta, scale))
-        dy2 = dy.view(tokens, wexp.shape[0])
-        dxn = _input_grad(dy2, wexp, ctx.w_cast, None, ctx.cast_cache) if ctx.needs_input_grad[0] else None
-        ctx.w_cast = ctx.cast_cache = None
-        dwexp, _ = _param_grads(dy2, xn2, wexp, None, ctx.needs_input_grad[1], False)
-        return dxn, dwexp, dgamma, dbeta, dw, None, None, None, None
+        grads = _ln_head_backward(y, mean, rstd, gamma, beta, weight, None, any(ctx.needs_input_grad[2:5]),
+                                  depth=(target, ctx.kind, ctx.delta, scale))
+        return _tail_backward(ctx, *grads) + (None, None, None, None)
 
 
 def expand_ln_head_depth(xn2, wexp, gamma, beta, weight, target, kind, delta=1.0, xn_lo=None):
@@ -390,8 +372,9 @@ class ExpandLnHeadDepthStepFn(torch.autograd.Function):
     ExpandLnHeadDepthFn's.  Runs without a gradient too (nothing saved: validation).  No host synchronisation."""
 
     @staticmethod
-    def forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, step):
-        loss, preds = _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, step=step)
+    def forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, transform, metrics, want_preds, batch):
+        loss, preds = _tail_depth_forward(ctx, xn2, wexp, gamma, beta, weight, target, kind, delta, xn_lo, True, transform, metrics,
+                                          want_preds, batch)
         if preds is None:
             return loss, None
         ctx.mark_non_differentiable(preds)
@@ -399,7 +382,7 @@ class ExpandLnHeadDepthStepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dpreds):
-        return ExpandLnHeadDepthFn.backward(ctx, dloss) + (None,)
+        return ExpandLnHeadDepthFn.backward(ctx, dloss) + (None, None, None, None)
 
 
 def expand_ln_head_depth_step(xn2, wexp, gamma, beta, weight, target, kind, delta=1.0, xn_lo=None, transform=None, metrics=None,
@@ -413,8 +396,8 @@ def expand_ln_head_depth_step(xn2, wexp, gamma, beta, weight, target, kind, delt
         raise ValueError("metrics.use_logvar needs a two-channel head (mean, log variance)")
     if metrics is not None and metrics.state.device != xn2.device:
         raise ValueError(f"metrics live on {metrics.state.device}, the rows on {xn2.device}")
-    return ExpandLnHeadDepthStepFn.apply(xn2, wexp, gamma, beta, weight, target, int(kind), float(delta), xn_lo,
-                                         (transform, metrics, bool(want_preds), int(batch)))
+    return ExpandLnHeadDepthStepFn.apply(xn2, wexp, gamma, beta, weight, target, int(kind), float(delta), xn_lo, transform, metrics,
+                                         bool(want_preds), int(batch))
 
 
 def expand_ln_head_ce(xn2, wexp, gamma, beta, weight, labels, class_weights=None, xn_lo=None):

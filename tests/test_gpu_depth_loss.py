@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from _golden import load
+from _lib_spy import launches, spy_on
 from tests._util import GRAD_TOL, assert_close, assert_unbiased
 
 pytestmark = pytest.mark.gpu
@@ -317,27 +318,32 @@ def test_bf16_depth_step_runs_the_fused_tail_only(which, monkeypatch):
     from heal_swin_amd import _lib
     m, x, t = (_hp_model if which == "healpix" else _flat_model)(1)
     m.compute_dtype = torch.bfloat16
-    called = []
-
-    class Spy:
-        def __getattr__(self, name):
-            fn = getattr(real, name)
-            if name.startswith(("hs_expand_ln_head", "hs_ln_head", "hs_depth_loss")):
-                def wrap(*a):
-                    called.append(name)
-                    return fn(*a)
-                return wrap
-            return fn
-
-    real = _lib.lib
     import heal_swin_amd.ops.tail as T
-    monkeypatch.setattr(T, "lib", Spy())
-    monkeypatch.setattr(_lib, "lib", Spy())
+    called = spy_on(monkeypatch, ("hs_expand_ln_head", "hs_ln_head", "hs_depth_loss"), (T, _lib))
     loss = m.forward_depth_loss(x, t, "l1")
     loss.backward()
     torch.cuda.synchronize()
     assert "hs_expand_ln_head_depth_fwd" in called and "hs_ln_head_depth_bwd" in called, called
     assert "hs_expand_ln_head_fwd" not in called and not any(c.startswith("hs_depth_loss") for c in called), called
+    # without a gradient: the rows-writing tail once, then the standalone loss kernel on the rows
+    del called[:]
+    with torch.no_grad():
+        m.forward_depth_loss(x, t, "l1")
+    torch.cuda.synchronize()
+    assert launches(called) == ["hs_depth_loss_fwd", "hs_expand_ln_head_fwd"], called
+
+
+def test_bf16_depth_step_of_three_channels_takes_the_rows_route(monkeypatch):
+    """A three-channel head is outside ops.expand_ln_head_depth_ok: a bf16 training step with forward_depth_loss writes the head
+    rows (hs_expand_ln_head_fwd) and takes the standalone loss kernels on them, forward and backward; no fused depth tail."""
+    from heal_swin_amd import _lib
+    import heal_swin_amd.ops.tail as T
+    m, x, t = _hp_model(3)
+    m.compute_dtype = torch.bfloat16
+    called = spy_on(monkeypatch, ("hs_expand_ln_head", "hs_ln_head", "hs_depth_loss"), (T, _lib))
+    m.forward_depth_loss(x, t, "l2").backward()
+    torch.cuda.synchronize()
+    assert launches(called) == ["hs_depth_loss_bwd", "hs_depth_loss_fwd", "hs_expand_ln_head_fwd", "hs_ln_head_bwd"], called
 
 
 def test_graph_replay_of_a_depth_step_equals_the_eager_step():

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from _lib_spy import spy_on
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -306,24 +308,10 @@ def test_forward_depth_step_equals_the_reference_route_bf16(which, f_out, monkey
             assert torch.equal(m.median, ref.median) and a["median_std"] == b["median_std"]
     # the bf16 step is the one-launch tail, with and without a gradient: no rows-writing forward, no standalone loss, transform or
     # metric kernel
-    called = []
-    real = _lib.lib
-
-    class Spy:
-        def __getattr__(self, name):
-            fn = getattr(real, name)
-            if name.startswith(("hs_expand_ln_head", "hs_ln_head", "hs_depth_loss", "hs_depth_target", "hs_depth_metrics")):
-                def wrap(*a):
-                    called.append(name)
-                    return fn(*a)
-                return wrap
-            return fn
-
     import heal_swin_amd.depth_data as D
     import heal_swin_amd.depth_evaluation as E
     import heal_swin_amd.ops.tail as T
-    for mod in (T, E, D, _lib):
-        monkeypatch.setattr(mod, "lib", Spy())
+    called = spy_on(monkeypatch, ("hs_expand_ln_head", "hs_ln_head", "hs_depth_loss", "hs_depth_target", "hs_depth_metrics"), (T, E, D, _lib))
     model.forward_depth_step(x, target, transform=tr, metrics=_metrics(use_logvar, True), **kw)[0].backward()
     with torch.no_grad():
         model.forward_depth_step(x, target, transform=tr, metrics=_metrics(use_logvar, True), return_preds=False, **kw)

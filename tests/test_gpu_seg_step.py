@@ -4,6 +4,8 @@ backward kernel), the class ids are torch.max's on the written logits and the co
 import pytest
 import torch
 
+from _lib_spy import launches, spy_on
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -207,29 +209,21 @@ def test_forward_seg_step_equals_the_reference_route_bf16(which, monkeypatch):
         assert torch.equal(c.iou(), ref.iou()) and torch.equal(c.accuracy(), ref.accuracy())
         assert torch.equal(c.accuracy(ignore_index=0), ref.accuracy(ignore_index=0))
     # the bf16 step is the one-launch tail, with and without a gradient: no logits-writing forward, no standalone loss / confusion kernel
-    called = []
-    real = _lib.lib
-
-    class Spy:
-        def __getattr__(self, name):
-            fn = getattr(real, name)
-            if name.startswith(("hs_expand_ln_head", "hs_ln_head", "hs_seg_")):
-                def wrap(*a):
-                    called.append(name)
-                    return fn(*a)
-                return wrap
-            return fn
-
     import heal_swin_amd.evaluation as E
     import heal_swin_amd.ops.tail as T
-    for mod in (T, E, _lib):
-        monkeypatch.setattr(mod, "lib", Spy())
+    called = spy_on(monkeypatch, ("hs_expand_ln_head", "hs_ln_head", "hs_seg_"), (T, E, _lib))
     model.forward_seg_step(x, labels, cw, confusion=SegConfusion(K))[0].backward()
     with torch.no_grad():
         model.forward_seg_step(x, labels, cw, confusion=SegConfusion(K))
     torch.cuda.synchronize()
     assert sorted(c for c in called if not c.endswith(("_supported", "_blocks", "_partials"))) == \
         ["hs_expand_ln_head_ce_step_fwd", "hs_expand_ln_head_ce_step_fwd", "hs_ln_head_ce_bwd"], called
+    # forward_seg_loss without a gradient: the rows-writing tail once, then the standalone loss kernel on the rows
+    del called[:]
+    with torch.no_grad():
+        model.forward_seg_loss(x, labels, cw)
+    torch.cuda.synchronize()
+    assert launches(called) == ["hs_expand_ln_head_fwd", "hs_seg_ce_fwd"], called
 
 
 @pytest.mark.parametrize("which", ["healpix", "flat"])
