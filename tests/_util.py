@@ -8,6 +8,8 @@ Error measures (all against the reference / oracle tensor b):
                                             judged against 1 % of the scale (relative error is meaningless at zero crossings)
 north_star tolerances: activations within 1e-3 (fp32) / 1e-2 (bf16) of the reference; asserted on scale_err.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -107,3 +109,27 @@ def assert_unbiased(a, b, what="", slope_tol=0.05, cos_min=None, min_elems=256):
     if cos_min is not None:
         assert cos >= cos_min, f"{what}: cosine with the reference {cos:.4f} < {cos_min}"
     return slope
+
+
+# ----------------------------------------------------------------------------- library state shared by the GPU tests
+@contextlib.contextmanager
+def reserved_cus(n):
+    """hs_set_reserved_cus(n) for the body; the previous value comes back on every path."""
+    from heal_swin_amd import _lib as L
+    prev = int(L.lib.hs_get_reserved_cus())
+    try:
+        L.check(L.lib.hs_set_reserved_cus(n), "hs_set_reserved_cus")
+        yield
+    finally:
+        L.lib.hs_set_reserved_cus(prev)
+
+
+def mask_of(seed, p, shape):
+    """The generator's keep mask (x 1 / (1 - p)) for a [rows, width] tensor, float64 on the device, read off the elementwise GELU
+    kernel in bf16: gelu(16) = 16.  The mask is a function of (seed, element index) only, so it is the mask of every kernel that
+    drops elements of a tensor of this shape with this seed."""
+    from heal_swin_amd import _lib as L
+    src = torch.full(shape, 16.0, device="cuda", dtype=torch.bfloat16)
+    dst = torch.empty_like(src)
+    L.check(L.lib.hs_gelu_fwd(L.ptr(src), L.ptr(dst), src.numel(), float(p), int(seed), L.HS_BF16, L.stream_ptr(src.device)), "hs_gelu_fwd")
+    return (dst.float() != 0).double() / (1.0 - p)

@@ -9,13 +9,11 @@ have at most 64 windows, i.e. ONE iteration per slot.  Here every slot walks at 
 head groups that only tensors >= 64 MB select (forward 8 heads, backward 4 heads per workgroup) are reached at the smallest
 such shape.  Every multi-iteration test asserts its own precondition (windows > 2 slots, windows % slots != 0, or the 64 MB
 line), so a change of the slot formulas cannot quietly turn it back into a one-iteration test."""
-import contextlib
-
 import pytest
 import torch
 
 import test_gpu_attn_module as TM
-from _util import GRAD_TOL, TOL, assert_close, assert_unbiased
+from _util import GRAD_TOL, TOL, assert_close, assert_unbiased, reserved_cus
 from test_gpu_kernels import _oracle_core
 
 pytestmark = pytest.mark.gpu
@@ -28,18 +26,6 @@ LARGE_LINE = 64 << 20  # pick_head_group / pick_head_group_bwd: one [B, N, C] bf
 def _L():
     from heal_swin_amd import _lib
     return _lib
-
-
-@contextlib.contextmanager
-def reserved_cus(n):
-    """hs_set_reserved_cus(n) for the body; the previous value comes back on every path."""
-    L = _L()
-    prev = int(L.lib.hs_get_reserved_cus())
-    try:
-        L.check(L.lib.hs_set_reserved_cus(n), "hs_set_reserved_cus")
-        yield
-    finally:
-        L.lib.hs_set_reserved_cus(prev)
 
 
 # ----------------------------------------------------------------------------- slot counts

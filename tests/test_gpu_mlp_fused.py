@@ -8,7 +8,7 @@ import ctypes
 import pytest
 import torch
 
-from _util import GRAD_TOL, TOL, assert_close
+from _util import GRAD_TOL, TOL, assert_close, mask_of
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -299,15 +299,6 @@ def test_fused_mlp_block_with_and_without_kept_activation(keep):
         assert_close(res[False][k], res[True][k], 3e-3, f"fused mlp keep_act on/off d{k}")
 
 
-def _mask_of(seed, p, shape):
-    """The generator's keep mask (x 1 / (1 - p)) for a [rows, width] bf16 tensor, read off the elementwise GELU kernel: gelu(16) = 16."""
-    L = _L()
-    src = torch.full(shape, 16.0, device=DEV, dtype=BF)
-    dst = torch.empty_like(src)
-    L.check(L.lib.hs_gelu_fwd(L.ptr(src), L.ptr(dst), src.numel(), float(p), int(seed), L.HS_BF16, _stream()), "hs_gelu_fwd")
-    return (dst.float() != 0).double() / (1.0 - p)
-
-
 @pytest.mark.parametrize("C", [96, 128])
 @pytest.mark.parametrize("drop_p,with_path", [(0.1, True), (0.25, False), (0.0, True)])
 def test_fused_mlp_block_stochastic_vs_oracle_and_composition(C, drop_p, with_path):
@@ -340,8 +331,8 @@ def test_fused_mlp_block_stochastic_vs_oracle_and_composition(C, drop_p, with_pa
     assert ops.fused_mlp_stochastic_ok(t["x"].view(B, per, C), True)
     out_f, dx_f, gp_f = run(True)
     out_c, dx_c, gp_c = run(False)
-    mh = _mask_of(seeds[0], drop_p, (rows, 4 * C)) if drop_p else 1.0
-    mo = _mask_of(seeds[1], drop_p, (rows, C)) if drop_p else 1.0
+    mh = mask_of(seeds[0], drop_p, (rows, 4 * C)) if drop_p else 1.0
+    mo = mask_of(seeds[1], drop_p, (rows, C)) if drop_p else 1.0
     if drop_p:
         frac = 1.0 - (mh != 0).double().mean().item()
         assert abs(frac - drop_p) < 0.01, f"hidden drop fraction {frac} vs {drop_p}"
