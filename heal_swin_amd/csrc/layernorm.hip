@@ -26,60 +26,70 @@ namespace {
 constexpr float kLnEps = 1e-5f;  // torch.nn.LayerNorm default, used by every norm in the reference
 constexpr int kBwdMaxBlocks = 2048;
 
-template <typename T, int VEC>
-struct vec_io;
+// One 16-byte chunk of the activation dtype (8 bf16 / 4 fp32) <-> its elements as fp32
+template <typename T>
+__device__ __forceinline__ void chunk_decode(const uint4& t, float* v);
 template <>
-struct vec_io<float, 4> {
-    static __device__ __forceinline__ void load(const void* p, int64_t i, float* v) {
-        const float4 t = *(const float4*)((const float*)p + i);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void store(void* p, int64_t i, const float* v) {
-        *(float4*)((float*)p + i) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    static __device__ __forceinline__ void decode(const uint4& t, float* v) {
-        v[0] = __uint_as_float(t.x); v[1] = __uint_as_float(t.y); v[2] = __uint_as_float(t.z); v[3] = __uint_as_float(t.w);
-    }
-};
+__device__ __forceinline__ void chunk_decode<float>(const uint4& t, float* v) {
+    v[0] = __uint_as_float(t.x); v[1] = __uint_as_float(t.y); v[2] = __uint_as_float(t.z); v[3] = __uint_as_float(t.w);
+}
 template <>
-struct vec_io<bf16_t, 8> {
-    static __device__ __forceinline__ void load(const void* p, int64_t i, float* v) {
-        const uint4 t = *(const uint4*)((const uint16_t*)p + i);
-        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+__device__ __forceinline__ void chunk_decode<bf16_t>(const uint4& t, float* v) {
+    const uint32_t w[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[2 * k] = __uint_as_float(w[k] << 16);
-            v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-        }
+    for (int k = 0; k < 4; ++k) {
+        v[2 * k] = __uint_as_float(w[k] << 16);
+        v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
     }
-    static __device__ __forceinline__ void store(void* p, int64_t i, const float* v) {
-        uint32_t w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
-        *(uint4*)((uint16_t*)p + i) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    static __device__ __forceinline__ void decode(const uint4& t, float* v) {
-        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[2 * k] = __uint_as_float(w[k] << 16);
-            v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-        }
-    }
-};
-// (non-temporal stores for the residual-stream sum were measured here: +1-3 % on the kernel, nothing on the step --
-// profiles/archive_r01_r04/r03_ln_store_ab.txt; the plain store stays)
-template <typename T, int VEC>
-__device__ __forceinline__ void store_stream(void* p, int64_t i, const float* v) {
-    vec_io<T, VEC>::store(p, i, v);
+}
+template <typename T>
+__device__ __forceinline__ uint4 chunk_pack(const float* v);
+template <>
+__device__ __forceinline__ uint4 chunk_pack<float>(const float* v) {
+    return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+}
+template <>
+__device__ __forceinline__ uint4 chunk_pack<bf16_t>(const float* v) {
+    return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+}
+// element k of a packed chunk
+template <typename T>
+__device__ __forceinline__ float chunk_elem(const uint4& w, int k);
+template <>
+__device__ __forceinline__ float chunk_elem<bf16_t>(const uint4& w, int k) {
+    const uint32_t d = (k >> 1) == 0 ? w.x : (k >> 1) == 1 ? w.y : (k >> 1) == 2 ? w.z : w.w;
+    return (k & 1) ? __uint_as_float(d & 0xffff0000u) : __uint_as_float(d << 16);
+}
+template <>
+__device__ __forceinline__ float chunk_elem<float>(const uint4& w, int k) {
+    return __uint_as_float(k == 0 ? w.x : k == 1 ? w.y : k == 2 ? w.z : w.w);
 }
 
+// VEC elements at element index i as fp32: a whole chunk (VEC * sizeof(T) == 16), or one element where the width has no chunks
+template <typename T, int VEC>
+struct vec_io {
+    static_assert(VEC * sizeof(T) == 16, "a vector is one 16-byte chunk");
+    static __device__ __forceinline__ void load(const void* p, int64_t i, float* v) { chunk_decode<T>(*(const uint4*)((const T*)p + i), v); }
+    static __device__ __forceinline__ void store(void* p, int64_t i, const float* v) { *(uint4*)((T*)p + i) = chunk_pack<T>(v); }
+};
 template <typename T>
 struct vec_io<T, 1> {
     static __device__ __forceinline__ void load(const void* p, int64_t i, float* v) { v[0] = io<T>::load(p, i); }
     static __device__ __forceinline__ void store(void* p, int64_t i, const float* v) { io<T>::store(p, i, v[0]); }
-    static __device__ __forceinline__ void decode(const uint4&, float*) {}
 };
+// the VEC fp32 parameters (gamma / beta) of chunk c, as float4 loads where the row has chunks
+template <int VEC>
+__device__ __forceinline__ void load_params(const float* __restrict__ p, int c, float* v) {
+    if constexpr (VEC == 1) {
+        v[0] = p[c];
+    } else {
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q) {
+            const float4 t = *(const float4*)(p + c * VEC + 4 * q);
+            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        }
+    }
+}
 
 // A wavefront normalises 64/LPR rows at a time: LPR lanes per row (a power of two >= the row's 16-byte chunk
 // count, capped at 64), lane `sub` of a row owning chunks sub, sub+LPR, ...  Narrow rows (C = 96..256 in bf16 are
@@ -96,6 +106,81 @@ __device__ __forceinline__ float row_sum(float v) {
 #pragma unroll
     for (int off = LPR / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// Row statistics of the forward from the row cached in registers (`sum`: the lane's share of the row sum): the mean, then the
+// squared deviations from it (two passes over registers, no E[x^2] - mean^2 cancellation), rstd = 1 / sqrt(var + eps).
+template <int VEC, int LPR, int ITERS>
+__device__ __forceinline__ void row_stats(const float (&v)[ITERS][VEC], float sum, bool live, int sub, int nchunk, float inv_w,
+                                          float& mean, float& rstd) {
+    mean = row_sum<LPR>(sum) * inv_w;
+    float sq = 0.f;
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        const int c = sub + LPR * it;
+        if (live && c < nchunk) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const float d = v[it][k] - mean;
+                sq = fmaf(d, d, sq);
+            }
+        }
+    }
+    rstd = rsqrtf(row_sum<LPR>(sq) * inv_w + kLnEps);
+}
+
+// End of both backward kernels: the lanes' sums of dy * xhat (dg) and dy (db) over their rows become the workgroup's partial row
+// pair partials[blockIdx.x][2][width], the layout the parameter reduce reads (csrc/reduce_many.hip).  The wave's row groups
+// (lanes sub, sub + LPR, ... hold the same columns) are folded by shuffles, waves 1.. park theirs in `red` ([waves - 1][2][width]
+// of LDS), wave 0 adds them in wave order and writes.
+template <int VEC, int LPR, int ITERS>
+__device__ __forceinline__ void param_grad_epilogue(float (&dg)[ITERS][VEC], float (&db)[ITERS][VEC], float* red,
+                                                    float* __restrict__ partials, int width) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int sub = lane % LPR, rsub = lane / LPR;
+    const int nchunk = width / VEC;
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it)
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+#pragma unroll
+            for (int off = LPR; off < 64; off <<= 1) {
+                dg[it][k] += __shfl_xor(dg[it][k], off, 64);
+                db[it][k] += __shfl_xor(db[it][k], off, 64);
+            }
+        }
+    if (wid > 0 && rsub == 0) {
+        float* mine = red + (size_t)(wid - 1) * 2 * width;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int c = sub + LPR * it;
+            if (c < nchunk)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    mine[c * VEC + k] = dg[it][k];
+                    mine[width + c * VEC + k] = db[it][k];
+                }
+        }
+    }
+    __syncthreads();
+    if (wid == 0 && rsub == 0) {
+        float* outp = partials + (size_t)blockIdx.x * 2 * width;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int c = sub + LPR * it;
+            if (c < nchunk)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    float a = dg[it][k], b = db[it][k];
+                    for (int w = 0; w < nw - 1; ++w) {
+                        a += red[(size_t)w * 2 * width + c * VEC + k];
+                        b += red[(size_t)w * 2 * width + width + c * VEC + k];
+                    }
+                    outp[c * VEC + k] = a;
+                    outp[width + c * VEC + k] = b;
+                }
+        }
+    }
 }
 
 template <typename T, int VEC, int LPR, int ITERS>
@@ -165,11 +250,11 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const void* __restri
         for (int it = 0; it < ITERS; ++it) {
             const int c = sub + LPR * it;
             if (live && c < nchunk) {
-                if constexpr (PF) vec_io<T, VEC>::decode(cx[it], v[it]);
+                if constexpr (PF) chunk_decode<T>(cx[it], v[it]);
                 else vec_io<T, VEC>::load(x, base + (int64_t)c * VEC, v[it]);
                 if (add_in) {  // s = x + rs*drop(add_in), rounded to the activation dtype exactly as a separate add would store it
                     float a2[VEC], l2[VEC], hi[VEC];
-                    if constexpr (PF) vec_io<T, VEC>::decode(ca[it], a2);
+                    if constexpr (PF) chunk_decode<T>(ca[it], a2);
                     else vec_io<T, VEC>::load(add_in, base + (int64_t)c * VEC, a2);
                     if (lo_in) vec_io<T, VEC>::load(lo_in, base + (int64_t)c * VEC, l2);
                     const int64_t e0 = base + (int64_t)c * VEC;
@@ -186,7 +271,9 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const void* __restri
                         // un-rounded one (the backward re-normalises the stored tensor: a 2^-9 relative difference in xhat)
                         v[it][k] = lo_out ? full : hi[k];
                     }
-                    store_stream<T, VEC>(sum_out, base + (int64_t)c * VEC, hi);
+                    // (a non-temporal store for the residual-stream sum was measured here: +1-3 % on the kernel, nothing on the
+                    // step -- profiles/archive_r01_r04/r03_ln_store_ab.txt; the plain store stays)
+                    vec_io<T, VEC>::store(sum_out, base + (int64_t)c * VEC, hi);
                     if (lo_out) vec_io<T, VEC>::store(lo_out, base + (int64_t)c * VEC, l2);
                 } else if (dropping) {
                     const int64_t e0 = base + (int64_t)c * VEC;
@@ -199,31 +286,15 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const void* __restri
                 for (int k = 0; k < VEC; ++k) sum += v[it][k];
             }
         }
-        const float mean = row_sum<LPR>(sum) * inv_w;
-        float sq = 0.f;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int c = sub + LPR * it;
-            if (live && c < nchunk) {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    const float d = v[it][k] - mean;
-                    sq = fmaf(d, d, sq);
-                }
-            }
-        }
-        const float rstd = rsqrtf(row_sum<LPR>(sq) * inv_w + kLnEps);
+        float mean, rstd;
+        row_stats<VEC, LPR, ITERS>(v, sum, live, sub, nchunk, inv_w, mean, rstd);
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int c = sub + LPR * it;
             if (live && c < nchunk) {
                 float g[VEC], b[VEC], r[VEC], o[VEC];
-                vec_io<float, VEC == 8 ? 4 : VEC>::load(gamma, (int64_t)c * VEC, g);
-                vec_io<float, VEC == 8 ? 4 : VEC>::load(beta, (int64_t)c * VEC, b);
-                if constexpr (VEC == 8) {
-                    vec_io<float, 4>::load(gamma, (int64_t)c * VEC + 4, g + 4);
-                    vec_io<float, 4>::load(beta, (int64_t)c * VEC + 4, b + 4);
-                }
+                load_params<VEC>(gamma, c, g);
+                load_params<VEC>(beta, c, b);
                 if (residual) vec_io<T, VEC>::load(residual, base + (int64_t)c * VEC, r);
                 if (residual && lo_in && !add_in) {  // v2 placement: the residual operand is the compensated stream
                     float rl[VEC];
@@ -255,29 +326,6 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(const void* __restri
             rstd_out[row] = rstd;
         }
     }
-}
-
-// element k of a packed 16-byte chunk, and the chunk of VEC fp32 values rounded to the activation dtype
-template <typename T>
-__device__ __forceinline__ float chunk_elem(const uint4& w, int k);
-template <>
-__device__ __forceinline__ float chunk_elem<bf16_t>(const uint4& w, int k) {
-    const uint32_t d = (k >> 1) == 0 ? w.x : (k >> 1) == 1 ? w.y : (k >> 1) == 2 ? w.z : w.w;
-    return (k & 1) ? __uint_as_float(d & 0xffff0000u) : __uint_as_float(d << 16);
-}
-template <>
-__device__ __forceinline__ float chunk_elem<float>(const uint4& w, int k) {
-    return __uint_as_float(k == 0 ? w.x : k == 1 ? w.y : k == 2 ? w.z : w.w);
-}
-template <typename T>
-__device__ __forceinline__ uint4 chunk_pack(const float* v);
-template <>
-__device__ __forceinline__ uint4 chunk_pack<bf16_t>(const float* v) {
-    return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
-}
-template <>
-__device__ __forceinline__ uint4 chunk_pack<float>(const float* v) {
-    return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
 }
 
 // The training default of the forward, specialised like layernorm_bwd_fast_kernel below (round 4): rows in 16-byte chunks (bf16 or fp32),
@@ -339,7 +387,7 @@ __global__ void __launch_bounds__(256, (ITERS == 1 ? 6 : ITERS == 2 ? 5 : ITERS 
         for (int it = 0; it < ITERS; ++it) {
             const int c = sub + LPR * it;
             if (live && c < nchunk) {
-                vec_io<T, VEC>::decode(cx[it], v[it]);
+                chunk_decode<T>(cx[it], v[it]);
                 if constexpr (EX) {
                     if (dropping) {
                         const int64_t e0 = row * width + (int64_t)c * VEC;
@@ -351,11 +399,11 @@ __global__ void __launch_bounds__(256, (ITERS == 1 ? 6 : ITERS == 2 ? 5 : ITERS 
                 }
                 if (adding) {  // the stream as every other consumer sees it: rounded to bf16 exactly as a separate add would store it
                     float a2[VEC];
-                    vec_io<T, VEC>::decode(ca[it], a2);
+                    chunk_decode<T>(ca[it], a2);
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) v[it][k] += a2[k];
                     const uint4 w = chunk_pack<T>(v[it]);
-                    vec_io<T, VEC>::decode(w, v[it]);
+                    chunk_decode<T>(w, v[it]);
                     const uint32_t e = ((uint32_t)row * (uint32_t)width + (uint32_t)(c * VEC)) * (uint32_t)ES;
                     *(uint4*)((char*)sum_out + e) = w;
                 }
@@ -363,31 +411,15 @@ __global__ void __launch_bounds__(256, (ITERS == 1 ? 6 : ITERS == 2 ? 5 : ITERS 
                 for (int k = 0; k < VEC; ++k) sum += v[it][k];
             }
         }
-        const float mean = row_sum<LPR>(sum) * inv_w;
-        float sq = 0.f;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int c = sub + LPR * it;
-            if (live && c < nchunk) {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    const float d = v[it][k] - mean;
-                    sq = fmaf(d, d, sq);
-                }
-            }
-        }
-        const float rstd = rsqrtf(row_sum<LPR>(sq) * inv_w + kLnEps);
+        float mean, rstd;
+        row_stats<VEC, LPR, ITERS>(v, sum, live, sub, nchunk, inv_w, mean, rstd);
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int c = sub + LPR * it;
             if (live && c < nchunk) {
                 float g[VEC], b[VEC], o[VEC];
-#pragma unroll
-                for (int q = 0; q < VEC / 4; ++q) {
-                    const float4 g4 = *(const float4*)(gamma + c * VEC + 4 * q), b4 = *(const float4*)(beta + c * VEC + 4 * q);
-                    g[4 * q] = g4.x; g[4 * q + 1] = g4.y; g[4 * q + 2] = g4.z; g[4 * q + 3] = g4.w;
-                    b[4 * q] = b4.x; b[4 * q + 1] = b4.y; b[4 * q + 2] = b4.z; b[4 * q + 3] = b4.w;
-                }
+                load_params<VEC>(gamma, c, g);
+                load_params<VEC>(beta, c, b);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) o[k] = fmaf((v[it][k] - mean) * rstd, g[k], b[k]);
                 if constexpr (EX) {  // DropPath factor of this row's sample
@@ -439,11 +471,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const void* __restri
     for (int it = 0; it < ITERS; ++it) {
         const int c = sub + LPR * it;
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            dg[it][k] = 0.f;
-            db[it][k] = 0.f;
-            gm[it][k] = (c < nchunk) ? gamma[c * VEC + k] : 0.f;
-        }
+        for (int k = 0; k < VEC; ++k) dg[it][k] = db[it][k] = gm[it][k] = 0.f;
+        if (c < nchunk) load_params<VEC>(gamma, c, gm[it]);
     }
     for (int64_t row0 = wave * RPW; row0 < rows; row0 += nwaves * RPW) {
         const int64_t row = row0 + rsub;
@@ -522,49 +551,7 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(const void* __restri
             }
         }
     }
-    // fold the wave's row groups (lanes sub, sub+LPR, ... hold the same columns)
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-#pragma unroll
-            for (int off = LPR; off < 64; off <<= 1) {
-                dg[it][k] += __shfl_xor(dg[it][k], off, 64);
-                db[it][k] += __shfl_xor(db[it][k], off, 64);
-            }
-        }
-    if (wid > 0 && rsub == 0) {
-        float* mine = red + (size_t)(wid - 1) * 2 * width;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int c = sub + LPR * it;
-            if (c < nchunk)
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    mine[c * VEC + k] = dg[it][k];
-                    mine[width + c * VEC + k] = db[it][k];
-                }
-        }
-    }
-    __syncthreads();
-    if (wid == 0 && rsub == 0) {
-        float* outp = partials + (size_t)blockIdx.x * 2 * width;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int c = sub + LPR * it;
-            if (c < nchunk)
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    float a = dg[it][k], b = db[it][k];
-                    for (int w = 0; w < nw - 1; ++w) {
-                        a += red[(size_t)w * 2 * width + c * VEC + k];
-                        b += red[(size_t)w * 2 * width + width + c * VEC + k];
-                    }
-                    outp[c * VEC + k] = a;
-                    outp[width + c * VEC + k] = b;
-                }
-        }
-    }
+    param_grad_epilogue<VEC, LPR, ITERS>(dg, db, red, partials, width);
 }
 
 // The training default, specialised (round 4): bf16 rows in 16-byte chunks, no dropout, no DropPath scale, one gradient out.
@@ -598,15 +585,8 @@ __global__ void __launch_bounds__(256, (ITERS == 1 ? (EX ? 4 : 5) : ITERS == 2 ?
     for (int it = 0; it < ITERS; ++it) {
         const int c = sub + LPR * it;
 #pragma unroll
-        for (int q = 0; q < VEC / 4; ++q) {
-            const float4 g4 = c < nchunk ? *(const float4*)(gamma + c * VEC + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-            gm[it][4 * q] = g4.x; gm[it][4 * q + 1] = g4.y; gm[it][4 * q + 2] = g4.z; gm[it][4 * q + 3] = g4.w;
-        }
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            dg[it][k] = 0.f;
-            db[it][k] = 0.f;
-        }
+        for (int k = 0; k < VEC; ++k) dg[it][k] = db[it][k] = gm[it][k] = 0.f;
+        if (c < nchunk) load_params<VEC>(gamma, c, gm[it]);
     }
     // every tensor is addressed as (uniform base) + (32-bit byte offset): one offset register per chunk instead of a 64-bit
     // pointer per tensor and chunk (the launcher keeps rows * width * 2 below 4 GiB for this kernel)
@@ -713,49 +693,7 @@ __global__ void __launch_bounds__(256, (ITERS == 1 ? (EX ? 4 : 5) : ITERS == 2 ?
             }
         }
     }
-    // fold the wave's row groups (lanes sub, sub+LPR, ... hold the same columns), then the workgroup's waves through LDS
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-#pragma unroll
-            for (int off = LPR; off < 64; off <<= 1) {
-                dg[it][k] += __shfl_xor(dg[it][k], off, 64);
-                db[it][k] += __shfl_xor(db[it][k], off, 64);
-            }
-        }
-    if (wid > 0 && rsub == 0) {
-        float* mine = red + (size_t)(wid - 1) * 2 * width;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int c = sub + LPR * it;
-            if (c < nchunk)
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    mine[c * VEC + k] = dg[it][k];
-                    mine[width + c * VEC + k] = db[it][k];
-                }
-        }
-    }
-    __syncthreads();
-    if (wid == 0 && rsub == 0) {
-        float* outp = partials + (size_t)blockIdx.x * 2 * width;
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) {
-            const int c = sub + LPR * it;
-            if (c < nchunk)
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    float a = dg[it][k], b = db[it][k];
-                    for (int w = 0; w < nw - 1; ++w) {
-                        a += red[(size_t)w * 2 * width + c * VEC + k];
-                        b += red[(size_t)w * 2 * width + width + c * VEC + k];
-                    }
-                    outp[c * VEC + k] = a;
-                    outp[width + c * VEC + k] = b;
-                }
-        }
-    }
+    param_grad_epilogue<VEC, LPR, ITERS>(dg, db, red, partials, width);
 }
 
 // Sum of the per-workgroup partial rows [nblocks][2 * width] into dgamma | dbeta (overwrite, or add when accumulate != 0) in
@@ -812,43 +750,62 @@ struct LnExtra {  // stochastic extras and the compensated-stream operands, all 
     void* lo_out = nullptr;
 };
 
+// the operands of one forward / backward call, as the entry points take them
+struct FwdArgs {
+    const void *x, *residual, *add_in;
+    const float *gamma, *beta;
+    void *y, *sum_out;
+    float *mean, *rstd;
+    int64_t rows; int width; hipStream_t s; LnExtra ex;
+};
+struct BwdArgs {
+    const void *dy, *x;
+    const float *gamma, *mean, *rstd;
+    void* dx;
+    float *dgamma, *dbeta, *ws;
+    int64_t rows; int width; hipStream_t s;
+    const void* dres_in; void* dadd_out; LnExtra ex; int v1_mode, accumulate;
+};
+
 template <typename T, int VEC, int LPR, int ITERS>
-int run_fwd(const void* x, const void* res, const float* g, const float* b, void* y, float* mean, float* rstd, int64_t rows,
-            int width, hipStream_t s, const void* add_in, void* sum_out, const LnExtra& ex) {
+int run_fwd(const FwdArgs& a) {
     constexpr int rows_per_block = 4 * (64 / LPR);
-    int64_t blocks = (rows + rows_per_block - 1) / rows_per_block;
+    int64_t blocks = (a.rows + rows_per_block - 1) / rows_per_block;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((layernorm_fwd_kernel<T, VEC, LPR, ITERS>), dim3((unsigned)blocks), dim3(256), 0, s, x, res, g, b, y,
-                       mean, rstd, rows, width, add_in, sum_out, ex.row_scale, ex.rows_per_sample, ex.drop_p, ex.seed, ex.lo_in,
-                       ex.lo_out);
+    hipLaunchKernelGGL((layernorm_fwd_kernel<T, VEC, LPR, ITERS>), dim3((unsigned)blocks), dim3(256), 0, a.s, a.x, a.residual, a.gamma,
+                       a.beta, a.y, a.mean, a.rstd, a.rows, a.width, a.add_in, a.sum_out, a.ex.row_scale, a.ex.rows_per_sample,
+                       a.ex.drop_p, a.ex.seed, a.ex.lo_in, a.ex.lo_out);
     HS_LAUNCH_CHECK("layernorm_fwd");
     return HS_OK;
 }
 
-template <typename T, int VEC, int LPR, int ITERS>
-int run_bwd(const void* dy, const void* x, const float* g, const float* mean, const float* rstd, void* dx, float* dgamma,
-            float* dbeta, float* ws, int64_t rows, int width, hipStream_t s, const void* dres_in, void* dadd_out,
-            const LnExtra& ex, int v1_mode, int accumulate) {
-    const int blocks = bwd_blocks(rows);
-    const size_t smem = (size_t)3 * 2 * width * sizeof(float);
-    auto kern = layernorm_bwd_kernel<T, VEC, LPR, ITERS>;
-    if (smem > 48 * 1024) HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), smem, s, dy, x, g, mean, rstd, dx, ws, rows, width, dres_in, dadd_out,
-                       ex.row_scale, ex.rows_per_sample, ex.drop_p, ex.seed, v1_mode);
-    HS_LAUNCH_CHECK("layernorm_bwd");
-    if ((accumulate & HS_ACC_DEFER) && width % 4 == 0)  // the parameter reduce joins the stream's deferred queue (csrc/reduce_many.hip)
-        return reduce_defer(ws, 2 * width, blocks, width, 2 * width, dgamma, dbeta, accumulate & 1, s);
-    if (width % 4 == 0) return reduce_now(ws, 2 * width, blocks, width, 2 * width, dgamma, dbeta, accumulate & 1, s);
-    accumulate &= 1;
-    hipLaunchKernelGGL(layernorm_param_reduce_kernel, dim3((2 * width + 15) / 16), dim3(1024), 0, s, ws, dgamma, dbeta, blocks, width,
-                       accumulate);
+// dgamma | dbeta from the `blocks` partial row pairs of a backward kernel: the float4 sum of csrc/reduce_many.hip, queued on the
+// stream's deferred list (HS_ACC_DEFER) or launched at once; element-wise where the width has no float4 columns
+int reduce_param_grads(const BwdArgs& a, int blocks) {
+    const int width = a.width, add = a.accumulate & 1;
+    if ((a.accumulate & HS_ACC_DEFER) && width % 4 == 0)
+        return reduce_defer(a.ws, 2 * width, blocks, width, 2 * width, a.dgamma, a.dbeta, add, a.s);
+    if (width % 4 == 0) return reduce_now(a.ws, 2 * width, blocks, width, 2 * width, a.dgamma, a.dbeta, add, a.s);
+    hipLaunchKernelGGL(layernorm_param_reduce_kernel, dim3((2 * width + 15) / 16), dim3(1024), 0, a.s, a.ws, a.dgamma, a.dbeta, blocks,
+                       width, add);
     HS_LAUNCH_CHECK("layernorm_param_reduce");
     return HS_OK;
 }
 
-template <typename T, int LPR, int ITERS, bool EX = false>
-int run_fwd_fast(const void* x, const void* add_in, const float* g, const float* b, void* y, void* sum_out, float* mean, float* rstd,
-                 int64_t rows, int width, hipStream_t s, const void* residual, const LnExtra& ex = LnExtra{}) {
+template <typename T, int VEC, int LPR, int ITERS>
+int run_bwd(const BwdArgs& a) {
+    const int blocks = bwd_blocks(a.rows);
+    const size_t smem = (size_t)3 * 2 * a.width * sizeof(float);
+    auto kern = layernorm_bwd_kernel<T, VEC, LPR, ITERS>;
+    if (smem > 48 * 1024) HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), smem, a.s, a.dy, a.x, a.gamma, a.mean, a.rstd, a.dx, a.ws, a.rows, a.width,
+                       a.dres_in, a.dadd_out, a.ex.row_scale, a.ex.rows_per_sample, a.ex.drop_p, a.ex.seed, a.v1_mode);
+    HS_LAUNCH_CHECK("layernorm_bwd");
+    return reduce_param_grads(a, blocks);
+}
+
+template <typename T, int LPR, int ITERS, bool EX>
+int run_fwd_fast(const FwdArgs& a) {
     auto kern = layernorm_fwd_fast_kernel<T, LPR, ITERS, EX>;
     static int resident = 0;
     if (resident == 0) {
@@ -858,10 +815,10 @@ int run_fwd_fast(const void* x, const void* add_in, const float* g, const float*
     }
     constexpr int rows_per_pass = 4 * (64 / LPR);
     int64_t blocks = (int64_t)usable_cus() * resident;
-    const int64_t by_rows = (rows + rows_per_pass - 1) / rows_per_pass;
+    const int64_t by_rows = (a.rows + rows_per_pass - 1) / rows_per_pass;
     if (blocks > by_rows) blocks = by_rows;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, x, add_in, g, b, y, sum_out, mean, rstd, rows, width, residual,
-                       ex.row_scale, ex.rows_per_sample, ex.drop_p, ex.seed);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, a.s, a.x, a.add_in, a.gamma, a.beta, a.y, a.sum_out, a.mean, a.rstd,
+                       a.rows, a.width, a.residual, a.ex.row_scale, a.ex.rows_per_sample, a.ex.drop_p, a.ex.seed);
     HS_LAUNCH_CHECK("layernorm_fwd_fast");
     return HS_OK;
 }
@@ -869,11 +826,10 @@ int run_fwd_fast(const void* x, const void* add_in, const float* g, const float*
 // One resident round: as many workgroups as the chip holds at this instantiation's register / LDS footprint (every workgroup
 // then sees the same number of rows and there is no second, partly filled round), at most kBwdMaxBlocks partial rows, at
 // least one row group per wave.
-template <typename T, int LPR, int ITERS, bool EX = false>
-int run_bwd_fast(const void* dy, const void* x, const float* g, const float* mean, const float* rstd, void* dx, float* dgamma,
-                 float* dbeta, float* ws, int64_t rows, int width, hipStream_t s, const void* dres_in, int accumulate,
-                 const LnExtra& ex = LnExtra{}) {
+template <typename T, int LPR, int ITERS, bool EX>
+int run_bwd_fast(const BwdArgs& a) {
     auto kern = layernorm_bwd_fast_kernel<T, LPR, ITERS, EX>;
+    const int width = a.width;
     const size_t smem = (size_t)3 * 2 * width * sizeof(float);
     if (smem > 48 * 1024) HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     static int resident_width = 0, resident = 0;  // per instantiation; the LDS footprint follows the width
@@ -886,23 +842,16 @@ int run_bwd_fast(const void* dy, const void* x, const float* g, const float* mea
     constexpr int rows_per_pass = 4 * (64 / LPR);
     int64_t blocks = (int64_t)usable_cus() * resident;
     if (blocks > kBwdMaxBlocks) blocks = kBwdMaxBlocks;
-    const int64_t by_rows = (rows + rows_per_pass - 1) / rows_per_pass;
+    const int64_t by_rows = (a.rows + rows_per_pass - 1) / rows_per_pass;
     if (blocks > by_rows) blocks = by_rows;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), smem, s, dy, x, g, mean, rstd, dx, ws, rows, width, dres_in, ex.row_scale,
-                       ex.rows_per_sample, ex.drop_p, ex.seed);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), smem, a.s, a.dy, a.x, a.gamma, a.mean, a.rstd, a.dx, a.ws, a.rows, width,
+                       a.dres_in, a.ex.row_scale, a.ex.rows_per_sample, a.ex.drop_p, a.ex.seed);
     HS_LAUNCH_CHECK("layernorm_bwd_fast");
-    if ((accumulate & HS_ACC_DEFER) && width % 4 == 0)
-        return reduce_defer(ws, 2 * width, (int)blocks, width, 2 * width, dgamma, dbeta, accumulate & 1, s);
-    if (width % 4 == 0) return reduce_now(ws, 2 * width, (int)blocks, width, 2 * width, dgamma, dbeta, accumulate & 1, s);
-    accumulate &= 1;
-    hipLaunchKernelGGL(layernorm_param_reduce_kernel, dim3((2 * width + 15) / 16), dim3(1024), 0, s, ws, dgamma, dbeta, (int)blocks,
-                       width, accumulate);
-    HS_LAUNCH_CHECK("layernorm_param_reduce");
-    return HS_OK;
+    return reduce_param_grads(a, (int)blocks);
 }
 
 // picks lanes-per-row and the per-lane register tile for a row of `width` elements in VEC-wide chunks
-template <typename T, int VEC, typename F>
+template <int VEC, typename F>
 int with_shape(int width, F&& f) {
     const int chunks = width / VEC;
     using std::integral_constant;
@@ -915,8 +864,94 @@ int with_shape(int width, F&& f) {
     if (chunks <= 128) return f(integral_constant<int, 64>{}, integral_constant<int, 2>{});
     if (chunks <= 256) return f(integral_constant<int, 64>{}, integral_constant<int, 4>{});
     if (chunks <= 512) return f(integral_constant<int, 64>{}, integral_constant<int, 8>{});
-    if (chunks <= 1024 && VEC == 1) return f(integral_constant<int, 64>{}, integral_constant<int, 16>{});
+    if constexpr (VEC == 1) {  // (16 registers per lane and tensor are affordable for single elements only)
+        if (chunks <= 1024) return f(integral_constant<int, 64>{}, integral_constant<int, 16>{});
+    }
     return fail(HS_ERR_UNSUPPORTED, "layernorm width %d too large", width);
+}
+
+// What the specialised kernels take: rows of whole 16-byte chunks (width % 8 == 0 in bf16, % 4 in fp32) of at most 8 KB (4096 bf16 /
+// 2048 fp32 columns: 512 chunks, the widest shape of with_shape), in a tensor below 4 GiB (they address by 32-bit byte offsets).
+template <typename T>
+constexpr bool fast_path_fits(int64_t rows, int width) {
+    constexpr int64_t es = (int64_t)sizeof(T);
+    return width * es % 16 == 0 && width * es <= 8192 && rows * width * es < (1ll << 32);
+}
+static_assert(fast_path_fits<bf16_t>(1, 4096) && !fast_path_fits<bf16_t>(1, 4104) && !fast_path_fits<bf16_t>(1, 4092), "bf16: 8 | width <= 4096");
+static_assert(fast_path_fits<float>(1, 2048) && !fast_path_fits<float>(1, 2052) && !fast_path_fits<float>(1, 2046), "fp32: 4 | width <= 2048");
+static_assert(fast_path_fits<bf16_t>((1 << 19) - 1, 4096) && !fast_path_fits<bf16_t>(1 << 19, 4096), "bf16: rows * width * 2 < 4 GiB");
+static_assert(fast_path_fits<float>((1 << 19) - 1, 2048) && !fast_path_fits<float>(1 << 19, 2048), "fp32: rows * width * 4 < 4 GiB");
+
+// The dispatch: which kernel a call runs.  The names are the rows of the table in tests/test_gpu_layernorm.py.
+enum class FwdPath { fast_plain, fast_ex, general_vec, general_elem };
+enum class BwdPath { fast_bf16, fast_fp32, fast_ex, general_v1, general };
+
+template <typename T>
+FwdPath fwd_path(const FwdArgs& a) {
+    constexpr bool bf16 = std::is_same_v<T, bf16_t>;
+    const LnExtra& ex = a.ex;
+    const bool plain = !(a.residual && a.add_in) && !ex.row_scale && ex.drop_p == 0.f && !ex.lo_in && !ex.lo_out;
+    // the v2 / plain form with dropout and / or a DropPath factor (y = [residual +] rs LN(drop(x))): the specialised kernel's EX variant
+    const bool extras = !a.add_in && (ex.row_scale || ex.drop_p > 0.f) && !ex.lo_in && !ex.lo_out;
+    if (fast_path_fits<T>(a.rows, a.width)) {
+        if (bf16 && extras) return FwdPath::fast_ex;
+        if (plain) return FwdPath::fast_plain;
+    }
+    return a.width % (16 / (int)sizeof(T)) == 0 ? FwdPath::general_vec : FwdPath::general_elem;
+}
+
+template <typename T>
+BwdPath bwd_path(const BwdArgs& a) {
+    constexpr bool bf16 = std::is_same_v<T, bf16_t>;
+    const bool plain = !a.ex.row_scale && a.ex.drop_p == 0.f && !a.dadd_out;
+    if (fast_path_fits<T>(a.rows, a.width)) {
+        if (bf16 && !plain && !a.v1_mode && !a.dadd_out && !a.dres_in) return BwdPath::fast_ex;
+        if (plain) return bf16 ? BwdPath::fast_bf16 : BwdPath::fast_fp32;
+    }
+    return a.v1_mode ? BwdPath::general_v1 : BwdPath::general;
+}
+
+// one kernel family (FAST: the specialised pair, else the general pair in VEC-wide chunks) at the lane shape of the width
+template <typename T, int VEC, bool FAST, bool EX = false>
+int launch_fwd(const FwdArgs& a) {
+    return with_shape<VEC>(a.width, [&](auto lpr, auto it) {
+        constexpr int LPR = decltype(lpr)::value, ITERS = decltype(it)::value;
+        if constexpr (FAST) return run_fwd_fast<T, LPR, ITERS, EX>(a);
+        else return run_fwd<T, VEC, LPR, ITERS>(a);
+    });
+}
+template <typename T, int VEC, bool FAST, bool EX = false>
+int launch_bwd(const BwdArgs& a) {
+    return with_shape<VEC>(a.width, [&](auto lpr, auto it) {
+        constexpr int LPR = decltype(lpr)::value, ITERS = decltype(it)::value;
+        if constexpr (FAST) return run_bwd_fast<T, LPR, ITERS, EX>(a);
+        else return run_bwd<T, VEC, LPR, ITERS>(a);
+    });
+}
+
+template <typename T>
+int dispatch_fwd(const FwdArgs& a) {
+    constexpr int V = 16 / (int)sizeof(T);
+    switch (fwd_path<T>(a)) {
+        case FwdPath::fast_plain: return launch_fwd<T, V, true>(a);
+        case FwdPath::fast_ex: return launch_fwd<bf16_t, 8, true, true>(a);  // (bf16 only: fwd_path<float> never answers this)
+        case FwdPath::general_vec: return launch_fwd<T, V, false>(a);
+        case FwdPath::general_elem: break;
+    }
+    return launch_fwd<T, 1, false>(a);
+}
+
+template <typename T>
+int dispatch_bwd(const BwdArgs& a) {
+    constexpr int V = 16 / (int)sizeof(T);
+    switch (bwd_path<T>(a)) {
+        case BwdPath::fast_bf16:
+        case BwdPath::fast_fp32: return launch_bwd<T, V, true>(a);
+        case BwdPath::fast_ex: return launch_bwd<bf16_t, 8, true, true>(a);  // (bf16 only)
+        case BwdPath::general_v1:
+        case BwdPath::general: break;  // one kernel, told apart by v1_mode
+    }
+    return a.width % V == 0 ? launch_bwd<T, V, false>(a) : launch_bwd<T, 1, false>(a);
 }
 
 }  // namespace
@@ -951,24 +986,8 @@ int ln_fwd_impl(const void* x, const void* residual, const float* gamma, const f
     HS_CHECK_ALIGNED("hs_layernorm_fwd", 16, x, residual, gamma, beta, y, add_in, sum_out, ex.lo_in, ex.lo_out);
     if (int st = check_extra(ex, rows)) return st;
     if (rows == 0) return HS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool plain = !(residual && add_in) && !ex.row_scale && ex.drop_p == 0.f && !ex.lo_in && !ex.lo_out;
-    // the v2 / plain form with dropout and / or a DropPath factor (y = [residual +] rs LN(drop(x))): the specialised kernel's EX variant
-    const bool extras = !add_in && (ex.row_scale || ex.drop_p > 0.f) && !ex.lo_in && !ex.lo_out;
-    if (dtype == HS_BF16 && extras && width % 8 == 0 && width <= 4096 && rows * width * 2 < (1ll << 32))
-        return with_shape<bf16_t, 8>(width, [&](auto lpr, auto it) { return run_fwd_fast<bf16_t, decltype(lpr)::value, decltype(it)::value, true>(x, add_in, gamma, beta, y, sum_out, mean, rstd, rows, width, s, residual, ex); });
-    if (dtype == HS_BF16) {
-        if (plain && width % 8 == 0 && width <= 4096 && rows * width * 2 < (1ll << 32))
-            return with_shape<bf16_t, 8>(width, [&](auto lpr, auto it) { return run_fwd_fast<bf16_t, decltype(lpr)::value, decltype(it)::value>(x, add_in, gamma, beta, y, sum_out, mean, rstd, rows, width, s, residual); });
-        if (width % 8 == 0)
-            return with_shape<bf16_t, 8>(width, [&](auto lpr, auto it) { return run_fwd<bf16_t, 8, decltype(lpr)::value, decltype(it)::value>(x, residual, gamma, beta, y, mean, rstd, rows, width, s, add_in, sum_out, ex); });
-        return with_shape<bf16_t, 1>(width, [&](auto lpr, auto it) { return run_fwd<bf16_t, 1, decltype(lpr)::value, decltype(it)::value>(x, residual, gamma, beta, y, mean, rstd, rows, width, s, add_in, sum_out, ex); });
-    }
-    if (plain && width % 4 == 0 && width <= 2048 && rows * width * 4 < (1ll << 32))
-        return with_shape<float, 4>(width, [&](auto lpr, auto it) { return run_fwd_fast<float, decltype(lpr)::value, decltype(it)::value>(x, add_in, gamma, beta, y, sum_out, mean, rstd, rows, width, s, residual); });
-    if (width % 4 == 0)
-        return with_shape<float, 4>(width, [&](auto lpr, auto it) { return run_fwd<float, 4, decltype(lpr)::value, decltype(it)::value>(x, residual, gamma, beta, y, mean, rstd, rows, width, s, add_in, sum_out, ex); });
-    return with_shape<float, 1>(width, [&](auto lpr, auto it) { return run_fwd<float, 1, decltype(lpr)::value, decltype(it)::value>(x, residual, gamma, beta, y, mean, rstd, rows, width, s, add_in, sum_out, ex); });
+    const FwdArgs a{x, residual, add_in, gamma, beta, y, sum_out, mean, rstd, rows, width, (hipStream_t)stream, ex};
+    return dtype == HS_BF16 ? dispatch_fwd<bf16_t>(a) : dispatch_fwd<float>(a);
 }
 
 int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
@@ -981,22 +1000,9 @@ int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const float* 
     // (dgamma / dbeta are written as float4 by the partial-record sum, csrc/reduce_many.hip)
     HS_CHECK_ALIGNED("hs_layernorm_bwd", 16, dy, x, gamma, dx, dgamma, dbeta, workspace, dres_in, dadd_out);
     if (int st = check_extra(ex, rows)) return st;
-    hipStream_t s = (hipStream_t)stream;
-    const bool plain = !ex.row_scale && ex.drop_p == 0.f && !dadd_out;
-    if (dtype == HS_BF16 && !plain && !v1_mode && !dadd_out && !dres_in && width % 8 == 0 && width <= 4096 && rows * width * 2 < (1ll << 32))
-        return with_shape<bf16_t, 8>(width, [&](auto lpr, auto it) { return run_bwd_fast<bf16_t, decltype(lpr)::value, decltype(it)::value, true>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, s, dres_in, accumulate, ex); });
-    if (dtype == HS_F32 && plain && width % 4 == 0 && width <= 2048 && rows * width * 4 < (1ll << 32))
-        return with_shape<float, 4>(width, [&](auto lpr, auto it) { return run_bwd_fast<float, decltype(lpr)::value, decltype(it)::value>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, s, dres_in, accumulate); });
-    if (dtype == HS_BF16) {
-        if (plain && width % 8 == 0 && width <= 4096 && rows * width * 2 < (1ll << 32))
-            return with_shape<bf16_t, 8>(width, [&](auto lpr, auto it) { return run_bwd_fast<bf16_t, decltype(lpr)::value, decltype(it)::value>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, s, dres_in, accumulate); });
-        if (width % 8 == 0)
-            return with_shape<bf16_t, 8>(width, [&](auto lpr, auto it) { return run_bwd<bf16_t, 8, decltype(lpr)::value, decltype(it)::value>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, s, dres_in, dadd_out, ex, v1_mode, accumulate); });
-        return with_shape<bf16_t, 1>(width, [&](auto lpr, auto it) { return run_bwd<bf16_t, 1, decltype(lpr)::value, decltype(it)::value>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, s, dres_in, dadd_out, ex, v1_mode, accumulate); });
-    }
-    if (width % 4 == 0)
-        return with_shape<float, 4>(width, [&](auto lpr, auto it) { return run_bwd<float, 4, decltype(lpr)::value, decltype(it)::value>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, s, dres_in, dadd_out, ex, v1_mode, accumulate); });
-    return with_shape<float, 1>(width, [&](auto lpr, auto it) { return run_bwd<float, 1, decltype(lpr)::value, decltype(it)::value>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, s, dres_in, dadd_out, ex, v1_mode, accumulate); });
+    const BwdArgs a{dy, x, gamma, mean, rstd, dx, dgamma, dbeta, workspace, rows, width, (hipStream_t)stream, dres_in, dadd_out, ex,
+                    v1_mode, accumulate};
+    return dtype == HS_BF16 ? dispatch_bwd<bf16_t>(a) : dispatch_bwd<float>(a);
 }
 
 hs::LnExtra make_extra(const float* row_scale, int64_t rows_per_sample, float drop_p, uint64_t seed) {

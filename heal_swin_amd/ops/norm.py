@@ -27,6 +27,18 @@ def _norm_param_result(weight, bias, dgamma, dbeta, direct):
     return None, None
 
 
+def _norm_backward(weight, bias, want, rows, width, device, call):
+    """What both LayerNorm backwards do around their kernel: `call(dgamma, dbeta, workspace, accumulate)` launches it; returns the
+    weight / bias gradients for autograd (None where they were deposited directly)."""
+    dgamma, dbeta, direct = _norm_param_grads(weight, bias, width, device, want)
+    ws = torch.empty(int(lib.hs_layernorm_bwd_workspace(rows, width)), dtype=torch.float32, device=device)
+    acc = (1 | _defer_flag(device)) if direct else 0
+    call(ptr(dgamma), ptr(dbeta), ptr(ws), acc)
+    if acc & _lib.HS_ACC_DEFER:
+        _defer_keep(device, ws)
+    return _norm_param_result(weight, bias, dgamma, dbeta, direct)
+
+
 class LayerNormFn(torch.autograd.Function):
     """y = [residual +] rs * LayerNorm(drop(x)) over the last dimension (eps 1e-5), statistics in fp32; rs / drop are the
     optional per-sample DropPath factor and dropout mask (train mode), absent in eval."""
@@ -57,20 +69,13 @@ class LayerNormFn(torch.autograd.Function):
         if pre is not None:
             assert res is None and extras is None and not want_lo and res_lo is None
             y, mean, rstd = pre
-        elif want_lo or res_lo is not None:
-            assert not passthrough and (res is not None or res_lo is None)
+        else:
+            assert not (passthrough and want_lo) and (res is not None or res_lo is None)
             y_lo = torch.empty_like(x) if want_lo else None
             rs, rps, p, seed = extras if extras is not None else (None, 1, 0.0, 0)
             check(lib.hs_layernorm_fwd_ex(ptr(x), ptr(res), None, ptr(None if res_lo is None else _aligned(res_lo.contiguous())), ptr(g), ptr(b),
                                           ptr(y), None, ptr(y_lo), ptr(mean), ptr(rstd), ptr(rs), rps, p, seed, rows, width, dt,
                                           stream_ptr(x.device)), "hs_layernorm_fwd_ex")
-        elif extras is None:
-            check(lib.hs_layernorm_fwd(ptr(x), ptr(res), ptr(g), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, width, dt,
-                                       stream_ptr(x.device)), "hs_layernorm_fwd")
-        else:
-            rs, rps, p, seed = extras
-            check(lib.hs_layernorm_drop_fwd(ptr(x), ptr(res), ptr(g), ptr(b), ptr(y), ptr(mean), ptr(rstd), ptr(rs), rps, p, seed,
-                                            rows, width, dt, stream_ptr(x.device)), "hs_layernorm_drop_fwd")
         ctx.save_for_backward(x, g, mean, rstd, None if extras is None else extras[0])
         ctx.meta = (rows, width, dt, residual is not None, extras)
         ctx.params = (weight, bias)
@@ -94,24 +99,17 @@ class LayerNormFn(torch.autograd.Function):
             return dx_alias, None, None, None, None, None, None, None, None
         dy = _aligned(dy.contiguous())
         dx = torch.empty_like(x)
-        dgamma, dbeta, direct = _norm_param_grads(weight, bias, width, x.device, ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
-        ws = torch.empty(int(lib.hs_layernorm_bwd_workspace(rows, width)), dtype=torch.float32, device=x.device)
-        acc = (1 | _defer_flag(x.device)) if direct else 0
-        if dx_alias is not None:
-            check(lib.hs_add_layernorm_bwd(ptr(dy), ptr(_aligned(dx_alias.contiguous())), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dx),
-                                           ptr(dgamma), ptr(dbeta), ptr(ws), acc, rows, width, dt, stream_ptr(x.device)),
-                  "hs_add_layernorm_bwd")
-        elif extras is None:
-            check(lib.hs_layernorm_bwd(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws),
-                                       acc, rows, width, dt, stream_ptr(x.device)), "hs_layernorm_bwd")
-        else:
-            _, rps, p, seed = extras
-            check(lib.hs_layernorm_drop_bwd(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dx), ptr(dgamma), ptr(dbeta),
-                                            ptr(ws), acc, ptr(rs), rps, p, seed, rows, width, dt, stream_ptr(x.device)),
-                  "hs_layernorm_drop_bwd")
-        if acc & _lib.HS_ACC_DEFER:
-            _defer_keep(x.device, ws)
-        dw, db = _norm_param_result(weight, bias, dgamma, dbeta, direct)
+
+        def call(dgamma, dbeta, ws, acc):
+            if dx_alias is not None:
+                check(lib.hs_add_layernorm_bwd(ptr(dy), ptr(_aligned(dx_alias.contiguous())), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dx),
+                                               dgamma, dbeta, ws, acc, rows, width, dt, stream_ptr(x.device)), "hs_add_layernorm_bwd")
+            else:
+                _, rps, p, seed = extras if extras is not None else (None, 1, 0.0, 0)
+                check(lib.hs_layernorm_drop_bwd(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dx), dgamma, dbeta, ws, acc, ptr(rs),
+                                                rps, p, seed, rows, width, dt, stream_ptr(x.device)), "hs_layernorm_drop_bwd")
+
+        dw, db = _norm_backward(weight, bias, ctx.needs_input_grad[1] and ctx.needs_input_grad[2], rows, width, x.device, call)
         return dx, dw, db, (dy if has_res else None), None, None, None, None, None
 
 
@@ -155,20 +153,11 @@ class AddLayerNormFn(torch.autograd.Function):
         y = torch.empty_like(a)
         mean = torch.empty(rows, dtype=torch.float32, device=a.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=a.device)
-        s_lo = None
-        if want_lo or a_lo is not None:
-            s_lo = torch.empty_like(a) if want_lo else None
-            rs, rps, p, seed = extras if extras is not None else (None, 1, 0.0, 0)
-            check(lib.hs_layernorm_fwd_ex(ptr(a), None, ptr(b), ptr(None if a_lo is None else _aligned(a_lo.contiguous())), ptr(g), ptr(be), ptr(y),
-                                          ptr(s), ptr(s_lo), ptr(mean), ptr(rstd), ptr(rs), rps, p, seed, rows, width, dt,
-                                          stream_ptr(a.device)), "hs_layernorm_fwd_ex")
-        elif extras is None:
-            check(lib.hs_add_layernorm_fwd(ptr(a), ptr(b), ptr(g), ptr(be), ptr(s), ptr(y), ptr(mean), ptr(rstd), rows, width,
-                                           dt, stream_ptr(a.device)), "hs_add_layernorm_fwd")
-        else:
-            rs, rps, p, seed = extras
-            check(lib.hs_add_layernorm_drop_fwd(ptr(a), ptr(b), ptr(g), ptr(be), ptr(s), ptr(y), ptr(mean), ptr(rstd), ptr(rs),
-                                                rps, p, seed, rows, width, dt, stream_ptr(a.device)), "hs_add_layernorm_drop_fwd")
+        s_lo = torch.empty_like(a) if want_lo else None
+        rs, rps, p, seed = extras if extras is not None else (None, 1, 0.0, 0)
+        check(lib.hs_layernorm_fwd_ex(ptr(a), None, ptr(b), ptr(None if a_lo is None else _aligned(a_lo.contiguous())), ptr(g), ptr(be), ptr(y),
+                                      ptr(s), ptr(s_lo), ptr(mean), ptr(rstd), ptr(rs), rps, p, seed, rows, width, dt,
+                                      stream_ptr(a.device)), "hs_layernorm_fwd_ex")
         ctx.save_for_backward(s, g, mean, rstd, None if extras is None else extras[0])
         ctx.meta = (rows, width, dt, extras)
         ctx.params = (weight, bias)
@@ -189,23 +178,19 @@ class AddLayerNormFn(torch.autograd.Function):
         dy = _aligned(dy.contiguous())
         ds_c = None if ds is None else _aligned(ds.contiguous())
         da = torch.empty_like(s)
-        dgamma, dbeta, direct = _norm_param_grads(weight, bias, width, s.device, ctx.needs_input_grad[2] and ctx.needs_input_grad[3])
-        ws = torch.empty(int(lib.hs_layernorm_bwd_workspace(rows, width)), dtype=torch.float32, device=s.device)
-        acc = (1 | _defer_flag(s.device)) if direct else 0
-        if extras is None:
-            check(lib.hs_add_layernorm_bwd(ptr(dy), ptr(ds_c), ptr(s), ptr(g), ptr(mean), ptr(rstd), ptr(da), ptr(dgamma),
-                                           ptr(dbeta), ptr(ws), acc, rows, width, dt, stream_ptr(s.device)),
-                  "hs_add_layernorm_bwd")
-            db = da
-        else:
-            _, rps, p, seed = extras
-            db = torch.empty_like(s)
-            check(lib.hs_add_layernorm_drop_bwd(ptr(dy), ptr(ds_c), ptr(s), ptr(g), ptr(mean), ptr(rstd), ptr(da), ptr(db),
-                                                ptr(dgamma), ptr(dbeta), ptr(ws), acc, ptr(rs), rps, p, seed, rows, width,
-                                                dt, stream_ptr(s.device)), "hs_add_layernorm_drop_bwd")
-        if acc & _lib.HS_ACC_DEFER:
-            _defer_keep(s.device, ws)
-        dw, dbias = _norm_param_result(weight, bias, dgamma, dbeta, direct)
+        db = da if extras is None else torch.empty_like(s)  # (without extras the two operands have the same gradient)
+
+        def call(dgamma, dbeta, ws, acc):
+            if extras is None:
+                check(lib.hs_add_layernorm_bwd(ptr(dy), ptr(ds_c), ptr(s), ptr(g), ptr(mean), ptr(rstd), ptr(da), dgamma, dbeta, ws, acc,
+                                               rows, width, dt, stream_ptr(s.device)), "hs_add_layernorm_bwd")
+            else:
+                _, rps, p, seed = extras
+                check(lib.hs_add_layernorm_drop_bwd(ptr(dy), ptr(ds_c), ptr(s), ptr(g), ptr(mean), ptr(rstd), ptr(da), ptr(db), dgamma, dbeta,
+                                                    ws, acc, ptr(rs), rps, p, seed, rows, width, dt, stream_ptr(s.device)),
+                      "hs_add_layernorm_drop_bwd")
+
+        dw, dbias = _norm_backward(weight, bias, ctx.needs_input_grad[2] and ctx.needs_input_grad[3], rows, width, s.device, call)
         return da, db, dw, dbias, None, None, None
 
 

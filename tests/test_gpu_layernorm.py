@@ -4,9 +4,10 @@ Every reference is the plain formula in torch float64 on inputs rounded to the k
 beta, eps 1e-5, autograd for the gradients), evaluated on the device; outputs are held to TOL[dtype], gradients to GRAD_TOL[dtype]
 on max|a - b| / max|b|, the saved row statistics to 1e-5 of their scale.
 
-Dispatch of ln_fwd_impl / ln_bwd_impl.  `vector`: width % 8 == 0 (bf16) / width % 4 == 0 (fp32); `extras`: row_scale or drop_p;
-`lo`: the compensated stream operands.  Every parametrised case below carries in its id the (lanes per row, chunks per lane) shape
-that `with_shape` picks and the row of this table it is meant to reach.
+Dispatch of ln_fwd_impl / ln_bwd_impl (`fwd_path` / `bwd_path`, whose enumerators are the rows' names).  `vector`: width % 8 == 0
+(bf16) / width % 4 == 0 (fp32); `extras`: row_scale or drop_p; `lo`: the compensated stream operands.  Every parametrised case
+below carries in its id the (lanes per row, chunks per lane) shape that `with_shape` picks and the row of this table it is meant
+to reach.
 
   # forward
   #   fwd-fast-plain   layernorm_fwd_fast_kernel<EX = false>   vector, no extras, no lo                (plain, residual, add, passthrough)
