@@ -22,6 +22,15 @@ int hs::window_attn_check_shape(const char* who, int batch, int64_t n_tokens, in
 
 namespace {
 
+void fill_shape(hs::AttnParams& p, int batch, int64_t n_tokens, int channels, int num_heads, int window_size) {
+    p.B = batch;
+    p.N = n_tokens;
+    p.C = channels;
+    p.nH = num_heads;
+    p.Ws = window_size;
+    p.hd = channels / num_heads;
+}
+
 int fill_params(hs::AttnParams& p, const void* qkv, void* out, float* lse, const float* bias, const float* head_scale,
                 const int32_t* idx, int64_t roll, const uint8_t* labels, int batch, int64_t n_tokens, int channels,
                 int num_heads, int window_size, unsigned flags, float attn_drop, uint64_t seed, int dtype) {
@@ -40,14 +49,18 @@ int fill_params(hs::AttnParams& p, const void* qkv, void* out, float* lse, const
     p.idx = idx;
     p.roll = idx ? 0 : roll;
     p.labels = labels;
-    p.B = batch;
-    p.N = n_tokens;
-    p.C = channels;
-    p.nH = num_heads;
-    p.Ws = window_size;
-    p.hd = channels / num_heads;
+    fill_shape(p, batch, n_tokens, channels, num_heads, window_size);
     p.flags = flags;
     return HS_OK;
+}
+
+// Which kernels serve a shape: the MFMA paths (Ws = 64, head_dim = 32; bf16 and fp32 I/O) unless HS_ATTN_FORCE_VALU asks for the
+// fp32-VALU path, which also takes everything else
+enum class Route { kMfmaBf16, kMfmaF32, kGeneric };
+Route route_of(const hs::AttnParams& p, int dtype, unsigned flags) {
+    if (flags & HS_ATTN_FORCE_VALU) return Route::kGeneric;
+    if (hs::attn_mfma_supported(p, dtype)) return Route::kMfmaBf16;
+    return hs::attn_mfma_f32_supported(p, dtype) ? Route::kMfmaF32 : Route::kGeneric;
 }
 
 }  // namespace
@@ -63,23 +76,22 @@ int hs_window_attn_fwd(const void* qkv, void* out, float* lse, const float* bias
                              window_size, flags, attn_drop, seed, dtype))
         return st;
     hipStream_t s = (hipStream_t)stream;
-    const bool valu = (flags & HS_ATTN_FORCE_VALU) != 0;
-    if (!valu && hs::attn_mfma_supported(p, dtype)) return hs::launch_attn_fwd_mfma(p, s);
-    if (!valu && hs::attn_mfma_f32_supported(p, dtype)) return hs::launch_attn_fwd_mfma_f32(p, s);
-    return hs::launch_attn_fwd_generic(p, dtype, s);
+    switch (route_of(p, dtype, flags)) {
+        case Route::kMfmaBf16: return hs::launch_attn_fwd_mfma(p, s);
+        case Route::kMfmaF32: return hs::launch_attn_fwd_mfma_f32(p, s);
+        default: return hs::launch_attn_fwd_generic(p, dtype, s);
+    }
 }
 
 int64_t hs_window_attn_bwd_workspace(int batch, int64_t n_tokens, int channels, int num_heads, int window_size, int dtype) {
     hs::AttnParams p{};
     if (batch <= 0 || n_tokens <= 0 || channels <= 0 || num_heads <= 0 || window_size <= 0 || channels % num_heads) return 0;
-    p.B = batch;
-    p.N = n_tokens;
-    p.C = channels;
-    p.nH = num_heads;
-    p.Ws = window_size;
-    p.hd = channels / num_heads;
-    if (hs::attn_mfma_supported(p, dtype)) return hs::attn_bwd_mfma_workspace_floats(p);
-    return hs::attn_mfma_f32_supported(p, dtype) ? hs::attn_bwd_mfma_f32_workspace_floats(p) : 0;
+    fill_shape(p, batch, n_tokens, channels, num_heads, window_size);
+    switch (route_of(p, dtype, 0u)) {  // (the size an MFMA path would need, whether or not the call then forces the VALU path)
+        case Route::kMfmaBf16: return hs::attn_bwd_mfma_workspace_floats(p);
+        case Route::kMfmaF32: return hs::attn_bwd_mfma_f32_workspace_floats(p);
+        default: return 0;
+    }
 }
 
 int hs_window_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias,
@@ -98,15 +110,15 @@ int hs_window_attn_bwd(const void* qkv, const void* out, const void* dout, const
     p.dbias = bias ? dbias : nullptr;
     p.dhead_scale = (flags & HS_ATTN_COSINE) ? dhead_scale : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    const bool valu = (flags & HS_ATTN_FORCE_VALU) != 0;
-    if (!valu && hs::attn_mfma_supported(p, dtype)) return hs::launch_attn_bwd_mfma(p, workspace, s);
+    const Route route = route_of(p, dtype, flags);
+    if (route == Route::kMfmaBf16) return hs::launch_attn_bwd_mfma(p, workspace, s);
     // HS_ATTN_OVERWRITE_GRADS is a contract of the ENTRY POINT: the bf16 MFMA path writes dbias / dhead_scale, every other path
     // accumulates -- so a caller that set the flag (and handed over uninitialised buffers) gets them zeroed here first
     if (flags & HS_ATTN_OVERWRITE_GRADS) {
         if (p.dbias) HS_HIP_CHECK(hipMemsetAsync(p.dbias, 0, sizeof(float) * (size_t)num_heads * window_size * window_size, s));
         if (p.dhead_scale) HS_HIP_CHECK(hipMemsetAsync(p.dhead_scale, 0, sizeof(float) * (size_t)num_heads, s));
     }
-    if (!valu && hs::attn_mfma_f32_supported(p, dtype)) return hs::launch_attn_bwd_mfma_f32(p, workspace, s);
+    if (route == Route::kMfmaF32) return hs::launch_attn_bwd_mfma_f32(p, workspace, s);
     return hs::launch_attn_bwd_generic(p, dtype, s);
 }
 

@@ -8,13 +8,12 @@
 // in LDS (row stride HD+1 floats: conflict-free both for the broadcast reads of the score loop and for
 // the per-thread row writes); every thread keeps its own query row, running max/sum and output row
 // in registers and walks the window's keys with an online softmax, four keys per rescale.
-#include "window_attn.h"
+#include "window_attn_device.h"
 
 namespace hs {
 HS_DEFINE_SEED_EPOCH_SETTER(set_seed_epoch_attn_generic)
 namespace {
 
-constexpr float kNormEps = 1e-12f;   // F.normalize eps, swin_hp_transformer.py:143
 constexpr float kMaskValue = -100.f; // hp_shifting.py:25
 
 template <typename T, int HD>

@@ -25,7 +25,7 @@
 // in the backward -- come from the same tiles through ds_read_b64_tr_b16, the hardware 4x16 transpose).
 // Cosine attention: k rows are L2-normalised while being staged; the query norm and the head's logit scale are one
 // per-lane factor applied to the fp32 scores.
-#include "window_attn.h"
+#include "window_attn_device.h"
 
 // HS_ATTN_STORE_AUX (measurement builds): cache policy of the row stores of O / dQ / dK / dV (gfx950: bit 1 = nt); see csrc/gemm_nt.hip
 #ifndef HS_ATTN_STORE_AUX
@@ -49,19 +49,8 @@ namespace hs {
 HS_DEFINE_SEED_EPOCH_SETTER(set_seed_epoch_attn_mfma)
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 constexpr int kWs = 64, kHd = 32;
 constexpr int kTileBytes = kWs * kHd * 2;  // 4096: [64][32] bf16, rows of 64 B = 4 chunks of 16 B
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kNormEps = 1e-12f;
-// 1 / max(|x|, eps) from the squared norm: v_rsq_f32 (1 ulp) + a clamp instead of the correctly rounded sqrt and division hipcc
-// expands to ~20 instructions each -- four of them per row block were half of what cosine attention added to the kernels' VALU
-// count (profiles/r05_attn_pmc_T256_vs_D256.txt: 66 vs 37 VALU per MFMA in the forward); results are bf16 rows
-__device__ __forceinline__ float inv_norm(float sumsq) { return fminf(__builtin_amdgcn_rsqf(sumsq), 1.f / kNormEps); }
-constexpr float kMaskLog2 = -100.f * kLog2e;
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
@@ -93,6 +82,117 @@ __device__ __forceinline__ bf16x8 join(s16x4 a, s16x4 b) {
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     return __builtin_bit_cast(bf16x8, v);
+}
+
+// ================================================================================================ shared by both kernels
+// blockIdx.x -> (window slot bx, head group by): the head groups of a window slot share an XCD (blocks go round-robin over 8 XCDs)
+struct BlockSlot {
+    int by, bx;
+    __device__ __forceinline__ explicit BlockSlot(int groups) {
+        const int bxcd = blockIdx.x & 7, blocal = blockIdx.x >> 3;
+        by = blocal % groups;
+        bx = bxcd + 8 * (blocal / groups);
+    }
+};
+
+// Staging geometry: the workgroup's threads move whole token rows of HG*64 B, 16 B per thread: thread -> row srow of a pass, head sg
+// inside the group, 16-byte chunk scc of that head's 64 B, byte column colb of the q slice.  Built from an opaque copy of the thread
+// id (`tid`, for whatever else a use site derives per lane) at every use site: hoisted, the per-thread addresses would be pinned
+// in registers for the whole kernel.
+template <int HG>
+struct StageGeometry {
+    int tid, srow, sg, scc;
+    uint32_t colb;
+    __device__ __forceinline__ StageGeometry(int tid_, int by) : tid(tid_) {
+        asm volatile("" : "+v"(tid));
+        srow = tid / (4 * HG);
+        const int sc = tid % (4 * HG);
+        sg = sc >> 2;
+        scc = sc & 3;
+        colb = (uint32_t)(by * HG * kHd + sc * 8) * 2u;
+    }
+};
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const void* base, uint32_t bytes_per_image, int b_l) {
+    const uint64_t a = (uint64_t)base + (uint64_t)b_l * bytes_per_image;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, (int)bytes_per_image, 0x00020000);
+}
+// natural-order token (inside its image) of shifted row j, without a table
+__device__ __forceinline__ int rolled(int j, int roll, int N) {
+    const int s = j + roll;
+    return s >= N ? s - N : s;
+}
+// (image, window) of the same slot's next window, without a division
+__device__ __forceinline__ void advance_window(int& b_l, int& w_l, int slots, int nW) {
+    w_l += slots;
+    while (w_l >= nW) {
+        w_l -= nW;
+        ++b_l;
+    }
+}
+__device__ __forceinline__ void lds_barrier() {  // orders LDS traffic only: global loads and stores stay in flight
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+// The prefetch step: request the rows of window (b_l, w_l) and, in table mode, the token rows of the window after it
+template <class IssueLoads, class RequestTokens>
+__device__ __forceinline__ void prefetch_window(int b_l, int w_l, int slots, int nW, int B, bool has_idx, IssueLoads&& issue_loads,
+                                                RequestTokens&& request_tokens) {
+    issue_loads(b_l, w_l);
+    if (has_idx) {
+        advance_window(b_l, w_l, slots, nW);
+        if (b_l < B) request_tokens(w_l);
+    }
+}
+
+// Cosine attention while staging: the 4 threads of a (row, head) hold 16 B of q and of k each; k is rescaled to unit length
+__device__ __forceinline__ void normalise_key_row(const u32x4& vq, u32x4& vk, float& qinv, float& kinv) {
+    float sq = 0.f, sk = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        sq += bf_lo(vq[i]) * bf_lo(vq[i]) + bf_hi(vq[i]) * bf_hi(vq[i]);
+        sk += bf_lo(vk[i]) * bf_lo(vk[i]) + bf_hi(vk[i]) * bf_hi(vk[i]);
+    }
+    sq += __shfl_xor(sq, 1, 64);
+    sq += __shfl_xor(sq, 2, 64);
+    sk += __shfl_xor(sk, 1, 64);
+    sk += __shfl_xor(sk, 2, 64);
+    kinv = inv_norm(sk);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) vk[i] = pack_bf16(bf_lo(vk[i]) * kinv, bf_hi(vk[i]) * kinv);
+    qinv = inv_norm(sq);
+}
+// Label scan, by the one wave that loaded the window's 64 labels: the labels and "more than one label" (wave-uniform) to LDS
+__device__ __forceinline__ void stage_labels(unsigned char* lab_s, uint32_t* flag_s, unsigned lab, int lane) {
+    lab_s[lane] = (unsigned char)lab;
+    const unsigned first = __builtin_amdgcn_readfirstlane(lab);
+    const bool any = __ballot(lab != first) != 0ull;
+    if (lane == 0) flag_s[0] = any ? 1u : 0u;
+}
+// Bias of one (query row, key tile) in the S^T accumulator layout: src points at key kappa(0, half) of the query's row, register r
+// gets key kappa(r, half) times `scale`.  The loads are unconditional (without a bias the kernels point src at qkv bytes and pass
+// scale 0); load and scaled are separate so that a kernel can keep the loads in flight across its MFMAs.
+struct BiasTile {
+    float4 raw[4];
+    __device__ __forceinline__ void load(const float* src) {
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) raw[rg] = *(const float4*)(src + 8 * rg);
+    }
+    __device__ __forceinline__ void scaled(float scale, float (&out)[16]) const {
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+            out[4 * rg] = raw[rg].x * scale;
+            out[4 * rg + 1] = raw[rg].y * scale;
+            out[4 * rg + 2] = raw[rg].z * scale;
+            out[4 * rg + 3] = raw[rg].w * scale;
+        }
+    }
+};
+__device__ __forceinline__ void load_bias_tile(const float* src, float scale, float (&out)[16]) {
+    BiasTile t;
+    t.load(src);
+    t.scaled(scale, out);
 }
 
 // ================================================================================================ backward
@@ -140,28 +240,6 @@ struct LdsLayoutBwd {
     }
 };
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-// 16 accumulator values of a transposed output tile (lane = token, register r = feature (r&3) + 8*(r>>2) + 4*half) -> two
-// 16-byte pieces of the token's 64-byte head slice: lanes < 32 hold bytes [0,16) and [32,48), lanes >= 32 bytes [16,32) and [48,64)
-__device__ __forceinline__ void pack_rows_t(const float (&v)[16], u32x4& p0, u32x4& p1) {
-    uint32_t w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-    // groups m = 0..3 are dwords (2m, 2m+1); pair (0,1) and pair (2,3): vdst = group m, src = group m+1
-#pragma unroll
-    for (int m = 0; m < 4; m += 2)
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            const auto r = __builtin_amdgcn_permlane32_swap(w[2 * m + d], w[2 * m + 2 + d], false, false);
-            w[2 * m + d] = r[0];
-            w[2 * m + 2 + d] = r[1];
-        }
-    p0 = u32x4{w[0], w[1], w[2], w[3]};
-    p1 = u32x4{w[4], w[5], w[6], w[7]};
-}
-
 template <int HG, bool DROP, bool COS>
 __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p, float* __restrict__ dbias_part,
                                                                  float* __restrict__ dscale_part, int slots, int groups) {
@@ -170,8 +248,8 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
     const LdsLayoutBwd L(HG);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bxcd = blockIdx.x & 7, blocal = blockIdx.x >> 3;
-    const int by = blocal % groups, bx = bxcd + 8 * (blocal / groups);
+    const BlockSlot blk(groups);
+    const int by = blk.by, bx = blk.bx;
     if (bx >= slots) return;
     const int g = wv >> 1, t = wv & 1;  // head inside the group; query half (score phase) = key tile (dK / dV phase)
     const int half = lane >> 5, l31 = lane & 31;
@@ -206,28 +284,7 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
     uint32_t* flag_s = (uint32_t*)(smem + L.flag);
     const int qq = t * 32 + l31;  // this lane's query row (score phase) and key row (dK / dV phase)
 
-    // staging geometry: 128*HG threads move 32 rows x HG*64 B per pass, 2 passes per tile.  (Re-derived from an opaque copy
-    // of the thread id wherever it is used: hoisted, the per-thread addresses would be pinned in registers for the whole kernel.)
-#define HS_STAGE_GEOMETRY                                                                          \
-    int tid_o = tid;                                                                               \
-    asm volatile("" : "+v"(tid_o));                                                                \
-    const int srow = tid_o / (4 * HG), sc = tid_o % (4 * HG), sg = sc >> 2, scc = sc & 3;          \
-    const uint32_t colb = (uint32_t)(by * HG * kHd + sc * 8) * 2u;                                 \
-    unsigned char* st = smem + sg * L.head;                                                        \
-    (void)scc;                                                                                     \
-    (void)st;                                                                                      \
-    (void)colb;
-
-    auto image_rsrc = [&](const void* base, uint32_t bytes_per_image, int b_l) {
-        const uint64_t a = (uint64_t)base + (uint64_t)b_l * bytes_per_image;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, (int)bytes_per_image, 0x00020000);
-    };
-    // natural-order token (inside its image) of shifted row j, without a table
-    auto rolled = [&](int j) {
-        const int s = j + roll;
-        return s >= N ? s - N : s;
-    };
+    // (staging: 128*HG threads move 32 rows x HG*64 B per pass, 2 passes per tile -- StageGeometry, re-derived at every use site)
 
     // bias (x log2 e) and bias gradient of this wave's 32 queries, in the S^T accumulator layout, for the whole launch
     float bias2[2][16], dbacc[2][16];
@@ -241,40 +298,33 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
     unsigned lab_next = 0;
 
     int b_cur = bx / nW, w_cur = bx - b_cur * nW;  // (one 32-bit division per launch)
-    auto advance = [&](int& b_l, int& w_l) {
-        w_l += slots;
-        while (w_l >= nW) {
-            w_l -= nW;
-            ++b_l;
-        }
-    };
     auto request_tokens = [&](int w_l) {  // table mode: token rows of window w_l -> tok_ld2 / tok_st2 (loads)
-        HS_STAGE_GEOMETRY
+        const StageGeometry<HG> geo(tid, by);
         const int j_l = w_l * kWs;
-        tok_ld2[0] = p.idx[j_l + srow];
-        tok_ld2[1] = p.idx[j_l + 32 + srow];
+        tok_ld2[0] = p.idx[j_l + geo.srow];
+        tok_ld2[1] = p.idx[j_l + 32 + geo.srow];
         tok_st2 = p.idx[j_l + qq];
     };
     auto issue_loads = [&](int b_l, int w_l) {
-        HS_STAGE_GEOMETRY
+        const StageGeometry<HG> geo(tid, by);
         const int j_l = w_l * kWs;
         if (has_idx) {
             tok_ld[0] = tok_ld2[0];
             tok_ld[1] = tok_ld2[1];
             tok_st = tok_st2;
         } else {
-            tok_ld[0] = rolled(j_l + srow);
-            tok_ld[1] = rolled(j_l + 32 + srow);
-            tok_st = rolled(j_l + qq);
+            tok_ld[0] = rolled(j_l + geo.srow, roll, N);
+            tok_ld[1] = rolled(j_l + 32 + geo.srow, roll, N);
+            tok_st = rolled(j_l + qq, roll, N);
         }
         const __amdgpu_buffer_rsrc_t rq = image_rsrc(p.qkv, img_qkv, b_l), rd = image_rsrc(p.dout, img_do, b_l);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
-            const uint32_t vo = (uint32_t)tok_ld[rb] * c3b + colb;
+            const uint32_t vo = (uint32_t)tok_ld[rb] * c3b + geo.colb;
             ldq[rb] = __builtin_amdgcn_raw_buffer_load_b128(rq, vo, 0, HS_ATTN_LOAD_AUX_BWD);
             ldk[rb] = __builtin_amdgcn_raw_buffer_load_b128(rq, vo, cb, HS_ATTN_LOAD_AUX_BWD);
             ldv[rb] = __builtin_amdgcn_raw_buffer_load_b128(rq, vo, 2 * cb, HS_ATTN_LOAD_AUX_BWD);
-            lddo[rb] = __builtin_amdgcn_raw_buffer_load_b128(rd, (uint32_t)tok_ld[rb] * cb + colb, 0, HS_ATTN_LOAD_AUX_BWD);
+            lddo[rb] = __builtin_amdgcn_raw_buffer_load_b128(rd, (uint32_t)tok_ld[rb] * cb + geo.colb, 0, HS_ATTN_LOAD_AUX_BWD);
         }
         lse_next = p.lse[((int64_t)b_l * nH + h) * N + j_l + qq];
         if (p.labels && wv == 0) lab_next = p.labels[j_l + lane];
@@ -287,41 +337,21 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
         }
         asm volatile("" : "+v"(lse_next), "+v"(lab_next), "+v"(tok_ld2[0]), "+v"(tok_ld2[1]), "+v"(tok_st2));
     };
-    auto lds_barrier = [&]() {  // orders LDS traffic only: global loads and stores stay in flight
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
+    auto prefetch_from = [&](int b_l, int w_l) { prefetch_window(b_l, w_l, slots, nW, p.B, has_idx, issue_loads, request_tokens); };
 
     if (bx < total_windows) {
         if (has_idx) {
             request_tokens(w_cur);
             asm volatile("" : "+v"(tok_ld2[0]), "+v"(tok_ld2[1]), "+v"(tok_st2));
         }
-        if constexpr (!NOPIPE) {
-            issue_loads(b_cur, w_cur);
-            int b_n = b_cur, w_n = w_cur;
-            advance(b_n, w_n);
-            if (has_idx && b_n < p.B) request_tokens(w_n);
-        }
+        if constexpr (!NOPIPE) prefetch_from(b_cur, w_cur);
     }
     const bool has_bias = p.bias != nullptr;
     const float* bsrc = has_bias ? p.bias + ((int64_t)h * kWs + qq) * kWs + 4 * half : (const float*)p.qkv + 4 * half;
     const float bscale = has_bias ? kLog2e : 0.f;  // (unconditional loads: without a bias they read qkv bytes and are zeroed here)
     if constexpr (BIASREG) {
-        float4 b4[2][4];
 #pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) b4[kt][rg] = *(const float4*)(bsrc + kt * 32 + 8 * rg);
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                bias2[kt][4 * rg] = b4[kt][rg].x * bscale;
-                bias2[kt][4 * rg + 1] = b4[kt][rg].y * bscale;
-                bias2[kt][4 * rg + 2] = b4[kt][rg].z * bscale;
-                bias2[kt][4 * rg + 3] = b4[kt][rg].w * bscale;
-            }
+        for (int kt = 0; kt < 2; ++kt) load_bias_tile(bsrc + kt * 32, bscale, bias2[kt]);
     }
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
@@ -333,15 +363,13 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
         const int b = b_cur, w = w_cur;
         const int j0 = w * kWs;
         if constexpr (NOPIPE) {
-            issue_loads(b, w);
-            int b_n = b, w_n = w;
-            advance(b_n, w_n);
-            if (has_idx && b_n < p.B) request_tokens(w_n);  // (table mode: the NEXT window's token rows still travel one window ahead)
+            prefetch_from(b, w);  // (table mode: the NEXT window's token rows still travel one window ahead)
             claim();
         }
         const int tok_store = tok_st;  // this lane's token row of the current window
         const float lse_cur = lse_next;
-        HS_STAGE_GEOMETRY
+        const StageGeometry<HG> geo(tid, by);
+        unsigned char* st = smem + geo.sg * L.head;
         int lane_o = lane;
         asm volatile("" : "+v"(lane_o));  // (per-lane LDS addresses are re-derived per window instead of pinned in ~40 registers)
         const int half = lane_o >> 5, l31 = lane_o & 31;
@@ -349,37 +377,21 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
         const int lane = lane_o;
 
         // ------------------------------------------------------------ stage q, k^, v, dO; norms; label scan
-        if (p.labels && wv == 0) {
-            lab_s[lane] = (unsigned char)lab_next;
-            const unsigned first = __builtin_amdgcn_readfirstlane(lab_next);
-            const bool any = __ballot(lab_next != first) != 0ull;
-            if (lane == 0) flag_s[0] = any ? 1u : 0u;
-        }
+        if (p.labels && wv == 0) stage_labels(lab_s, flag_s, lab_next, lane);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
-            const int row = rb * 32 + srow;
+            const int row = rb * 32 + geo.srow;
             const u32x4 vq = ldq[rb];
             u32x4 vk = ldk[rb];
             if (cosine) {
-                float sq = 0.f, sk = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    sq += bf_lo(vq[i]) * bf_lo(vq[i]) + bf_hi(vq[i]) * bf_hi(vq[i]);
-                    sk += bf_lo(vk[i]) * bf_lo(vk[i]) + bf_hi(vk[i]) * bf_hi(vk[i]);
-                }
-                sq += __shfl_xor(sq, 1, 64);
-                sq += __shfl_xor(sq, 2, 64);
-                sk += __shfl_xor(sk, 1, 64);
-                sk += __shfl_xor(sk, 2, 64);
-                const float kinv = inv_norm(sk);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) vk[i] = pack_bf16(bf_lo(vk[i]) * kinv, bf_hi(vk[i]) * kinv);
-                if (scc == 0) {
-                    qinv_s[sg * kWs + row] = inv_norm(sq);
-                    kinv_s[sg * kWs + row] = kinv;
+                float qinv, kinv;
+                normalise_key_row(vq, vk, qinv, kinv);
+                if (geo.scc == 0) {
+                    qinv_s[geo.sg * kWs + row] = qinv;
+                    kinv_s[geo.sg * kWs + row] = kinv;
                 }
             }
-            const int off = swz(row, scc);
+            const int off = swz(row, geo.scc);
             *(u32x4*)(st + off) = vq;
             *(u32x4*)(st + kTileBytes + off) = vk;
             *(u32x4*)(st + 2 * kTileBytes + off) = ldv[rb];
@@ -389,16 +401,9 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
 
         // ------------------------------------------------------------ request the next window's rows (a whole window ahead)
         int b_n = b_cur, w_n = w_cur;
-        advance(b_n, w_n);
+        advance_window(b_n, w_n, slots, nW);
         auto prefetch = [&]() {
-            if (wi + slots < total_windows) {
-                issue_loads(b_n, w_n);
-                if (has_idx) {
-                    int b_nn = b_n, w_nn = w_n;
-                    advance(b_nn, w_nn);
-                    if (b_nn < p.B) request_tokens(w_nn);
-                }
-            }
+            if (wi + slots < total_windows) prefetch_from(b_n, w_n);
         };
         if constexpr (EARLY) prefetch();
         b_cur = b_n;
@@ -406,12 +411,10 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
         const bool mixed = p.labels ? (flag_s[0] != 0u) : false;  // wave-uniform (one LDS word)
 
         // ------------------------------------------------------------ S^T = K^ Q^T and dP^T = V dO^T for this wave's 32 queries
-        float4 biasv[2][4];
+        BiasTile biasv[2];
         if constexpr (!BIASREG) {  // in flight (L2) during the MFMAs below
 #pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) biasv[kt][rg] = *(const float4*)(bsrc + kt * 32 + 8 * rg);
+            for (int kt = 0; kt < 2; ++kt) biasv[kt].load(bsrc + kt * 32);
         }
         f32x16 accS[2], accP[2];
 #pragma unroll
@@ -445,14 +448,7 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
         const DropRng rng(p, ((int64_t)b * nH + h) * N + j0 + qq);
         if constexpr (!BIASREG) {
 #pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) {
-                    bias2[kt][4 * rg] = biasv[kt][rg].x * bscale;
-                    bias2[kt][4 * rg + 1] = biasv[kt][rg].y * bscale;
-                    bias2[kt][4 * rg + 2] = biasv[kt][rg].z * bscale;
-                    bias2[kt][4 * rg + 3] = biasv[kt][rg].w * bscale;
-                }
+            for (int kt = 0; kt < 2; ++kt) biasv[kt].scaled(bscale, bias2[kt]);
         }
         float dsum = 0.f, s_pds = 0.f, s_ps = 0.f;
         uint32_t keepbits = 0u;
@@ -474,11 +470,11 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
                     const float sraw = accS[kt][r];
                     float tt = fmaf(sraw, fq2, bias2[kt][r]);
                     if constexpr (MASKED)
-                        if (lab_s[kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] != mylab) tt += kMaskLog2;
+                        if (lab_s[kt * 32 + kappa(r, half)] != mylab) tt += kMaskLog2;
                     const float pr = __builtin_amdgcn_exp2f(tt + nlse2);
                     float dpv = accP[kt][r];
                     if constexpr (DROP) {  // the keep bit is kept for pass 2 (the mask is evaluated once per probability)
-                        const float mk = rng.mult_half(kt * 32 + (r & 3) + 8 * (r >> 2), half);
+                        const float mk = rng.mult_half(kt * 32 + kappa(r, 0), half);
                         keepbits |= (mk != 0.f ? 1u : 0u) << (kt * 16 + r);
                         dpv *= mk;
                     }
@@ -549,9 +545,6 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
                 const u32x4 bw = {pS[kt][4 * c], pS[kt][4 * c + 1], pS[kt][4 * c + 2], pS[kt][4 * c + 3]};
                 xt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ak, __builtin_bit_cast(bf16x8, bw), xt, 0, 0, 0);
             }
-            float x[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) x[r] = xt[r];
             if (cosine) {  // dq = X - q^ (q^ . X): features 8m + 4*half .. +3 of the raw q row are one 8-byte LDS read
                 float qv[16];
 #pragma unroll
@@ -564,14 +557,14 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
                 }
                 float pq = 0.f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) pq = fmaf(x[r], qv[r], pq);
+                for (int r = 0; r < 16; ++r) pq = fmaf(xt[r], qv[r], pq);
                 pq += __shfl_xor(pq, 32, 64);
                 pq *= qinv * qinv;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) x[r] = fmaf(-qv[r], pq, x[r]);
+                for (int r = 0; r < 16; ++r) xt[r] = fmaf(-qv[r], pq, xt[r]);
             }
             u32x4 p0, p1;
-            pack_rows_t(x, p0, p1);
+            pack_rows_t(xt, p0, p1);
             __builtin_amdgcn_raw_buffer_store_b128(p0, rdq, vst, 0, HS_ATTN_STORE_AUX);
             __builtin_amdgcn_raw_buffer_store_b128(p1, rdq, vst + 32u, 0, HS_ATTN_STORE_AUX);
         }
@@ -597,9 +590,6 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
                 const bf16x8 bp = join(tr_read_scratch(scr_p, qrow, t, lane), tr_read_scratch(scr_p, qrow + 4, t, lane));
                 vt_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, bp, vt_acc, 0, 0, 0);
             }
-            float x[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) x[r] = kt_acc[r];
             if (cosine) {  // dk = (dK^ - k^ (k^ . dK^)) / |k|   (the K tile holds the normalised rows)
                 float kv[16];
 #pragma unroll
@@ -612,16 +602,14 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
                 }
                 float pk = 0.f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) pk = fmaf(x[r], kv[r], pk);
+                for (int r = 0; r < 16; ++r) pk = fmaf(kt_acc[r], kv[r], pk);
                 pk += __shfl_xor(pk, 32, 64);
                 const float kinv = kinv_s[g * kWs + qq];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) x[r] = fmaf(-kv[r], pk, x[r]) * kinv;
+                for (int r = 0; r < 16; ++r) kt_acc[r] = fmaf(-kv[r], pk, kt_acc[r]) * kinv;
             }
-            pack_rows_t(x, k0, k1);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) x[r] = vt_acc[r];
-            pack_rows_t(x, v0, v1);
+            pack_rows_t(kt_acc, k0, k1);
+            pack_rows_t(vt_acc, v0, v1);
         }
         // The prefetched rows (requested a whole window ago, long landed) are claimed HERE, in front of the last stores: vmcnt
         // counts loads and stores together and the two complete out of order, so a wait for the rows at the top of the next
@@ -649,7 +637,6 @@ __global__ void __launch_bounds__(128 * HG, 2) attn_bwd_mfma_kernel(AttnParams p
         if (lane == 0) dscale_part[((int64_t)bx * nH + h) * 2 + t] = tot;
     }
 }
-#undef HS_STAGE_GEOMETRY
 
 // ================================================================================================ forward
 // The output product is transposed like the backward's (O^T = V^T P^T: lane = query, registers = features, each
@@ -674,8 +661,8 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
     const LdsLayoutFwd L(HG);
     const int tid = threadIdx.x, lane = tid & 63;
     const int g = __builtin_amdgcn_readfirstlane(tid >> 6);  // head inside the group
-    const int bxcd = blockIdx.x & 7, blocal = blockIdx.x >> 3;
-    const int by = blocal % groups, bx = bxcd + 8 * (blocal / groups);
+    const BlockSlot blk(groups);
+    const int by = blk.by, bx = blk.bx;
     if (bx >= slots) return;
     const int half = lane >> 5, l31 = lane & 31;
     const int h = by * HG + g;
@@ -697,53 +684,24 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
     unsigned char* lab_s = smem + L.lab;
     uint32_t* flag_s = (uint32_t*)(smem + L.flag);
 
-    // staging geometry: 12 steps = 3 parts (q, k, v) x 4 row blocks of 16 rows; a step moves 16 rows x HG*64 B.  (Re-derived
-    // from an opaque copy of the thread id wherever it is used instead of being pinned in registers for the whole kernel.)
-#define HS_STAGE_GEOMETRY                                                                          \
-    int tid_o = tid;                                                                               \
-    asm volatile("" : "+v"(tid_o));                                                                \
-    const int srow = tid_o / (4 * HG), sc = tid_o % (4 * HG), sg = sc >> 2, scc = sc & 3;          \
-    const uint32_t colb = (uint32_t)(by * HG * kHd + sc * 8) * 2u;                                 \
-    unsigned char* st = smem + sg * L.head;                                                        \
-    const int l31 = tid_o & 31;                                                                    \
-    (void)scc;                                                                                     \
-    (void)st;                                                                                      \
-    (void)colb;                                                                                    \
-    (void)l31;
-
-    auto image_rsrc = [&](const void* base, uint32_t bytes_per_image, int b_l) {
-        const uint64_t a = (uint64_t)base + (uint64_t)b_l * bytes_per_image;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, (int)bytes_per_image, 0x00020000);
-    };
-    auto rolled = [&](int j) {
-        const int s = j + roll;
-        return s >= N ? s - N : s;
-    };
-
+    // staging: 12 steps = 3 parts (q, k, v) x 4 row blocks of 16 rows; a step moves 16 rows x HG*64 B (StageGeometry, re-derived
+    // at every use site)
     u32x4 ld[3][4];
     int tok_ld[4] = {0, 0, 0, 0}, tok_st[2] = {0, 0};
     int tok_ld2[4] = {0, 0, 0, 0}, tok_st2[2] = {0, 0};  // table mode: token rows of the window after the one in flight
     unsigned lab_next = 0;
     int b_cur = bx / nW, w_cur = bx - b_cur * nW;
-    auto advance = [&](int& b_l, int& w_l) {
-        w_l += slots;
-        while (w_l >= nW) {
-            w_l -= nW;
-            ++b_l;
-        }
-    };
     auto request_tokens = [&](int w_l) {
-        HS_STAGE_GEOMETRY
-        const int j_l = w_l * kWs;
+        const StageGeometry<HG> geo(tid, by);
+        const int j_l = w_l * kWs, l31 = geo.tid & 31;
 #pragma unroll
-        for (int rb = 0; rb < 4; ++rb) tok_ld2[rb] = p.idx[j_l + rb * 16 + srow];
+        for (int rb = 0; rb < 4; ++rb) tok_ld2[rb] = p.idx[j_l + rb * 16 + geo.srow];
         tok_st2[0] = p.idx[j_l + l31];
         tok_st2[1] = p.idx[j_l + 32 + l31];
     };
     auto issue_loads = [&](int b_l, int w_l) {
-        HS_STAGE_GEOMETRY
-        const int j_l = w_l * kWs;
+        const StageGeometry<HG> geo(tid, by);
+        const int j_l = w_l * kWs, l31 = geo.tid & 31;
         if (has_idx) {
 #pragma unroll
             for (int rb = 0; rb < 4; ++rb) tok_ld[rb] = tok_ld2[rb];
@@ -751,14 +709,14 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
             tok_st[1] = tok_st2[1];
         } else {
 #pragma unroll
-            for (int rb = 0; rb < 4; ++rb) tok_ld[rb] = rolled(j_l + rb * 16 + srow);
-            tok_st[0] = rolled(j_l + l31);
-            tok_st[1] = rolled(j_l + 32 + l31);
+            for (int rb = 0; rb < 4; ++rb) tok_ld[rb] = rolled(j_l + rb * 16 + geo.srow, roll, N);
+            tok_st[0] = rolled(j_l + l31, roll, N);
+            tok_st[1] = rolled(j_l + 32 + l31, roll, N);
         }
         const __amdgpu_buffer_rsrc_t rq = image_rsrc(p.qkv, img_qkv, b_l);
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb) {
-            const uint32_t vo = (uint32_t)tok_ld[rb] * c3b + colb;
+            const uint32_t vo = (uint32_t)tok_ld[rb] * c3b + geo.colb;
             ld[0][rb] = __builtin_amdgcn_raw_buffer_load_b128(rq, vo, 0, HS_ATTN_LOAD_AUX_FWD);
             ld[1][rb] = __builtin_amdgcn_raw_buffer_load_b128(rq, vo, cb, HS_ATTN_LOAD_AUX_FWD);
             ld[2][rb] = __builtin_amdgcn_raw_buffer_load_b128(rq, vo, 2 * cb, HS_ATTN_LOAD_AUX_FWD);
@@ -773,46 +731,27 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
         asm volatile("" : "+v"(lab_next), "+v"(tok_ld2[0]), "+v"(tok_ld2[1]), "+v"(tok_ld2[2]), "+v"(tok_ld2[3]), "+v"(tok_st2[0]),
                      "+v"(tok_st2[1]));
     };
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
+    auto prefetch_from = [&](int b_l, int w_l) { prefetch_window(b_l, w_l, slots, nW, p.B, has_idx, issue_loads, request_tokens); };
 
     if (bx < total_windows) {
         if (has_idx) {
             request_tokens(w_cur);
             asm volatile("" : "+v"(tok_ld2[0]), "+v"(tok_ld2[1]), "+v"(tok_ld2[2]), "+v"(tok_ld2[3]), "+v"(tok_st2[0]), "+v"(tok_st2[1]));
         }
-        issue_loads(b_cur, w_cur);
-        int b_n = b_cur, w_n = w_cur;
-        advance(b_n, w_n);
-        if (has_idx && b_n < p.B) request_tokens(w_n);
+        prefetch_from(b_cur, w_cur);
     }
 
     // relative-position bias of this head (x log2 e), in the S^T accumulator layout: tile (kt, qt), register r holds query
-    // qt*32 + l31, key kt*32 + (r&3) + 8*(r>>2) + 4*half.  Unconditional loads (without a bias they read qkv bytes, zeroed below).
+    // qt*32 + l31, key kt*32 + kappa(r, half).  Unconditional loads (without a bias they read qkv bytes, zeroed by the scale).
     float biasr[2][2][16];
     {
         const bool has_bias = p.bias != nullptr;
         const float* bsrc = has_bias ? p.bias + ((int64_t)h * kWs + l31) * kWs + 4 * half : (const float*)p.qkv + 4 * half;
         const float bs = has_bias ? kLog2e : 0.f;
 #pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-            float4 b4[2][4];
+        for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-            for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) b4[qt][m] = *(const float4*)(bsrc + (has_bias ? qt * 32 * kWs : 0) + kt * 32 + 8 * m);
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    biasr[kt][qt][4 * m] = b4[qt][m].x * bs;
-                    biasr[kt][qt][4 * m + 1] = b4[qt][m].y * bs;
-                    biasr[kt][qt][4 * m + 2] = b4[qt][m].z * bs;
-                    biasr[kt][qt][4 * m + 3] = b4[qt][m].w * bs;
-                }
-        }
+            for (int qt = 0; qt < 2; ++qt) load_bias_tile(bsrc + (has_bias ? qt * 32 * kWs : 0) + kt * 32, bs, biasr[kt][qt]);
     }
     claim();
 
@@ -820,39 +759,24 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
         const int b = b_cur, w = w_cur;
         const int j0 = w * kWs;
         const int tq0 = tok_st[0], tq1 = tok_st[1];
-        HS_STAGE_GEOMETRY
-        const int half = tid_o >> 5 & 1;
-        const int lane = tid_o & 63;
+        const StageGeometry<HG> geo(tid, by);
+        unsigned char* st = smem + geo.sg * L.head;
+        const int half = geo.tid >> 5 & 1, l31 = geo.tid & 31;
+        const int lane = geo.tid & 63;
 
         // ------------------------------------------------------------ stage q, k^, v (row-major, swizzled); norms; label scan
-        if (p.labels && g == 0) {
-            lab_s[lane] = (unsigned char)lab_next;
-            const unsigned first = __builtin_amdgcn_readfirstlane(lab_next);
-            const bool any = __ballot(lab_next != first) != 0ull;
-            if (lane == 0) flag_s[0] = any ? 1u : 0u;
-        }
+        if (p.labels && g == 0) stage_labels(lab_s, flag_s, lab_next, lane);
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb) {
-            const int row = rb * 16 + srow;
+            const int row = rb * 16 + geo.srow;
             const u32x4 vq = ld[0][rb];
             u32x4 vk = ld[1][rb];
             if (cosine) {
-                float sq = 0.f, sk = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    sq += bf_lo(vq[i]) * bf_lo(vq[i]) + bf_hi(vq[i]) * bf_hi(vq[i]);
-                    sk += bf_lo(vk[i]) * bf_lo(vk[i]) + bf_hi(vk[i]) * bf_hi(vk[i]);
-                }
-                sq += __shfl_xor(sq, 1, 64);
-                sq += __shfl_xor(sq, 2, 64);
-                sk += __shfl_xor(sk, 1, 64);
-                sk += __shfl_xor(sk, 2, 64);
-                const float kinv = inv_norm(sk);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) vk[i] = pack_bf16(bf_lo(vk[i]) * kinv, bf_hi(vk[i]) * kinv);
-                if (scc == 0) qinv_s[sg * kWs + row] = inv_norm(sq);
+                float qinv, kinv;
+                normalise_key_row(vq, vk, qinv, kinv);
+                if (geo.scc == 0) qinv_s[geo.sg * kWs + row] = qinv;
             }
-            const int off = swz(row, scc);
+            const int off = swz(row, geo.scc);
             *(u32x4*)(st + off) = vq;
             *(u32x4*)(st + kTileBytes + off) = vk;
             *(u32x4*)(st + 2 * kTileBytes + off) = ld[2][rb];
@@ -860,16 +784,9 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
         lds_barrier();  // A
 
         int b_n = b_cur, w_n = w_cur;
-        advance(b_n, w_n);
+        advance_window(b_n, w_n, slots, nW);
         auto prefetch = [&]() {
-            if (wi + slots < total_windows) {
-                issue_loads(b_n, w_n);
-                if (has_idx) {
-                    int b_nn = b_n, w_nn = w_n;
-                    advance(b_nn, w_nn);
-                    if (b_nn < p.B) request_tokens(w_nn);
-                }
-            }
+            if (wi + slots < total_windows) prefetch_from(b_n, w_n);
         };
         // (the dropout instantiation is at the register limit during the softmax: it requests the rows behind it)
         if constexpr (!DROP) prefetch();
@@ -917,9 +834,8 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                         float tv = fmaf(acc[kt][qt][r], fq, biasr[kt][qt][r]);
-                        if (lab_s[key] != my) tv += kMaskLog2;
+                        if (lab_s[kt * 32 + kappa(r, half)] != my) tv += kMaskLog2;
                         acc[kt][qt][r] = tv;
                         m = fmaxf(m, tv);
                     }
@@ -942,7 +858,7 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        acc[kt][qt][r] *= linv * rng.mult_half(kt * 32 + (r & 3) + 8 * (r >> 2), half);
+                        acc[kt][qt][r] *= linv * rng.mult_half(kt * 32 + kappa(r, 0), half);
             } else {
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt)
@@ -969,15 +885,8 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
             }
         }
         u32x4 o00, o01, o10, o11;
-        {
-            float x[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) x[r] = o[0][r];
-            pack_rows_t(x, o00, o01);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) x[r] = o[1][r];
-            pack_rows_t(x, o10, o11);
-        }
+        pack_rows_t(o[0], o00, o01);
+        pack_rows_t(o[1], o10, o11);
         // the next window's rows are claimed in front of the stores (see the backward)
         claim();
         const __amdgpu_buffer_rsrc_t ro = image_rsrc(p.out, img_out, b);
@@ -989,7 +898,6 @@ __global__ void __launch_bounds__(64 * HG, 2) attn_fwd_mfma_kernel(AttnParams p,
         lds_barrier();  // B: every wave is done with the tiles
     }
 }
-#undef HS_STAGE_GEOMETRY
 
 // dst[e] += sum over parts of src[part][e].  A block of 16 waves owns 256 consecutive elements (one float4 per lane); wave w sums
 // the parts p = w, w + 16, ... with all of its loads in flight at once, the 16 partial rows are combined through LDS in a fixed
@@ -1049,6 +957,19 @@ int persistent_slots(const AttnParams& p, int groups, int waves_per_wg) {
 int bwd_slots(const AttnParams& p, int hg) { return persistent_slots(p, p.nH / hg, 2 * hg); }  // two wavefronts per head
 int fwd_slots(const AttnParams& p, int hg) { return persistent_slots(p, p.nH / hg, hg); }
 
+// What every launch of a persistent kernel needs: the one-time opt-in to its dynamic LDS size, and the grid -- the slots rounded up
+// to whole rounds of the 8 XCDs, times the head groups (BlockSlot decodes it; the surplus blocks return at once)
+template <auto Kernel>
+int persistent_grid(int lds_bytes, int slots, int groups, unsigned& grid) {
+    static bool configured = false;
+    if (!configured) {
+        HS_HIP_CHECK(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        configured = true;
+    }
+    grid = 8u * (unsigned)((slots + 7) / 8) * (unsigned)groups;
+    return HS_OK;
+}
+
 // Heads per workgroup.  Forward (one wave per head): 4 where the head count allows (round 2: 2 / 1 heads per workgroup 3-7 % / 20 %
 // slower).  Backward (two waves per head): round 2 measured pairs ahead of four heads on the 5-barrier kernel (8-wave barriers);
 // with the 3-barrier kernel of round 4 FOUR heads per workgroup (8 waves, 137 KB of LDS, one workgroup per CU, 256-byte row
@@ -1071,16 +992,12 @@ int pick_head_group_bwd(const AttnParams& p) {
 template <int HG, bool DROP, bool COS>
 int launch_bwd(const AttnParams& p, float* workspace, hipStream_t stream) {
     const LdsLayoutBwd L(HG);
-    auto kern = attn_bwd_mfma_kernel<HG, DROP, COS>;
-    static bool configured = false;
-    if (!configured) {
-        HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-        configured = true;
-    }
+    constexpr auto kern = attn_bwd_mfma_kernel<HG, DROP, COS>;
     const int groups = p.nH / HG, slots = bwd_slots(p, HG);
+    unsigned grid;
+    if (int st = persistent_grid<kern>(L.total, slots, groups, grid)) return st;
     float* dbias_part = p.dbias ? workspace : nullptr;
     float* dscale_part = p.dhead_scale ? workspace + (int64_t)slots * p.nH * kWs * kWs : nullptr;
-    const unsigned grid = 8u * (unsigned)((slots + 7) / 8) * (unsigned)groups;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * HG), L.total, stream, p, dbias_part, dscale_part, slots, groups);
     HS_LAUNCH_CHECK("attn_bwd_mfma");
     if (dbias_part) {
@@ -1110,18 +1027,30 @@ int pick_head_group(const AttnParams& p) {
 template <int HG, bool DROP>
 int launch_fwd(const AttnParams& p, hipStream_t stream) {
     const LdsLayoutFwd L(HG);
-    auto kern = attn_fwd_mfma_kernel<HG, DROP>;
-    static bool configured = false;
-    if (!configured) {
-        HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-        configured = true;
-    }
-    const int groups = p.nH / HG;
-    const int slots = fwd_slots(p, HG);
-    const unsigned grid = 8u * (unsigned)((slots + 7) / 8) * (unsigned)groups;
+    constexpr auto kern = attn_fwd_mfma_kernel<HG, DROP>;
+    const int groups = p.nH / HG, slots = fwd_slots(p, HG);
+    unsigned grid;
+    if (int st = persistent_grid<kern>(L.total, slots, groups, grid)) return st;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * HG), L.total, stream, p, slots, groups);
     HS_LAUNCH_CHECK("attn_fwd_mfma");
     return HS_OK;
+}
+
+// f(std::integral_constant<int, HG>) for the head group a pick_head_group* returned: 1, 2, 3, 4 and, where MAX_HG allows, 8
+template <int MAX_HG, class F>
+int with_head_group(int hg, F&& f) {
+    if constexpr (MAX_HG >= 8)
+        if (hg == 8) return f(std::integral_constant<int, 8>{});
+    switch (hg) {
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return f(std::integral_constant<int, 1>{});
+    }
+}
+template <class F>
+int with_bool(bool v, F&& f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
 }
 
 }  // namespace
@@ -1138,31 +1067,20 @@ int64_t attn_bwd_mfma_workspace_floats(const AttnParams& p) {
 }
 
 int launch_attn_fwd_mfma(const AttnParams& p, hipStream_t stream) {
-    const bool drop = p.drop_p > 0.f;
-    switch (pick_head_group(p)) {
-        case 8: return drop ? launch_fwd<8, true>(p, stream) : launch_fwd<8, false>(p, stream);
-        case 4: return drop ? launch_fwd<4, true>(p, stream) : launch_fwd<4, false>(p, stream);
-        case 3: return drop ? launch_fwd<3, true>(p, stream) : launch_fwd<3, false>(p, stream);
-        case 2: return drop ? launch_fwd<2, true>(p, stream) : launch_fwd<2, false>(p, stream);
-        default: return drop ? launch_fwd<1, true>(p, stream) : launch_fwd<1, false>(p, stream);
-    }
-}
-
-template <int HG>
-int launch_bwd_hg(const AttnParams& p, float* workspace, hipStream_t stream) {
-    const bool drop = p.drop_p > 0.f, cos = (p.flags & HS_ATTN_COSINE) != 0;
-    if (cos) return drop ? launch_bwd<HG, true, true>(p, workspace, stream) : launch_bwd<HG, false, true>(p, workspace, stream);
-    return drop ? launch_bwd<HG, true, false>(p, workspace, stream) : launch_bwd<HG, false, false>(p, workspace, stream);
+    return with_head_group<8>(pick_head_group(p), [&](auto hg) {
+        return with_bool(p.drop_p > 0.f, [&](auto drop) { return launch_fwd<decltype(hg)::value, decltype(drop)::value>(p, stream); });
+    });
 }
 
 int launch_attn_bwd_mfma(const AttnParams& p, float* workspace, hipStream_t stream) {
     if (!workspace) return fail(HS_ERR_INVALID_ARG, "the MFMA backward needs a workspace (hs_window_attn_bwd_workspace)");
-    switch (pick_head_group_bwd(p)) {
-        case 4: return launch_bwd_hg<4>(p, workspace, stream);
-        case 3: return launch_bwd_hg<3>(p, workspace, stream);
-        case 2: return launch_bwd_hg<2>(p, workspace, stream);
-        default: return launch_bwd_hg<1>(p, workspace, stream);
-    }
+    return with_head_group<4>(pick_head_group_bwd(p), [&](auto hg) {
+        return with_bool(p.drop_p > 0.f, [&](auto drop) {
+            return with_bool((p.flags & HS_ATTN_COSINE) != 0, [&](auto cos) {
+                return launch_bwd<decltype(hg)::value, decltype(drop)::value, decltype(cos)::value>(p, workspace, stream);
+            });
+        });
+    });
 }
 
 }  // namespace hs

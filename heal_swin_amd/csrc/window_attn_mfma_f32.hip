@@ -16,23 +16,16 @@
 //            would halve the wavefronts per CU).
 // LDS tiles: row-major [64 tokens][32 features] fp32, row stride 36 floats (16-byte aligned rows; feature-indexed reads
 // of 32 consecutive rows are at most 2-way conflicted, token-row reads are conflict-free).
-#include "window_attn.h"
+#include "window_attn_device.h"
 
 namespace hs {
 HS_DEFINE_SEED_EPOCH_SETTER(set_seed_epoch_attn_mfma_f32)
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 constexpr int kWs = 64, kHd = 32;
 constexpr int kLd = 36;                 // floats per staged row
 constexpr int kTile = kWs * kLd;        // floats per tile
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kNormEps = 1e-12f;
-constexpr float kMaskLog2 = -100.f * kLog2e;
 
-__device__ __forceinline__ int kappa(int j, int half) { return (j & 3) + 8 * (j >> 2) + 4 * half; }
 __device__ __forceinline__ f32x16 mfma2(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ void zero(f32x16& v) {
 #pragma unroll

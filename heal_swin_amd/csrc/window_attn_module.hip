@@ -37,27 +37,17 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "window_attn.h"
+#include "window_attn_device.h"
 
 namespace hs {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef unsigned int u32x2v __attribute__((__vector_size__(8)));
 typedef unsigned int u32x4v __attribute__((__vector_size__(16)));
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kWs = 64;
 constexpr int kRowB = 256;  // bytes per LDS tile row (C <= 128 bf16; rows of C = 96 are padded)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kNormEps = 1e-12f;
-// 1 / max(|x|, eps) from the squared norm: v_rsq_f32 (1 ulp) + a clamp instead of the correctly rounded sqrt and division hipcc
-// expands to ~20 instructions each -- four of them per row block were half of what cosine attention added to the kernels' VALU
-// count (profiles/r05_attn_pmc_T256_vs_D256.txt: 66 vs 37 VALU per MFMA in the forward); results are bf16 rows
-__device__ __forceinline__ float inv_norm(float sumsq) { return fminf(__builtin_amdgcn_rsqf(sumsq), 1.f / kNormEps); }
-constexpr float kMaskLog2 = -100.f * kLog2e;
 constexpr float kLnEps = 1e-5f;
 __device__ constexpr uint32_t kOob = 0x7FFFFF00u;
 
@@ -118,32 +108,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& a, int r0) {
                      pack_bf16x2(a[r0 + 6], a[r0 + 7])};
     return __builtin_bit_cast(bf16x8, v);
 }
-
-// 16 accumulator values of a transposed output tile (lane = token, register r = feature (r&3) + 8*(r>>2) + 4*half) -> two
-// 16-byte pieces of the token's 64-byte head slice: lanes < 32 hold bytes [0,16) and [32,48), lanes >= 32 bytes [16,32) and [48,64)
-// (v_permlane32_swap pairs the 8-byte pieces of the two lane halves)
-__device__ __forceinline__ void swap_rows_t(const uint32_t (&packed)[8], u32x4& p0, u32x4& p1) {  // packed[i] = registers 2i, 2i+1
-    uint32_t w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = packed[i];
-#pragma unroll
-    for (int m = 0; m < 4; m += 2)
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            const auto r = __builtin_amdgcn_permlane32_swap(w[2 * m + d], w[2 * m + 2 + d], false, false);
-            w[2 * m + d] = r[0];
-            w[2 * m + 2 + d] = r[1];
-        }
-    p0 = u32x4{w[0], w[1], w[2], w[3]};
-    p1 = u32x4{w[4], w[5], w[6], w[7]};
-}
-__device__ __forceinline__ void pack_rows_t(const f32x16& v, u32x4& p0, u32x4& p1) {
-    uint32_t w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-    swap_rows_t(w, p0, p1);
-}
-constexpr float kLn2 = 0.6931471805599453f;
 
 template <int NH, bool COS, bool TRAIN>
 __global__ void __launch_bounds__(NH * 64, 1) attn_module_fwd_kernel(ModParams p) {
