@@ -18,9 +18,7 @@
 // (A = weight rows from LDS) leaves the child's C channels of a token in ONE lane pair: LayerNorm statistics are in-register
 // sums plus one lane^32 exchange, the normalised registers are (after packing) the B operand of the head product, and the
 // logits of the row land in registers 0..7 of the same lane pair.  32 C / 16 + 4 C / 16 MFMAs per 32 pixel rows.
-#include <type_traits>
-
-#include "hs_device.h"
+#include "ln_head_device.h"
 #include "hs_depth_loss.h"
 
 // the target transform and the metric rules of TailDepthStep form their values unfused (their headers say why); everything else in
@@ -33,79 +31,11 @@
 namespace hs {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-constexpr float kEps = 1e-5f;
-constexpr int kKP = 16;     // class columns of the padded logits row
 constexpr int kP = 4;       // children per token (patch_size 4: every BASELINE config)
 constexpr int kRowB = 256;  // bytes per weight row in LDS (C <= 128 bf16; rows of C = 96 / 64 are padded)
 constexpr int kPatchRow = 128;
 
-__device__ __forceinline__ uint4 pack8f(const float* f) {
-    return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
-}
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
-// Optional fused loss (SURVEY 8f N2, the caller's CrossEntropyLoss(weight), models_lightning/segmentation/model_lightning_swin_hp.py:
-// 39-45, 104-111): the 16 logits of a pixel row sit in one lane pair, so log-sum-exp, the label's logit and the row's weighted
-// term are eight registers + one lane^32 exchange away; with `logits == nullptr` the [rows, 16] fp32 tensor is never written.
-struct TailCe {
-    const uint8_t* labels;  // [rows] class ids in pixel order (rows = (token, child)); ids >= n_classes are ignored (weight 0)
-    const float* class_w;   // [n_classes] or null (all ones)
-    float* loss_part;       // [4 * gridDim.x][2]: per-wave sums of w (lse - logit_y) and of w
-    int n_classes;
-};
-
-// ... or the depth caller's regression loss (hs_depth_loss.h; heal_swin/training/loss_depth_regression.py): a head of one or two
-// channels, i.e. accumulator registers 0 and 1 of the lane pair's half 0, against the row's fp32 target.  The kernel is a template
-// over the loss type, so the TailCe instantiation is the code it was before this epilogue existed.
-struct TailDepth {
-    const float* target;  // [rows] in pixel order; rows whose target is infinite are masked out
-    float* loss_part;     // [4 * gridDim.x][2]: per-wave sums of the depth term and of the kept rows
-    int kind;             // HS_DEPTH_*
-    float delta;          // huber delta
-};
-// ... or the segmentation caller's whole `shared_step` (model_lightning_swin_hp.py:104-111: argmax, weighted cross-entropy, IoU /
-// Accuracy on (preds, masks)): TailCe's loss with the same arithmetic in the same order, plus the row's class id
-// (torch.max(logits, 1): the first maximal class, a NaN counts as the maximum -- argmax_step of evaluation.hip) and the confusion
-// matrix behind the metrics (hs_seg_confusion's counting: labels >= n_classes stay out of the matrix and are counted in bad[0]).
-// A separate instantiation: TailCe and TailDepth compile to the code they were.
-struct TailCeStep {
-    const uint8_t* labels;     // as TailCe (never null here)
-    const float* class_w;
-    float* loss_part;
-    int n_classes;
-    uint8_t* preds;            // [rows] class ids, or null; 4-byte aligned (the 4 children of a token leave as one dword)
-    unsigned long long* conf;  // [n_classes][n_classes] (target, prediction) counts, added to; or null
-    unsigned long long* bad;   // [2]; [0] += rows whose label is >= n_classes (with conf)
-};
-// ... or the depth caller's whole `shared_step` (models_lightning/depth_estimation/model_lightning_depth_swin_hp.py:132-159: the loss
-// in the normalised space, unnormalize_and_retransform of prediction and target, DepthMSE / MeanSTD on them): TailDepth's loss with
-// the same arithmetic in the same order, plus the row's prediction in metres (target_op's inverse chain, hs_depth_target.h), the
-// HS_DEPTH_NSUMS float64 sums of hs_depth_metrics over (metres, target in metres, log variance) as per-lane sums that leave as one
-// record per workgroup (merged in a fixed order by depth_metrics::reduce_kernel: no float atomics), and the prediction itself.
-// A separate instantiation: the other three compile to the code they were.
-struct TailDepthStep {
-    const float* target;  // as TailDepth: the normalised target
-    float* loss_part;
-    int kind;
-    float delta;
-    int n_out;            // head channels: 1 or 2 (channel 1 = the log variance)
-    TargetOp inv;         // the inverse chain (HS_DT_INVERSE set)
-    depth_metrics::Rule rule;
-    double* partial;      // [gridDim.x][HS_DEPTH_NSUMS] or null (no metrics)
-    float* preds;         // [n_out][rows] fp32: channel 0 in metres, channel 1 the raw log variance; or null; 16-byte aligned
-    float* logvar_out;    // [rows]: channel 1 alone (read when preds is null); or null
-    int64_t rows;
-};
 constexpr int kHistBins = kKP * kKP;  // per-wave LDS histogram of TailCeStep: 16 x 16 uint32 bins = 1 KB
-
-__device__ __forceinline__ bool has_loss(const TailCe& ce) { return ce.labels != nullptr; }
-__device__ __forceinline__ bool has_loss(const TailDepth&) { return true; }
-__device__ __forceinline__ bool has_loss(const TailCeStep&) { return true; }
-__device__ __forceinline__ bool has_loss(const TailDepthStep&) { return true; }
 
 // torch.max(logits, 1)'s index over a row split between two lanes: (best, arg) is each lane's own result over its classes in
 // ascending order (argmax_step), `ob`, `oa` the partner's.  The first NaN wins, else the larger value, and on equal values the
@@ -117,6 +47,167 @@ __device__ __forceinline__ int argmax_merge(float best, int arg, float ob, int o
     return best > ob ? arg : (ob > best ? oa : lower);
 }
 
+// ---- The loss epilogues.  The kernel is a template over one of the four structs below and calls its row() once per pixel
+// row, with the row's 16 head outputs in registers 0..7 of the lane pair (class_natural) and TailLane for what the lane carries
+// from row to row; instantiations that do not touch a field of TailLane do not hold it.
+struct TailLane {
+    float num = 0.f, den = 0.f;  // the lane's part of the loss: numerator and denominator
+    uint32_t pred4 = 0;          // TailCeStep: the class ids of the token's 4 children, child p in byte p
+    uint32_t bad_rows = 0;       // TailCeStep: rows whose label is outside the matrix (wave-uniform: counted with ballots)
+    uint32_t* hist = nullptr;    // TailCeStep: the wave's LDS histogram
+    float4 m4, lv4;              // TailDepthStep: metres and log variance of the token's 4 children
+    double dsum[depth_metrics::kNSums];  // TailDepthStep: the lane's metric sums (half 0 lanes add, one row each)
+};
+
+// Optional fused loss (SURVEY 8f N2, the caller's CrossEntropyLoss(weight), models_lightning/segmentation/model_lightning_swin_hp.py:
+// 39-45, 104-111): the 16 logits of a pixel row sit in one lane pair, so log-sum-exp, the label's logit and the row's weighted
+// term are eight registers + one lane^32 exchange away; with `logits == nullptr` the [rows, 16] fp32 tensor is never written.
+struct TailCe {
+    const uint8_t* labels;  // [rows] class ids in pixel order (rows = (token, child)); ids >= n_classes are ignored (weight 0);
+                            // null: no loss
+    const float* class_w;   // [n_classes] or null (all ones)
+    float* loss_part;       // [4 * gridDim.x][2]: per-wave sums of w (lse - logit_y) and of w
+    int n_classes;
+    __device__ __forceinline__ bool has_loss() const { return labels != nullptr; }
+    // weighted cross-entropy of the row, from the fp32 logits in registers; leaves the lane's logits in v[], the label in yl
+    __device__ __forceinline__ bool ce_row(TailLane& st, const f32x16& lg, const float (&bk)[8], int64_t orow, bool live, int half,
+                                           float (&v)[8], int& yl) const {
+        if (!labels) return false;
+        float m = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            v[r] = lg[r] + bk[r];
+            if (class_natural(r, half) < n_classes) m = fmaxf(m, v[r]);
+        }
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        yl = live ? (int)labels[orow] : 255;
+        float ssum = 0.f, pick = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int cls = class_natural(r, half);
+            if (cls < n_classes) ssum += __builtin_amdgcn_exp2f((v[r] - m) * kLog2e);
+            pick = cls == yl ? v[r] : pick;
+        }
+        ssum += __shfl_xor(ssum, 32, 64);
+        pick += __shfl_xor(pick, 32, 64);  // (the other half holds 0)
+        const float wy = yl < n_classes ? (class_w ? class_w[yl] : 1.f) : 0.f;
+        if (half == 0) {
+            st.num = fmaf(wy, m + __builtin_amdgcn_logf(ssum) * kLn2 - pick, st.num);
+            st.den += wy;
+        }
+        return true;
+    }
+    __device__ __forceinline__ void row(TailLane& st, const f32x16& lg, const float (&bk)[8], int64_t orow, int, bool live,
+                                        int lane) const {
+        float v[8];
+        int yl;
+        ce_row(st, lg, bk, orow, live, lane >> 5, v, yl);
+    }
+};
+
+// ... or the segmentation caller's whole `shared_step` (model_lightning_swin_hp.py:104-111: argmax, weighted cross-entropy, IoU /
+// Accuracy on (preds, masks)): TailCe's loss, plus the row's class id (torch.max(logits, 1): the first maximal class, a NaN
+// counts as the maximum -- argmax_step of evaluation.hip) and the confusion matrix behind the metrics (hs_seg_confusion's
+// counting: labels >= n_classes stay out of the matrix and are counted in bad[0]).  labels is never null here.
+struct TailCeStep : TailCe {
+    uint8_t* preds;            // [rows] class ids, or null; 4-byte aligned (the 4 children of a token leave as one dword)
+    unsigned long long* conf;  // [n_classes][n_classes] (target, prediction) counts, added to; or null
+    unsigned long long* bad;   // [2]; [0] += rows whose label is >= n_classes (with conf)
+    __device__ __forceinline__ bool has_loss() const { return true; }
+    __device__ __forceinline__ void row(TailLane& st, const f32x16& lg, const float (&bk)[8], int64_t orow, int p, bool live,
+                                        int lane) const {
+        const int half = lane >> 5;
+        float v[8];
+        int yl;
+        if (!ce_row(st, lg, bk, orow, live, half, v, yl)) return;
+        float best = -INFINITY;  // (the lowest class wins over -inf by index; a lane without a class loses every tie)
+        int arg = 4 * half < n_classes ? 4 * half : 64;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {  // r ascending = class id ascending
+            const int cls = class_natural(r, half);
+            if (cls < n_classes && !(best != best) && (v[r] > best || v[r] != v[r])) {
+                best = v[r];
+                arg = cls;
+            }
+        }
+        const int pred = argmax_merge(best, arg, __shfl_xor(best, 32, 64), __shfl_xor(arg, 32, 64));
+        st.pred4 |= (uint32_t)pred << (8 * p);
+        if (conf) {  // (wave-uniform) one row per lane pair: half 0 counts it
+            const bool mine = live && half == 0;
+            const int bin = mine && yl < n_classes ? yl * n_classes + pred : -1;
+            st.bad_rows += (uint32_t)__popcll(__ballot(mine && yl >= n_classes));
+            // the lanes that share the first lane's bin (most of them in the uniform regions of a mask) add with one atomic
+            const int lead = __builtin_amdgcn_readfirstlane(bin);
+            const unsigned long long same = __ballot(bin == lead);
+            if (bin == lead) {
+                if (lead >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(&st.hist[lead], (uint32_t)__popcll(same));
+            } else if (bin >= 0) {
+                atomicAdd(&st.hist[bin], 1u);
+            }
+        }
+    }
+};
+
+// ... or the depth caller's regression loss (hs_depth_loss.h; heal_swin/training/loss_depth_regression.py): a head of one or two
+// channels, i.e. accumulator registers 0 and 1 of the lane pair's half 0, against the row's fp32 target.
+struct TailDepth {
+    const float* target;  // [rows] in pixel order; rows whose target is infinite are masked out
+    float* loss_part;     // [4 * gridDim.x][2]: per-wave sums of the depth term and of the kept rows
+    int kind;             // HS_DEPTH_*
+    float delta;          // huber delta
+    __device__ __forceinline__ bool has_loss() const { return true; }
+    // the depth term of the row; returns its target
+    __device__ __forceinline__ float depth_row(TailLane& st, const f32x16& lg, const float (&bk)[8], int64_t orow, bool live,
+                                               int half) const {
+        const float t = live && half == 0 ? target[orow] : INFINITY;
+        if (depth_keep(t)) {
+            st.num += depth_term(kind, delta, lg[0] + bk[0], lg[1] + bk[1], t);
+            st.den += 1.f;
+        }
+        return t;
+    }
+    __device__ __forceinline__ void row(TailLane& st, const f32x16& lg, const float (&bk)[8], int64_t orow, int, bool live,
+                                        int lane) const {
+        depth_row(st, lg, bk, orow, live, lane >> 5);
+    }
+};
+
+// ... or the depth caller's whole `shared_step` (models_lightning/depth_estimation/model_lightning_depth_swin_hp.py:132-159: the
+// loss in the normalised space, unnormalize_and_retransform of prediction and target, DepthMSE / MeanSTD on them): TailDepth's
+// loss, plus the row's prediction in metres (target_op's inverse chain, hs_depth_target.h), the HS_DEPTH_NSUMS float64 sums of
+// hs_depth_metrics over (metres, target in metres, log variance) as per-lane sums that leave as one record per workgroup
+// (merged in a fixed order by depth_metrics::reduce_kernel: no float atomics), and the prediction itself.
+struct TailDepthStep : TailDepth {
+    int n_out;            // head channels: 1 or 2 (channel 1 = the log variance)
+    TargetOp inv;         // the inverse chain (HS_DT_INVERSE set)
+    depth_metrics::Rule rule;
+    double* partial;      // [gridDim.x][HS_DEPTH_NSUMS] or null (no metrics)
+    float* preds;         // [n_out][rows] fp32: channel 0 in metres, channel 1 the raw log variance; or null; 16-byte aligned
+    float* logvar_out;    // [rows]: channel 1 alone (read when preds is null); or null
+    int64_t rows;
+    __device__ __forceinline__ void row(TailLane& st, const f32x16& lg, const float (&bk)[8], int64_t orow, int p, bool live,
+                                        int lane) const {
+        const int half = lane >> 5;
+        // (p0 and p1 are named before the loss term, as they always were here: with them the compiler contracts the log-variance
+        // term of this instantiation, d d (e / 2) + p1 / 2, into one fma, and TailDepth's not -- profiles/tail_refactor.txt)
+        const float p0 = lg[0] + bk[0], p1 = lg[1] + bk[1], t = depth_row(st, lg, bk, orow, live, half);
+        if (partial || preds) {  // (uniform) back to metres, as unnormalize_and_retransform on prediction and target
+#pragma clang fp contract(off)
+            const float m = target_op(p0, inv);
+            if (partial && live && half == 0)
+                depth_metrics::accumulate<float, float>(st.dsum, rule, m, target_op(t, inv), [&] { return p1; });
+            st.m4.x = p == 0 ? m : st.m4.x;  // (selects: an index would put the four values into scratch)
+            st.m4.y = p == 1 ? m : st.m4.y;
+            st.m4.z = p == 2 ? m : st.m4.z;
+            st.m4.w = p == 3 ? m : st.m4.w;
+        }
+        st.lv4.x = p == 0 ? p1 : st.lv4.x;
+        st.lv4.y = p == 1 ? p1 : st.lv4.y;
+        st.lv4.z = p == 2 ? p1 : st.lv4.z;
+        st.lv4.w = p == 3 ? p1 : st.lv4.w;
+    }
+};
+
 template <int NB, typename Loss>
 __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16_t* __restrict__ xn, const uint16_t* __restrict__ xn_lo,
                                                                     const uint16_t* __restrict__ wexp,
@@ -124,8 +215,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                                                                     uint16_t* __restrict__ y, float* __restrict__ logits,
                                                                     float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                                     int64_t tokens, Loss ce) {
-    constexpr bool kDepth = std::is_same<Loss, TailDepth>::value, kStep = std::is_same<Loss, TailCeStep>::value;
-    constexpr bool kDStep = std::is_same<Loss, TailDepthStep>::value;
+    constexpr bool kStep = std::is_same<Loss, TailCeStep>::value, kDStep = std::is_same<Loss, TailDepthStep>::value;
     constexpr int C = 32 * NB, KS = 2 * NB, NCH = C / 8;  // channels (= input width), 16-deep k-steps, 16-byte chunks per row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* wl = smem;                                  // [kP * C][kRowB], 16-byte chunk ^ (row & 15)
@@ -153,24 +243,21 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             wfl[ct][j] = __builtin_bit_cast(bf16x8, make_uint4(al.x, al.y, bl.x, bl.y));
         }
     float bk[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) bk[r] = bvec[4 * half + (r & 3) + 8 * (r >> 2)];
+    load_head_bias(bvec, half, bk);
     // TailCeStep: one histogram per wave behind the patches (4 x 1 KB: 148 KB of LDS at C = 128), flushed once after the loop
     uint32_t* hist = (uint32_t*)(smem + kP * C * kRowB + 4 * 32 * kPatchRow);
-    uint32_t bad_rows = 0;  // (wave-uniform: counted with ballots)
+    TailLane st;
+    st.hist = hist + (tid >> 6) * kHistBins;
     if constexpr (kStep) {
         for (int j = tid; j < 4 * kHistBins; j += 256) hist[j] = 0;
     }
-    double dsum[kDStep ? depth_metrics::kNSums : 1];  // TailDepthStep: the lane's metric sums (half 0 lanes add, one row each)
     if constexpr (kDStep) {
 #pragma unroll
-        for (int k = 0; k < depth_metrics::kNSums; ++k) dsum[k] = 0.0;
+        for (int k = 0; k < depth_metrics::kNSums; ++k) st.dsum[k] = 0.0;
     }
     __syncthreads();
 
     const int sx = l31 & 15;
-    const float inv_c = 1.f / (float)C;
-    float ce_num = 0.f, ce_den = 0.f;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (tid >> 6), nwaves = (int64_t)gridDim.x * 4;
     for (int64_t tok0 = wave * 32; tok0 < tokens; tok0 += nwaves * 32) {
         const int64_t tok = tok0 + l31;
@@ -181,8 +268,8 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             const uint4 v = live ? *(const uint4*)(xn + tok * C + 16 * ks + 8 * half) : make_uint4(0, 0, 0, 0);
             xb[ks] = __builtin_bit_cast(bf16x8, v);
         }
-        uint32_t pred4 = 0;  // TailCeStep: the class ids of the token's 4 children, child p in byte p
-        float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), lv4 = m4;  // TailDepthStep: metres and log variance of the 4 children
+        st.pred4 = 0;
+        st.m4 = st.lv4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 1
         for (int p = 0; p < kP; ++p) {
             // ------------------------------------------------------------ the child's C channels of 32 tokens: D = Wexp_p xn^T
@@ -246,23 +333,8 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                 }
             }
             // ------------------------------------------------------------ LayerNorm statistics of each row (lane pair)
-            float sum = 0.f;
-#pragma unroll
-            for (int ct = 0; ct < NB; ++ct)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sum += acc[ct][r];
-            sum += __shfl_xor(sum, 32, 64);
-            const float mean = sum * inv_c;
-            float sq = 0.f;
-#pragma unroll
-            for (int ct = 0; ct < NB; ++ct)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    acc[ct][r] -= mean;
-                    sq = fmaf(acc[ct][r], acc[ct][r], sq);
-                }
-            sq += __shfl_xor(sq, 32, 64);
-            const float rstd = rsqrtf(sq * inv_c + kEps);
+            float mean, rstd;
+            row_stats<16>(acc, mean, rstd);
             // ------------------------------------------------------------ head: logits^T = (gamma W) xhat^T, xhat = hi + lo
             f32x16 lg;
 #pragma unroll
@@ -271,104 +343,14 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             for (int ct = 0; ct < NB; ++ct)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    float xh[8], lo[8];
+                    float xh[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) xh[i] = acc[ct][8 * j + i] * rstd;
-                    const uint4 hb = pack8f(xh);
-                    const uint32_t hw[4] = {hb.x, hb.y, hb.z, hb.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        lo[2 * i] = xh[2 * i] - bf_lo(hw[i]);
-                        lo[2 * i + 1] = xh[2 * i + 1] - bf_hi(hw[i]);
-                    }
-                    lg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfa[ct][j], __builtin_bit_cast(bf16x8, hb), lg, 0, 0, 0);
-                    lg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfa[ct][j], __builtin_bit_cast(bf16x8, pack8f(lo)), lg, 0, 0, 0);
-                    lg = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfl[ct][j], __builtin_bit_cast(bf16x8, hb), lg, 0, 0, 0);
+                    lg = head_step<3>(lg, xh, wfa[ct][j], wfl[ct][j]);
                 }
-            if constexpr (kDepth) {  // depth term of the row: channels 0 and 1 are registers 0 and 1 of half 0
-                const float t = live && half == 0 ? ce.target[orow] : INFINITY;
-                if (depth_keep(t)) {
-                    ce_num += depth_term(ce.kind, ce.delta, lg[0] + bk[0], lg[1] + bk[1], t);
-                    ce_den += 1.f;
-                }
-            } else if constexpr (kDStep) {
-                const float t = live && half == 0 ? ce.target[orow] : INFINITY;
-                const float p0 = lg[0] + bk[0], p1 = lg[1] + bk[1];
-                if (depth_keep(t)) {  // (TailDepth's lines)
-                    ce_num += depth_term(ce.kind, ce.delta, p0, p1, t);
-                    ce_den += 1.f;
-                }
-                if (ce.partial || ce.preds) {  // (uniform) back to metres, as unnormalize_and_retransform on prediction and target
-#pragma clang fp contract(off)
-                    const float m = target_op(p0, ce.inv);
-                    if (ce.partial && live && half == 0)
-                        depth_metrics::accumulate<float, float>(dsum, ce.rule, m, target_op(t, ce.inv), [&] { return p1; });
-                    m4.x = p == 0 ? m : m4.x;  // (selects: an index would put the four values into scratch)
-                    m4.y = p == 1 ? m : m4.y;
-                    m4.z = p == 2 ? m : m4.z;
-                    m4.w = p == 3 ? m : m4.w;
-                }
-                lv4.x = p == 0 ? p1 : lv4.x;
-                lv4.y = p == 1 ? p1 : lv4.y;
-                lv4.z = p == 2 ? p1 : lv4.z;
-                lv4.w = p == 3 ? p1 : lv4.w;
-            } else if (ce.labels) {  // weighted cross-entropy of the row, from the fp32 logits in registers
-                constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
-                float v[8];
-                float m = -INFINITY;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    v[r] = lg[r] + bk[r];
-                    if (4 * half + (r & 3) + 8 * (r >> 2) < ce.n_classes) m = fmaxf(m, v[r]);
-                }
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-                const int yl = live ? (int)ce.labels[orow] : 255;
-                float ssum = 0.f, pick = 0.f;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int cls = 4 * half + (r & 3) + 8 * (r >> 2);
-                    if (cls < ce.n_classes) ssum += __builtin_amdgcn_exp2f((v[r] - m) * kLog2e);
-                    pick = cls == yl ? v[r] : pick;
-                }
-                ssum += __shfl_xor(ssum, 32, 64);
-                pick += __shfl_xor(pick, 32, 64);  // (the other half holds 0)
-                const float wy = yl < ce.n_classes ? (ce.class_w ? ce.class_w[yl] : 1.f) : 0.f;
-                if (half == 0) {
-                    ce_num = fmaf(wy, m + __builtin_amdgcn_logf(ssum) * kLn2 - pick, ce_num);
-                    ce_den += wy;
-                }
-                if constexpr (kStep) {
-                    float best = -INFINITY;  // (the lowest class wins over -inf by index; a lane without a class loses every tie)
-                    int arg = 4 * half < ce.n_classes ? 4 * half : 64;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) {  // r ascending = class id ascending
-                        const int cls = 4 * half + (r & 3) + 8 * (r >> 2);
-                        if (cls < ce.n_classes && !(best != best) && (v[r] > best || v[r] != v[r])) {
-                            best = v[r];
-                            arg = cls;
-                        }
-                    }
-                    const int pred = argmax_merge(best, arg, __shfl_xor(best, 32, 64), __shfl_xor(arg, 32, 64));
-                    pred4 |= (uint32_t)pred << (8 * p);
-                    if (ce.conf) {  // (wave-uniform) one row per lane pair: half 0 counts it
-                        const bool mine = live && half == 0;
-                        const int bin = mine && yl < ce.n_classes ? yl * ce.n_classes + pred : -1;
-                        bad_rows += (uint32_t)__popcll(__ballot(mine && yl >= ce.n_classes));
-                        // the lanes that share the first lane's bin (most of them in the uniform regions of a mask) add with one atomic
-                        uint32_t* h = hist + (tid >> 6) * kHistBins;
-                        const int lead = __builtin_amdgcn_readfirstlane(bin);
-                        const unsigned long long same = __ballot(bin == lead);
-                        if (bin == lead) {
-                            if (lead >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(&h[lead], (uint32_t)__popcll(same));
-                        } else if (bin >= 0) {
-                            atomicAdd(&h[bin], 1u);
-                        }
-                    }
-                }
-            }
+            ce.row(st, lg, bk, orow, p, live, lane);
             if (live) {
-                // accumulator register r = class 4 half + (r & 3) + 8 (r >> 2) of this lane's row: classes 0..15 are r = 0..7
-                if (logits) {
+                if (logits) {  // classes 0..15 of the row are registers 0..7 of the lane pair (class_natural)
                     *(float4*)(logits + orow * kKP + 4 * half) = make_float4(lg[0] + bk[0], lg[1] + bk[1], lg[2] + bk[2], lg[3] + bk[3]);
                     *(float4*)(logits + orow * kKP + 8 + 4 * half) = make_float4(lg[4] + bk[4], lg[5] + bk[5], lg[6] + bk[6], lg[7] + bk[7]);
                 }
@@ -379,13 +361,13 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             }
         }
         if constexpr (kStep) {
-            if (ce.preds && live && half == 0) *(uint32_t*)(ce.preds + tok * kP) = pred4;  // one 128-byte line per wave and step
+            if (ce.preds && live && half == 0) *(uint32_t*)(ce.preds + tok * kP) = st.pred4;  // one 128-byte line per wave and step
         }
         if constexpr (kDStep) {  // the token's 4 children as one 16-byte store per channel: 512 contiguous bytes per wave and step
             if (live && half == 0) {
-                if (ce.preds) *(float4*)(ce.preds + tok * kP) = m4;
+                if (ce.preds) *(float4*)(ce.preds + tok * kP) = st.m4;
                 float* lv = ce.preds ? (ce.n_out > 1 ? ce.preds + ce.rows : nullptr) : ce.logvar_out;
-                if (lv) *(float4*)(lv + tok * kP) = lv4;
+                if (lv) *(float4*)(lv + tok * kP) = st.lv4;
             }
         }
     }
@@ -398,7 +380,7 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
             double* red = (double*)smem;
             __syncthreads();  // (every wave has left the weights and its patch)
 #pragma unroll
-            for (int k = 0; k < NS; ++k) red[k * 256 + tid] = dsum[k];
+            for (int k = 0; k < NS; ++k) red[k * 256 + tid] = st.dsum[k];
             __syncthreads();
             for (int h = 128; h > 0; h >>= 1) {
                 for (int q = tid; q < NS * h; q += 256) {
@@ -418,11 +400,11 @@ __global__ void __launch_bounds__(256, 1) expand_ln_head_fwd_kernel(const uint16
                 const uint32_t n = hist[tid] + hist[kHistBins + tid] + hist[2 * kHistBins + tid] + hist[3 * kHistBins + tid];
                 if (n) atomicAdd(&ce.conf[tid], (unsigned long long)n);
             }
-            if (lane == 0 && bad_rows) atomicAdd(&ce.bad[0], (unsigned long long)bad_rows);
+            if (lane == 0 && st.bad_rows) atomicAdd(&ce.bad[0], (unsigned long long)st.bad_rows);
         }
     }
-    if (has_loss(ce)) {  // every wave writes its pair (zeros if it owned no rows): the host sums the array
-        const float n = wave_sum(ce_num), d = wave_sum(ce_den);
+    if (ce.has_loss()) {  // every wave writes its pair (zeros if it owned no rows): the host sums the array
+        const float n = wave_sum(st.num), d = wave_sum(st.den);
         if (lane == 0) {
             ce.loss_part[2 * wave] = n;
             ce.loss_part[2 * wave + 1] = d;
@@ -454,7 +436,6 @@ int launch_expand_ln_head(const void* xn, const void* xn_lo, const void* wexp, c
         return fail(HS_ERR_UNSUPPORTED, "%s: bf16, 4 children, C in {64, 96, 128} (got C = %d, children %d): the expand "
                     "weight must fit the LDS", who, width, children);
     HS_CHECK_ALIGNED(who, 16, xn, xn_lo, wexp, wfold, bvec, y);  // 16-byte row chunks, weights staged into the LDS in 16-byte units
-    const int nb = width / 32;
     constexpr bool kStep = std::is_same<Loss, TailCeStep>::value;
     const size_t smem = (size_t)kP * width * kRowB + 4 * 32 * kPatchRow + (kStep ? 4 * kHistBins * sizeof(uint32_t) : 0);
     HS_CHECK_ARG(smem <= 160 * 1024, "%s: %zu bytes of LDS", who, smem);  // (148 KB with the histograms at C = 128)
@@ -464,24 +445,27 @@ int launch_expand_ln_head(const void* xn, const void* xn_lo, const void* wexp, c
         HS_CHECK_ARG((groups + waves - 1) / waves < (1ll << 25), "%s: %lld tokens on %lld waves overflow the 32-bit histogram bins", who,
                      (long long)tokens, (long long)waves);
     }
-    hipStream_t s = (hipStream_t)stream;
-#define HS_ELH(NB)                                                                                                                  \
-    case NB: {                                                                                                                      \
-        auto kern = expand_ln_head_fwd_kernel<NB, Loss>;                                                                                 \
-        static bool configured = false;                                                                                             \
-        if (!configured) {                                                                                                          \
-            HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));           \
-            configured = true;                                                                                                      \
-        }                                                                                                                           \
-        hipLaunchKernelGGL(kern, grid, block, smem, s, (const uint16_t*)xn, (const uint16_t*)xn_lo, (const uint16_t*)wexp, (const uint16_t*)wfold, bvec, \
-                           (uint16_t*)y, logits, mean, rstd, tokens, ce);                                                          \
-    } break;
-    switch (nb) {
-        HS_ELH(2) HS_ELH(3) HS_ELH(4)
-    }
-#undef HS_ELH
-    HS_LAUNCH_CHECK("expand_ln_head_fwd");
-    return HS_OK;
+    return with_width_blocks<4>(width, [&](auto nb) {
+        auto kern = expand_ln_head_fwd_kernel<decltype(nb)::value, Loss>;
+        static bool configured = false;  // (one per instantiation)
+        if (!configured) {
+            HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            configured = true;
+        }
+        hipLaunchKernelGGL(kern, grid, block, smem, (hipStream_t)stream, (const uint16_t*)xn, (const uint16_t*)xn_lo,
+                           (const uint16_t*)wexp, (const uint16_t*)wfold, bvec, (uint16_t*)y, logits, mean, rstd, tokens, ce);
+        HS_LAUNCH_CHECK("expand_ln_head_fwd");
+        return (int)HS_OK;
+    });
+}
+// what the entry points with a loss check before the common part
+int check_ce_loss(const char* who, const void* labels, const void* loss_partials, int n_classes) {
+    HS_CHECK_ARG(labels && loss_partials, "%s: null pointer", who);
+    return hs::check_class_count(who, n_classes);
+}
+int check_depth_loss(const char* who, const void* target, const void* loss_partials, int kind, float huber_delta, int n_out) {
+    HS_CHECK_ARG(target && loss_partials, "%s: null pointer", who);
+    return hs::check_depth_head(who, kind, huber_delta, n_out);
 }
 }  // namespace
 }  // extern "C++"
@@ -503,8 +487,7 @@ int hs_expand_ln_head_fwd(const void* xn, const void* xn_lo, const void* wexp, c
 int hs_expand_ln_head_ce_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const uint8_t* labels,
                              const float* class_weights, int n_classes, void* y, float* logits, float* mean, float* rstd,
                              float* loss_partials, int64_t tokens, int width, int children, int dtype, void* stream) {
-    HS_CHECK_ARG(labels && loss_partials, "hs_expand_ln_head_ce_fwd: null pointer");
-    HS_CHECK_ARG(n_classes >= 1 && n_classes <= 16, "hs_expand_ln_head_ce_fwd: 1..16 classes");
+    if (int e = check_ce_loss("hs_expand_ln_head_ce_fwd", labels, loss_partials, n_classes)) return e;
     return launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream,
                                  hs::TailCe{labels, class_weights, loss_partials, n_classes}, "hs_expand_ln_head_ce_fwd");
 }
@@ -513,14 +496,13 @@ int hs_expand_ln_head_ce_step_fwd(const void* xn, const void* xn_lo, const void*
                                   const uint8_t* labels, const float* class_weights, int n_classes, void* y, float* logits, float* mean,
                                   float* rstd, float* loss_partials, uint8_t* preds, int64_t* confmat, int64_t* bad, int64_t tokens,
                                   int width, int children, int dtype, void* stream) {
-    HS_CHECK_ARG(labels && loss_partials, "hs_expand_ln_head_ce_step_fwd: null pointer");
-    HS_CHECK_ARG(n_classes >= 1 && n_classes <= 16, "hs_expand_ln_head_ce_step_fwd: 1..16 classes");
-    HS_CHECK_ARG(!confmat || bad, "hs_expand_ln_head_ce_step_fwd: confmat needs bad (the counter of labels >= n_classes)");
-    HS_CHECK_ARG(((uintptr_t)preds & 3) == 0, "hs_expand_ln_head_ce_step_fwd: preds must be 4-byte aligned");
+    const char* who = "hs_expand_ln_head_ce_step_fwd";
+    if (int e = check_ce_loss(who, labels, loss_partials, n_classes)) return e;
+    HS_CHECK_ARG(!confmat || bad, "%s: confmat needs bad (the counter of labels >= n_classes)", who);
+    HS_CHECK_ARG(((uintptr_t)preds & 3) == 0, "%s: preds must be 4-byte aligned", who);
     return launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream,
-                                 hs::TailCeStep{labels, class_weights, loss_partials, n_classes, preds, (unsigned long long*)confmat,
-                                                (unsigned long long*)bad},
-                                 "hs_expand_ln_head_ce_step_fwd");
+                                 hs::TailCeStep{{labels, class_weights, loss_partials, n_classes}, preds, (unsigned long long*)confmat,
+                                                (unsigned long long*)bad}, who);
 }
 
 int hs_expand_ln_head_depth_step_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec,
@@ -529,15 +511,13 @@ int hs_expand_ln_head_depth_step_fwd(const void* xn, const void* xn_lo, const vo
                                      double total_mean, const float* ranges, int n_ranges, double* metric_partials, double* metric_state,
                                      float* preds, float* logvar_out, int64_t tokens, int width, int children, int dtype, void* stream) {
     const char* who = "hs_expand_ln_head_depth_step_fwd";
-    HS_CHECK_ARG(target && loss_partials, "%s: null pointer", who);
-    HS_CHECK_ARG(hs::depth_head_ok(kind, huber_delta, n_out), "%s: kind %d with %d head channels (1 or 2; Huber 1, log variance 2; "
-                 "huber delta > 0)", who, kind, n_out);
+    if (int e = check_depth_loss(who, target, loss_partials, kind, huber_delta, n_out)) return e;
     HS_CHECK_ARG(transform == HS_DT_NONE || transform == HS_DT_LOG || transform == HS_DT_INV, "%s: transform %d", who, transform);
     HS_CHECK_ARG((flags & ~(HS_DT_AFFINE | HS_DT_INVERSE)) == 0, "%s: flags %d (HS_DT_AFFINE or 0: the inverse chain is applied)", who, flags);
     HS_CHECK_ARG((metric_partials == nullptr) == (metric_state == nullptr), "%s: metric_partials and metric_state go together", who);
     HS_CHECK_ARG(n_out == 2 || !(logvar_out || (use_logvar && metric_state)), "%s: the log variance needs a two-channel head", who);
-    hs::TailDepthStep st{target, loss_partials, kind, huber_delta, n_out, hs::TargetOp{flags | HS_DT_INVERSE, transform, shift, scale}, {},
-                         metric_partials, preds, logvar_out, tokens * hs::kP};
+    hs::TailDepthStep st{{target, loss_partials, kind, huber_delta}, n_out, hs::TargetOp{flags | HS_DT_INVERSE, transform, shift, scale},
+                         {}, metric_partials, preds, logvar_out, tokens * hs::kP};
     if (int e = hs::depth_metrics::fill_rule(st.rule, use_logvar, total_mean, ranges, n_ranges)) return e;
     HS_CHECK_ALIGNED(who, 16, preds, logvar_out);  // the 4 children of a token leave as one 16-byte store
     HS_CHECK_ALIGNED(who, 8, metric_partials, metric_state);
@@ -555,9 +535,7 @@ int hs_expand_ln_head_depth_step_fwd(const void* xn, const void* xn_lo, const vo
 int hs_expand_ln_head_depth_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const float* target,
                                 int kind, float huber_delta, int n_out, void* y, float* logits, float* mean, float* rstd, float* loss_partials,
                                 int64_t tokens, int width, int children, int dtype, void* stream) {
-    HS_CHECK_ARG(target && loss_partials, "hs_expand_ln_head_depth_fwd: null pointer");
-    HS_CHECK_ARG(hs::depth_head_ok(kind, huber_delta, n_out), "hs_expand_ln_head_depth_fwd: kind %d with %d head channels (1 or 2; Huber 1, "
-                 "log variance 2; huber delta > 0)", kind, n_out);
+    if (int e = check_depth_loss("hs_expand_ln_head_depth_fwd", target, loss_partials, kind, huber_delta, n_out)) return e;
     return launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream,
                                  hs::TailDepth{target, loss_partials, kind, huber_delta}, "hs_expand_ln_head_depth_fwd");
 }

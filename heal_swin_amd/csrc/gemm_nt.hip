@@ -36,8 +36,6 @@ namespace hs {
 HS_DEFINE_SEED_EPOCH_SETTER(set_seed_epoch_gemm_nt)
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef unsigned int u32x2 __attribute__((__vector_size__(8)));    // the types the b64 / b128 buffer builtins take
 typedef unsigned int u32x4v __attribute__((__vector_size__(16)));

@@ -21,6 +21,11 @@ inline bool depth_head_ok(int kind, float delta, int n_out) {
     if (kind == HS_DEPTH_HUBER) return n_out == 1 && delta > 0.f;
     return kind == HS_DEPTH_LOGVAR && n_out == 2;
 }
+inline int check_depth_head(const char* who, int kind, float delta, int n_out) {
+    HS_CHECK_ARG(depth_head_ok(kind, delta, n_out), "%s: kind %d with %d head channels (1 or 2; Huber 1, log variance 2; huber delta > 0)",
+                 who, kind, n_out);
+    return HS_OK;
+}
 
 __device__ __forceinline__ bool depth_keep(float t) { return !__builtin_isinf(t); }
 

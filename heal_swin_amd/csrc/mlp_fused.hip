@@ -36,8 +36,6 @@ namespace hs {
 HS_DEFINE_SEED_EPOCH_SETTER(set_seed_epoch_mlp_fused)
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef unsigned int u32x2v __attribute__((__vector_size__(8)));

@@ -6,12 +6,8 @@
 
 namespace hs {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 constexpr float kNormEps = 1e-12f;             // F.normalize eps, swin_hp_transformer.py:143
 constexpr float kMaskLog2 = -100.f * kLog2e;  // hp_shifting.py:25, in the log2 domain
 // 1 / max(|x|, eps) from the squared norm: v_rsq_f32 (1 ulp) + a clamp instead of the correctly rounded sqrt and division hipcc

@@ -186,7 +186,7 @@ _CE_PERM = {}
 
 def _fold_head_ce(gamma, beta, weight, C, device):
     """The folded head weight for `hs_ln_head_ce_bwd`: as _fold_head, but with row blocks 4..7 and 8..11 exchanged, so that the
-    kernel's accumulator register r < 8 of lane half h is class 8 h + r (csrc/ln_head.hip:ln_head_ce_bwd_kernel)."""
+    kernel's accumulator register r < 8 of lane half h is class 8 h + r (csrc/ln_head_device.h:class_exchanged)."""
     wfold, bvec = _fold_head(gamma, beta, weight, C, device)
     key = str(device)
     if key not in _CE_PERM:  # (built once per device: six tiny launches per step otherwise)
