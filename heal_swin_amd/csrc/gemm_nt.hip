@@ -36,10 +36,8 @@ namespace hs {
 HS_DEFINE_SEED_EPOCH_SETTER(set_seed_epoch_gemm_nt)
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef unsigned int u32x2 __attribute__((__vector_size__(8)));    // the types the b64 / b128 buffer builtins take
 typedef unsigned int u32x4v __attribute__((__vector_size__(16)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 // HS_GEMM_EPI_RING (A/B: 0 = register loads, one HBM round trip per row block behind a full vmcnt(0)): the epilogue's INPUT rows
 // (h for GELU', the residual) of the 256 x 256 tile go global -> LDS by DMA through two patches per wave inside the consumed stage
@@ -71,7 +69,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 #define HS_GEMM_STAGGER_CYCLES 40000  // one 256 x 256 x 512 tile with a GELU epilogue (tools/gemm_trace.py)
 #endif
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_DGELU = 2, EPI_RESID = 3 };
-__device__ constexpr uint32_t kOob = 0x7FFFFF00u;  // a byte offset outside every descriptor below
 constexpr int64_t kMaxRecords = 0x7FFFFE00;  // descriptors are clamped to this many bytes (tiles address < 2 GiB from their origin)
 
 struct GemmParams {

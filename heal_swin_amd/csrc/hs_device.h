@@ -30,6 +30,12 @@ __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 
 // operand and accumulator registers of v_mfma_f32_32x32x16_bf16
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+// 16 bytes of packed words (a b128 LDS / global access, four bf16 pairs)
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+// LDS-DMA (buffer_load ... lds): the destination type of the builtin, and a byte offset outside every descriptor (a lane pointed
+// there is predicated off: the DMA writes zeros, a store is dropped)
+typedef __attribute__((address_space(3))) void lds_void;
+__device__ constexpr uint32_t kOob = 0x7FFFFF00u;
 
 // exp and log through v_exp_f32 / v_log_f32 (base 2)
 constexpr float kLog2e = 1.4426950408889634f;

@@ -51,6 +51,26 @@ struct Geometry {
     int64_t rows_per_slice;
 };
 
+// floats of one slice's partial record: the weight partial [n_out][k_in], the bias partial [n_out] behind it
+__host__ __device__ constexpr int64_t record_floats(int n_out, int k_in) { return (int64_t)n_out * k_in + n_out; }
+
+// Token slices for g.tiles output tiles: one resident round of equal workgroups over the CUs this library may plan for (256 minus
+// hs_set_reserved_cus()); at least 512 tokens per slice, whole 32-token stages
+inline void plan_slices(Geometry& g, int64_t rows, int wgs_per_cu) {
+    int64_t want = ((int64_t)usable_cus() * wgs_per_cu) / g.tiles;
+    const int64_t max_by_rows = (rows + 511) / 512;
+    if (want > max_by_rows) want = max_by_rows;
+    if (want > kMaxSlices) want = kMaxSlices;
+    if (want < 1) want = 1;
+    g.slices = (int)want;
+    const int64_t rps = (rows + g.slices - 1) / g.slices;
+    g.rows_per_slice = ((rps + kTok - 1) / kTok) * kTok;
+    g.per_xcd = (g.slices * g.tiles + 7) / 8;
+}
+
+// the LDS-DMA kernels address a slice through 32-bit buffer offsets: `width` = elements of the widest operand row
+inline bool slice_fits_dma(const Geometry& g, int64_t width, int elt) { return g.rows_per_slice * width * elt < ((int64_t)1 << 31); }
+
 inline Geometry geometry_for(int64_t rows, int n_out, int k_in, int tile_k, int wgs_per_cu, int tile_n = 0, int elt = 2) {
     Geometry g;
     g.tile_n = tile_n ? tile_n : ((n_out % 256 == 0 || n_out >= 512) ? 256 : 128);
@@ -58,23 +78,15 @@ inline Geometry geometry_for(int64_t rows, int n_out, int k_in, int tile_k, int 
     g.tiles_n = (n_out + g.tile_n - 1) / g.tile_n;
     g.tiles_k = (k_in + tile_k - 1) / tile_k;
     g.tiles = g.tiles_n * g.tiles_k;
-    // one resident round of equal workgroups over the CUs this library may plan for (256 minus hs_set_reserved_cus()); at
-    // least 512 tokens per slice
-    int64_t want = ((int64_t)usable_cus() * wgs_per_cu) / g.tiles;
-    int64_t max_by_rows = (rows + 511) / 512;
-    if (want > max_by_rows) want = max_by_rows;
-    if (want > kMaxSlices) want = kMaxSlices;
-    if (want < 1) want = 1;
-    g.slices = (int)want;
-    int64_t rps = (rows + g.slices - 1) / g.slices;
-    g.rows_per_slice = ((rps + kTok - 1) / kTok) * kTok;
+    plan_slices(g, rows, wgs_per_cu);
     g.chunks = g.slices > 2 * kReduceChunks ? kReduceChunks : 1;
-    g.per_xcd = (g.slices * g.tiles + 7) / 8;
-    // the LDS-DMA kernels address a slice through 32-bit buffer offsets
-    g.dma = g.rows_per_slice * (int64_t)(n_out > k_in ? n_out : k_in) * elt < ((int64_t)1 << 31);
-    // stage schedule of the LDS-DMA kernels: 3 = next stage's DMA issued behind the fragment reads + the second wave group half a
+    g.dma = slice_fits_dma(g, n_out > k_in ? n_out : k_in, elt);
+    // stage schedule of the bf16 LDS-DMA kernel: 3 = next stage's DMA issued behind the fragment reads + the second wave group half a
     // stage out of phase (8-wave tile).  (0 = DMA before the reads, 1 = behind them, 2 = behind the first MFMA group: the schedules
-    // round 2 measured against it, profiles/archive_r01_r04/r02_wgrad_schedule_ab.txt)
+    // round 2 measured against it, profiles/archive_r01_r04/r02_wgrad_schedule_ab.txt.)  Always 3, and still a run-time value ON
+    // PURPOSE: with the three other schedules compiled out the 256 x 256 kernel issues the same instructions in the same order
+    // and is 5-10 % SLOWER (profiles/wgrad_refactor.txt, section 5) -- the scalar compares and taken branches of the dead schedules
+    // stand between the fragment reads and the DMA issue, and between the two MFMA groups
     g.reads_first = 3;
     return g;
 }
@@ -106,6 +118,79 @@ __device__ __forceinline__ bool block_to_work(const Geometry& g, int b, int& sli
     return (b >> 3) < g.per_xcd && v < g.slices * g.tiles;
 }
 
+// ---------------------------------------------------------------------------------------- pieces every kernel below shares
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// token rows [m_begin, m_begin + m_len) of a slice; a kernel with T-token stages runs (m_len + T - 1) / T of them
+struct SliceRows {
+    int64_t m_begin;
+    int m_len;
+};
+__device__ __forceinline__ SliceRows slice_rows(const Geometry& g, int slice, int64_t rows) {
+    const int64_t m_begin = (int64_t)slice * g.rows_per_slice;
+    int64_t m_end = m_begin + g.rows_per_slice;
+    if (m_end > rows) m_end = rows;
+    return {m_begin, m_end > m_begin ? (int)(m_end - m_begin) : 0};
+}
+
+template <int NB>
+__device__ __forceinline__ void zero(f32x16 (&acc)[NB][2]) {
+#pragma unroll
+    for (int i = 0; i < NB; ++i) acc[i][0] = acc[i][1] = 0.f;
+}
+
+// A wave's NB x 2 accumulators (32 x 32 each, origin (n_wave, k_wave)) -> the slice's partial record `dst` [n_out][k_in];
+// accumulator: column = k (lane & 31), rows = n
+template <int NB>
+__device__ __forceinline__ void store_partial(const f32x16 (&acc)[NB][2], float* dst, int n_wave, int k_wave, int n_out, int k_in,
+                                              int lane) {
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int kk = k_wave + j * 32 + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int nn = n_wave + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (nn < n_out && kk < k_in) dst[(int64_t)nn * k_in + kk] = acc[i][j][r];
+            }
+        }
+}
+
+// Bias partial of a tile: every thread holds the sums of PER_THREAD columns over its share of the rows (thread -> row group
+// tid / (TN / PER_THREAD), column chunk tid % (TN / PER_THREAD)); the GROUPS row groups are folded through `bred` (the tile
+// buffers, which every wave must be done with) into the record's bias part `dst` [n_out]
+template <int TN, int GROUPS, int PER_THREAD>
+__device__ __forceinline__ void fold_bias(float* bred, const float (&bsum)[PER_THREAD], int tid, int n0, int n_out, float* dst) {
+    constexpr int CH = TN / PER_THREAD;
+#pragma unroll
+    for (int i = 0; i < PER_THREAD; ++i) bred[(tid / CH) * TN + (tid % CH) * PER_THREAD + i] = bsum[i];
+    __syncthreads();
+    if (tid < TN) {
+        float t = 0.f;
+#pragma unroll
+        for (int rg = 0; rg < GROUPS; ++rg) t += bred[rg * TN + tid];
+        if (n0 + tid < n_out) dst[n0 + tid] = t;
+    }
+}
+
+// adds the eight bf16 of four dwords to eight column sums
+__device__ __forceinline__ void add_bf16x8(float (&bsum)[8], uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
+    const uint32_t w[4] = {w0, w1, w2, w3};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        bsum[2 * i] += bf_lo(w[i]);
+        bsum[2 * i + 1] += bf_hi(w[i]);
+    }
+}
+
 // NB = 32-row blocks per wave along n: the workgroup tile is (64*NB) x 128, waves in 2 x 2, each (32*NB) x 64
 template <int NB>
 __global__ void __launch_bounds__(256, 2) wgrad_kernel(const uint16_t* __restrict__ dy, const uint16_t* __restrict__ x,
@@ -128,9 +213,8 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const uint16_t* __restric
     if (!block_to_work(g, blockIdx.x, slice, tile)) return;
     const int tn = tile / g.tiles_k, tk = tile % g.tiles_k;
     const int n0 = tn * TN, k0 = tk * kTileK;
-    const int64_t m_begin = (int64_t)slice * g.rows_per_slice;
-    int64_t m_end = m_begin + g.rows_per_slice;
-    if (m_end > rows) m_end = rows;
+    const SliceRows sr = slice_rows(g, slice, rows);
+    const int64_t m_begin = sr.m_begin, m_end = sr.m_begin + sr.m_len;
 
     // staging: X tile: thread -> (row tid/16 + 16*pass, chunk tid%16); dY tile: (row tid/YCH + (256/YCH)*pass, chunk tid%YCH)
     const int xr = tid >> 4, xc = tid & 15;
@@ -142,12 +226,7 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const uint16_t* __restric
     float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     f32x16 acc[NB][2];
-#pragma unroll
-    for (int a = 0; a < NB; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b2][r] = 0.f;
+    zero(acc);
 
     uint4 ry[YPASS], rx[2];
     auto load_regs = [&](int64_t m0) {
@@ -166,14 +245,7 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const uint16_t* __restric
 #pragma unroll
         for (int ps = 0; ps < YPASS; ++ps) {
             *(uint4*)(ytile(buf) + (yr + (256 / YCH) * ps) * LDY + yc * 16) = ry[ps];
-            if (do_bias) {
-                const uint32_t w[4] = {ry[ps].x, ry[ps].y, ry[ps].z, ry[ps].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    bsum[2 * i] += __uint_as_float(w[i] << 16);
-                    bsum[2 * i + 1] += __uint_as_float(w[i] & 0xffff0000u);
-                }
-            }
+            if (do_bias) add_bf16x8(bsum, ry[ps].x, ry[ps].y, ry[ps].z, ry[ps].w);
         }
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) *(uint4*)(xtile(buf) + (xr + 16 * ps) * LDX + xc * 16) = rx[ps];
@@ -210,30 +282,11 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const uint16_t* __restric
         buf ^= 1;
     }
 
-    // partial tile -> workspace [slice][n_out][k_in]; accumulator: column = k (lane & 31), rows = n
-    float* dst = part_w + (int64_t)slice * ((int64_t)n_out * k_in + n_out);
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kk = k0 + wk * 64 + j * 32 + (lane & 31);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = n0 + wn * 32 * NB + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (nn < n_out && kk < k_in) dst[(int64_t)nn * k_in + kk] = acc[i][j][r];
-            }
-        }
-    if (do_bias) {  // fold the row groups that share a column chunk (tile buffers are free: last loop barrier passed)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bred[yr * TN + yc * 8 + i] = bsum[i];
-        __syncthreads();
-        if (tid < TN) {
-            float t = 0.f;
-#pragma unroll
-            for (int rg = 0; rg < 256 / YCH; ++rg) t += bred[rg * TN + tid];
-            if (n0 + tid < n_out) part_b[(int64_t)slice * ((int64_t)n_out * k_in + n_out) + n0 + tid] = t;
-        }
-    }
+    // partial tile -> workspace [slice][n_out][k_in]
+    const int64_t rec = slice * record_floats(n_out, k_in);
+    store_partial(acc, part_w + rec, n0 + wn * 32 * NB, k0 + wk * 64, n_out, k_in, lane);
+    // (the tile buffers are free: the last loop barrier has passed)
+    if (do_bias) fold_bias<TN, 256 / YCH>(bred, bsum, tid, n0, n_out, part_b + rec);
 }
 
 // LDS-DMA variant of the kernel above: the token tiles go global -> LDS directly (buffer_load_dwordx4 ... lds), three
@@ -246,8 +299,52 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const uint16_t* __restric
 //     column overrun of a partial tile reads the next row / zeros and only ever reaches accumulators that are not stored;
 //   * per stage: s_waitcnt vmcnt(own loads of the NEXT stage) -> s_barrier -> issue stage t+2 -> fragments + MFMA.
 //     The barrier both publishes stage t and retires every wave's reads of the buffer that stage t+2 overwrites.
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+#if defined(__HIP_DEVICE_COMPILE__)  // buffer-resource / LDS-DMA builtins exist in the device pass only
+// One wave's share of a stage: YI + XI 1-KB DMA instructions, piece j of a run filling LDS bytes [j KB, j KB + 1 KB) behind
+// ylds / xlds; the offsets then move on by one stage of rows
+template <int YI, int XI>
+__device__ __forceinline__ void issue_stage(__amdgpu_buffer_rsrc_t rs_y, __amdgpu_buffer_rsrc_t rs_x, unsigned char* ylds,
+                                            unsigned char* xlds, int (&voff_y)[YI], int (&voff_x)[XI], int ystep, int xstep) {
+#pragma unroll
+    for (int j = 0; j < YI; ++j) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void*)(ylds + j * 1024), 16, voff_y[j], 0, 0, 0);
+        voff_y[j] += ystep;
+    }
+#pragma unroll
+    for (int j = 0; j < XI; ++j) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void*)(xlds + j * 1024), 16, voff_x[j], 0, 0, 0);
+        voff_x[j] += xstep;
+    }
+}
+
+// A stage has landed once only the `younger` stages still issued behind it (at most AH - 1, fewer at the tail) are outstanding;
+// PIECES = DMA instructions per wave and stage
+template <int PIECES, int AH>
+__device__ __forceinline__ void wait_stage(int younger) {
+    if (AH - 1 >= 2 && younger >= 2)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PIECES) : "memory");
+    else if (younger >= 1)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
+    else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+#endif
+
+// The stage ring: the DMA runs NSTAGE - 1 stages ahead; stage(t, buffer, next) computes buffer t % NSTAGE and refills the one that
+// stage t - 1 consumed.  The loop is unrolled by NSTAGE so that the buffer indices are compile-time constants and the compiler can
+// tell the DMA's destination buffer from the one being read: with run-time indices it orders them with an s_waitcnt vmcnt(0)
+template <int NSTAGE, typename Issue, typename Stage>
+__device__ __forceinline__ void run_stages(int nst, Issue&& issue, Stage&& stage) {
+    static_for<NSTAGE - 1>([&](auto bc) {
+        constexpr int b = decltype(bc)::value;
+        if (nst > b) issue(b);
+    });
+    for (int t = 0; t < nst; t += NSTAGE)
+        static_for<NSTAGE>([&](auto bc) {
+            constexpr int b = decltype(bc)::value;
+            if (t + b < nst) stage(t + b, bc, std::integral_constant<int, (b + NSTAGE - 1) % NSTAGE>{});
+        });
+}
 
 // one MFMA operand (8 tokens x 1 column per lane) by two transposing reads issued from inline asm; a = LDS byte address of
 // the lane's first 4-row group, ks = 16-token half of the stage
@@ -293,7 +390,7 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
     // ldy / ldx: row strides of dY / X in elements; yc0 / xc0: first column of the operand inside its row (the operands may be
     // column blocks of wider matrices -- the hi / lo parts of a bf16x3 split, ops.split3).  The descriptors cover whole rows of the
     // WIDE matrices, so a tile that overhangs the operand's columns reads its neighbours (never stored), not unmapped memory
-#if defined(__HIP_DEVICE_COMPILE__)  // buffer-resource / LDS-DMA builtins exist in the device pass only
+#if defined(__HIP_DEVICE_COMPILE__)
     constexpr int TN = 64 * NB;
     constexpr int WK = TK / 64, NW = 2 * WK, NT = 64 * NW;  // waves along k, waves, threads: waves in 2 x WK, each (32*NB) x 64
     constexpr int YRB = TN * 2, XRB = TK * 2;    // bytes of one staged dY / X tile row
@@ -324,11 +421,9 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
     tile -= mb.first_tile;
     const int tn = tile / mb.tiles_k, tk = tile % mb.tiles_k;
     const int n0 = tn * TN, k0 = tk * TK;
-    const int64_t m_begin = (int64_t)slice * g.rows_per_slice;
-    int64_t m_end = m_begin + g.rows_per_slice;
-    if (m_end > rows) m_end = rows;
-    const int m_len = m_end > m_begin ? (int)(m_end - m_begin) : 0;
-    const int nst = (m_len + kTok - 1) / kTok;
+    const SliceRows sr = slice_rows(g, slice, rows);
+    const int64_t m_begin = sr.m_begin;
+    const int m_len = sr.m_len, nst = (m_len + kTok - 1) / kTok;
     const bool do_bias = part_b != nullptr && tk == 0;
 
     // descriptors over [m_begin, m_end) x the full row; raw (stride 0) buffers return 0 past num_records
@@ -349,16 +444,7 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
     const int ystep = kTok * ldy * 2, xstep = kTok * ldx * 2;
     auto issue = [&](int b) {
         unsigned char* base = smem + b * STAGE;
-#pragma unroll
-        for (int j = 0; j < YI; ++j) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void*)(base + (wave * YI + j) * 1024), 16, voff_y[j], 0, 0, 0);
-            voff_y[j] += ystep;
-        }
-#pragma unroll
-        for (int j = 0; j < XI; ++j) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void*)(base + YB + (wave * XI + j) * 1024), 16, voff_x[j], 0, 0, 0);
-            voff_x[j] += xstep;
-        }
+        issue_stage(rs_y, rs_x, base + wave * YI * 1024, base + YB + wave * XI * 1024, voff_y, voff_x, ystep, xstep);
     };
 
     // transposing fragment reads: lane -> (row L/4 of a 4-row group, 4 columns) ; swizzled chunk = chunk ^ (row_in << 2)
@@ -379,15 +465,9 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
     float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     f32x16 acc[NB][2];
-#pragma unroll
-    for (int a = 0; a < NB; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b2][r] = 0.f;
+    zero(acc);
 
-    // one stage; the buffer indices are compile-time constants (loop unrolled by NSTAGE) so that the compiler can tell the
-    // DMA's destination buffer from the one being read: with run-time indices it orders them with an s_waitcnt vmcnt(0)
+    // one stage; the buffer indices are compile-time constants (run_stages)
     s16x8 af[2][NB], bf[2][2];  // the stage's MFMA operands (the second wave group keeps them across the barrier, see below)
     auto read_frags = [&](auto buf_c) {
         constexpr int buf = decltype(buf_c)::value;
@@ -416,7 +496,7 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
                     u32x4 w = __builtin_bit_cast(u32x4, bf[ks][j]);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const f32x2 v = gelu2(f32x2{__uint_as_float(w[e] << 16), __uint_as_float(w[e] & 0xffff0000u)});
+                        const f32x2 v = gelu2(f32x2{bf_lo(w[e]), bf_hi(w[e])});
                         w[e] = pack_bf16x2(v.x, v.y);
                     }
                     bf[ks][j] = __builtin_bit_cast(s16x8, w);
@@ -444,13 +524,7 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]));
         }
 #pragma unroll
-        for (int ps = 0; ps < PS; ++ps) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                bsum[2 * i] += __uint_as_float(v[ps][i] << 16);
-                bsum[2 * i + 1] += __uint_as_float(v[ps][i] & 0xffff0000u);
-            }
-        }
+        for (int ps = 0; ps < PS; ++ps) add_bf16x8(bsum, v[ps][0], v[ps][1], v[ps][2], v[ps][3]);
     };
     // ALTERNATING WAVE GROUPS (8-wave tile): the workgroup barrier of every stage phase-locks the two waves of a SIMD -- both
     // read their fragments, both wait for the LDS, both then want the matrix pipe, both idle at the next barrier -- so the pipe
@@ -461,14 +535,7 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
     const bool late_group = NW == 8 && g.reads_first == 3 && wave >= NW / 2;
     auto stage = [&](int t, auto buf_c, auto nbuf_c) {
         constexpr int nbuf = decltype(nbuf_c)::value;
-        // stage t has landed once only the younger stages still issued (at most AH - 1, fewer at the tail) are outstanding
-        const int younger = nst - 1 - t;
-        if (AH - 1 >= 2 && younger >= 2)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (YI + XI)) : "memory");
-        else if (younger >= 1)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YI + XI) : "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_stage<YI + XI, AH>(nst - 1 - t);
         __builtin_amdgcn_s_barrier();
         if (late_group) {
             if (t > 0) {
@@ -496,51 +563,18 @@ __global__ void __launch_bounds__(TK * 2, 2) wgrad_dma_kernel(const MemberTable 
         mma_half(1);
         if (do_bias) bias_sums(buf_c);
     };
-    if (nst > 0) issue(0);
-    if (nst > 1) issue(1);
-    if (AH > 2 && nst > 2) issue(2);
-    using std::integral_constant;
-    for (int t = 0; t < nst; t += NSTAGE) {  // stage t computes buffer t % NSTAGE and refills the one stage t - 1 consumed
-        if constexpr (NSTAGE == 3) {
-            stage(t, integral_constant<int, 0>{}, integral_constant<int, 2>{});
-            if (t + 1 < nst) stage(t + 1, integral_constant<int, 1>{}, integral_constant<int, 0>{});
-            if (t + 2 < nst) stage(t + 2, integral_constant<int, 2>{}, integral_constant<int, 1>{});
-        } else {
-            stage(t, integral_constant<int, 0>{}, integral_constant<int, 3>{});
-            if (t + 1 < nst) stage(t + 1, integral_constant<int, 1>{}, integral_constant<int, 0>{});
-            if (t + 2 < nst) stage(t + 2, integral_constant<int, 2>{}, integral_constant<int, 1>{});
-            if (t + 3 < nst) stage(t + 3, integral_constant<int, 3>{}, integral_constant<int, 2>{});
-        }
-    }
+    run_stages<NSTAGE>(nst, issue, stage);
 
     if (late_group && nst > 0) {  // the last stage's fragments are still to be multiplied
         mma_half(0);
         mma_half(1);
     }
 
-    float* dst = part_w + (int64_t)slice * ((int64_t)n_out * k_in + n_out);
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kk = k0 + wk * 64 + j * 32 + (lane & 31);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = n0 + wn * 32 * NB + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (nn < n_out && kk < k_in) dst[(int64_t)nn * k_in + kk] = acc[i][j][r];
-            }
-        }
+    const int64_t rec = slice * record_floats(n_out, k_in);
+    store_partial(acc, part_w + rec, n0 + wn * 32 * NB, k0 + wk * 64, n_out, k_in, lane);
     if (do_bias) {
         __syncthreads();  // every wave is done with the stage buffers
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bred[yr * TN + yc * 8 + i] = bsum[i];
-        __syncthreads();
-        if (tid < TN) {
-            float t = 0.f;
-#pragma unroll
-            for (int rg = 0; rg < NT / YCH; ++rg) t += bred[rg * TN + tid];
-            if (n0 + tid < n_out) part_b[(int64_t)slice * ((int64_t)n_out * k_in + n_out) + n0 + tid] = t;
-        }
+        fold_bias<TN, NT / YCH>(bred, bsum, tid, n0, n_out, part_b + rec);
     }
 #endif
 }
@@ -566,14 +600,6 @@ __device__ __forceinline__ u32x4 lds_b128(uint32_t a) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "n"(OFF));
     return v;
 }
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 __global__ void __launch_bounds__(256, 3) wgrad_dma_f32_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                float* __restrict__ part_w, float* __restrict__ part_b, int64_t rows,
@@ -582,9 +608,7 @@ __global__ void __launch_bounds__(256, 3) wgrad_dma_f32_kernel(const float* __re
     constexpr int TN = 128, TK = 128;
     constexpr int RB = TN * 4;                       // bytes of one staged tile row (both tiles are 128 floats wide)
     constexpr int YB = kTokF * RB, XB = kTokF * RB;  // 8 KB each
-    // the DMA runs NSTAGE - 1 stages ahead: what bounds the main loop is the bytes in flight per CU, so the
-    // 256-wide tile (one workgroup per CU) takes a fourth 32 KB buffer: 96 instead of 64 KB in flight
-    constexpr int STAGE = YB + XB, NSTAGE = TK == 256 ? 4 : 3, AH = NSTAGE - 1;
+    constexpr int STAGE = YB + XB, NSTAGE = 3, AH = NSTAGE - 1;  // the DMA runs two 16 KB stages ahead
     constexpr int YI = YB / 1024 / 4, XI = XB / 1024 / 4;  // 1-KB DMA instructions per wave and stage (2 + 2)
     __shared__ __attribute__((aligned(16))) unsigned char smem[NSTAGE * STAGE];
     float* bred = (float*)smem;
@@ -594,11 +618,9 @@ __global__ void __launch_bounds__(256, 3) wgrad_dma_f32_kernel(const float* __re
     if (!block_to_work(g, blockIdx.x, slice, tile)) return;
     const int tn = tile / g.tiles_k, tk = tile % g.tiles_k;
     const int n0 = tn * TN, k0 = tk * TK;
-    const int64_t m_begin = (int64_t)slice * g.rows_per_slice;
-    int64_t m_end = m_begin + g.rows_per_slice;
-    if (m_end > rows) m_end = rows;
-    const int m_len = m_end > m_begin ? (int)(m_end - m_begin) : 0;
-    const int nst = (m_len + kTokF - 1) / kTokF;
+    const SliceRows sr = slice_rows(g, slice, rows);
+    const int64_t m_begin = sr.m_begin;
+    const int m_len = sr.m_len, nst = (m_len + kTokF - 1) / kTokF;
     const bool do_bias = part_b != nullptr && tk == 0;
 
     const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(dy + m_begin * n_out), 0, m_len * n_out * 4, 0x00020000);
@@ -617,16 +639,7 @@ __global__ void __launch_bounds__(256, 3) wgrad_dma_f32_kernel(const float* __re
     const int ystep = kTokF * n_out * 4, xstep = kTokF * k_in * 4;
     auto issue = [&](int b) {
         unsigned char* base = smem + b * STAGE;
-#pragma unroll
-        for (int j = 0; j < YI; ++j) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void*)(base + (wave * YI + j) * 1024), 16, voff_y[j], 0, 0, 0);
-            voff_y[j] += ystep;
-        }
-#pragma unroll
-        for (int j = 0; j < XI; ++j) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void*)(base + YB + (wave * XI + j) * 1024), 16, voff_x[j], 0, 0, 0);
-            voff_x[j] += xstep;
-        }
+        issue_stage(rs_y, rs_x, base + wave * YI * 1024, base + YB + wave * XI * 1024, voff_y, voff_x, ystep, xstep);
     };
     // LDS reads through inline asm (a compiler-visible LDS load beside the DMA queue is preceded by s_waitcnt vmcnt(0))
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
@@ -636,23 +649,11 @@ __global__ void __launch_bounds__(256, 3) wgrad_dma_f32_kernel(const float* __re
     float bsum[4] = {0.f, 0.f, 0.f, 0.f};
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b2][r] = 0.f;
+    zero(acc);
 
     auto stage = [&](int t, auto buf_c, auto nbuf_c) {
         constexpr int buf = decltype(buf_c)::value, nbuf = decltype(nbuf_c)::value;
-        // stage t has landed once only the younger stages still issued (at most AH - 1, fewer at the tail) are outstanding
-        const int younger = nst - 1 - t;
-        if (AH - 1 >= 2 && younger >= 2)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (YI + XI)) : "memory");
-        else if (younger >= 1)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YI + XI) : "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_stage<YI + XI, AH>(nst - 1 - t);
         __builtin_amdgcn_s_barrier();
         if (t + AH < nst) issue(nbuf);
         const uint32_t yb = ya + buf * STAGE, xb = xa + buf * STAGE;
@@ -694,53 +695,25 @@ __global__ void __launch_bounds__(256, 3) wgrad_dma_f32_kernel(const float* __re
             for (int i = 0; i < 4; ++i) bsum[i] += __uint_as_float(v0[i]) + __uint_as_float(v1[i]);
         }
     };
-    if (nst > 0) issue(0);
-    if (nst > 1) issue(1);
-    if (AH > 2 && nst > 2) issue(2);
-    using std::integral_constant;
-    for (int t = 0; t < nst; t += NSTAGE) {  // stage t computes buffer t % NSTAGE and refills the one stage t - 1 consumed
-        if constexpr (NSTAGE == 3) {
-            stage(t, integral_constant<int, 0>{}, integral_constant<int, 2>{});
-            if (t + 1 < nst) stage(t + 1, integral_constant<int, 1>{}, integral_constant<int, 0>{});
-            if (t + 2 < nst) stage(t + 2, integral_constant<int, 2>{}, integral_constant<int, 1>{});
-        } else {
-            stage(t, integral_constant<int, 0>{}, integral_constant<int, 3>{});
-            if (t + 1 < nst) stage(t + 1, integral_constant<int, 1>{}, integral_constant<int, 0>{});
-            if (t + 2 < nst) stage(t + 2, integral_constant<int, 2>{}, integral_constant<int, 1>{});
-            if (t + 3 < nst) stage(t + 3, integral_constant<int, 3>{}, integral_constant<int, 2>{});
-        }
-    }
+    run_stages<NSTAGE>(nst, issue, stage);
 
-    float* dst = part_w + (int64_t)slice * ((int64_t)n_out * k_in + n_out);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2) {
-            const int kk = k0 + wk * 64 + b2 * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = n0 + wn * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (nn < n_out && kk < k_in) dst[(int64_t)nn * k_in + kk] = acc[a][b2][r];
-            }
-        }
+    const int64_t rec = slice * record_floats(n_out, k_in);
+    store_partial(acc, part_w + rec, n0 + wn * 64, k0 + wk * 64, n_out, k_in, lane);
     if (do_bias) {
         __syncthreads();  // every wave is done with the stage buffers
-        const int rg = tid >> 5, c4 = (tid & 31) * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bred[rg * TN + c4 + i] = bsum[i];
-        __syncthreads();
-        if (tid < TN) {
-            float t = 0.f;
-#pragma unroll
-            for (int r2 = 0; r2 < 8; ++r2) t += bred[r2 * TN + tid];
-            if (n0 + tid < n_out) part_b[(int64_t)slice * ((int64_t)n_out * k_in + n_out) + n0 + tid] = t;
-        }
+        fold_bias<TN, 8>(bred, bsum, tid, n0, n_out, part_b + rec);
     }
 #endif
 }
 
 // Which LDS-DMA kernel a bf16 problem runs on: 0 = none (register-staged kernels), 1 = 256 x 256, 2 = 256 x 128, 3 = 128 x 128
 inline int dma_variant(const Geometry& g) { return !g.dma ? 0 : (g.tile_k == 256 ? 1 : (g.tile_n == 256 ? 2 : 3)); }
+// the GELU operand exists on the 128 x 128 LDS-DMA tile only
+inline bool on_gelu_tile(const Geometry& g) { return dma_variant(g) == 3; }
+// what the bf16 kernels take at all (linear_wgrad_check_shape says why)
+inline bool bf16_shape_ok(int64_t rows, int n_out, int k_in) {
+    return rows > 0 && n_out > 0 && k_in > 0 && n_out % 4 == 0 && k_in % 8 == 0;
+}
 
 inline void launch_dma(int variant, bool any_gelu, dim3 grid, hipStream_t s, const MemberTable& tb, int64_t rows, const Geometry& g) {
     if (variant == 1)
@@ -751,6 +724,14 @@ inline void launch_dma(int variant, bool any_gelu, dim3 grid, hipStream_t s, con
         hipLaunchKernelGGL((wgrad_dma_kernel<2, 128, true>), grid, dim3(256), 0, s, tb, rows, g);
     else
         hipLaunchKernelGGL((wgrad_dma_kernel<2, 128>), grid, dim3(256), 0, s, tb, rows, g);
+}
+
+// The sum over a problem's `slices` partial records into dw / dbias, now or with the stream's queue of deferred reductions
+// (csrc/reduce_many.hip).  Without a bias the tail of each record is never written nor read
+inline int sum_slices(const float* part_w, int slices, int n_out, int k_in, float* dw, float* dbias, int accumulate, hipStream_t s) {
+    const int64_t n = (int64_t)n_out * k_in, rec = record_floats(n_out, k_in), count = dbias ? rec : n;
+    if (accumulate & HS_ACC_DEFER) return reduce_defer(part_w, rec, slices, n, count, dw, dbias, accumulate & 1, s);
+    return reduce_now(part_w, rec, slices, n, count, dw, dbias, accumulate & 1, s);
 }
 
 // One launch for several bf16 problems over the same token rows: possible when each of them, launched alone, takes the same
@@ -770,7 +751,7 @@ inline GroupPlan plan_group(const hs_wgrad_problem* p, int count, int64_t rows, 
     pl.grouped = dtype == HS_BF16 && count > 1;
     int tiles = 0;
     for (int i = 0; i < count && pl.grouped; ++i) {
-        if (p[i].n_out <= 0 || p[i].k_in <= 0 || p[i].n_out % 4 || p[i].k_in % 8) pl.grouped = false;
+        if (!bf16_shape_ok(rows, p[i].n_out, p[i].k_in)) pl.grouped = false;
         if (!pl.grouped) break;
         const Geometry gi = make_geometry(rows, p[i].n_out, p[i].k_in);
         const int v = dma_variant(gi);
@@ -778,35 +759,66 @@ inline GroupPlan plan_group(const hs_wgrad_problem* p, int count, int64_t rows, 
             pl.variant = v;
             pl.g = gi;
         }
-        if (v == 0 || v != pl.variant || (p[i].gelu_x && v != 3)) pl.grouped = false;
+        if (v == 0 || v != pl.variant || (p[i].gelu_x && !on_gelu_tile(gi))) pl.grouped = false;
         pl.first_tile[i] = tiles;
         pl.tiles_k[i] = gi.tiles_k;
         pl.any_gelu |= p[i].gelu_x ? 1 : 0;
         tiles += gi.tiles;
     }
     if (pl.grouped) {
-        Geometry& g = pl.g;
-        g.tiles = tiles;
-        int64_t want = ((int64_t)usable_cus() * (pl.variant == 1 ? 1 : 2)) / tiles;
-        const int64_t max_by_rows = (rows + 511) / 512;
-        if (want > max_by_rows) want = max_by_rows;
-        if (want > kMaxSlices) want = kMaxSlices;
-        if (want < 1) want = 1;
-        g.slices = (int)want;
-        const int64_t rps = (rows + g.slices - 1) / g.slices;
-        g.rows_per_slice = ((rps + kTok - 1) / kTok) * kTok;
-        g.per_xcd = (g.slices * g.tiles + 7) / 8;
+        pl.g.tiles = tiles;
+        plan_slices(pl.g, rows, pl.variant == 1 ? 1 : 2);
         for (int i = 0; i < count; ++i)  // longer slices than alone: every member must still fit the 32-bit buffer offsets
-            if (g.rows_per_slice * (int64_t)(p[i].n_out > p[i].k_in ? p[i].n_out : p[i].k_in) * 2 >= ((int64_t)1 << 31)) pl.grouped = false;
+            if (!slice_fits_dma(pl.g, p[i].n_out > p[i].k_in ? p[i].n_out : p[i].k_in, 2)) pl.grouped = false;
     }
     int64_t off = 0;
     for (int i = 0; i < count; ++i) {
         pl.offset[i] = off;
-        off += pl.grouped ? (int64_t)pl.g.slices * ((int64_t)p[i].n_out * p[i].k_in + p[i].n_out)
-                          : hs_linear_wgrad_workspace(rows, p[i].n_out, p[i].k_in);
+        off += pl.grouped ? pl.g.slices * record_floats(p[i].n_out, p[i].k_in) : hs_linear_wgrad_workspace(rows, p[i].n_out, p[i].k_in);
     }
     pl.total = off;
     return pl;
+}
+
+// an operand as a column block of a wider row-major matrix: row stride and first column, in elements
+struct ColumnBlock {
+    int ld, col0;
+};
+
+int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, float* workspace, int64_t rows, int n_out, int k_in,
+                      int accumulate, int dtype, void* stream, ColumnBlock yb, ColumnBlock xb, bool gelu_x) {
+    HS_CHECK_ARG(dy && x && dw && workspace, "null pointer");
+    // operands: 16-byte buffer-to-LDS chunks; dw / dbias: float4 read-modify-writes of the slice sum (csrc/reduce_many.hip)
+    HS_CHECK_ALIGNED("hs_linear_wgrad", 16, dy, x, dw, dbias, workspace);
+    if (int st = linear_wgrad_check_shape("hs_linear_wgrad", rows, n_out, k_in, dtype)) return st;
+    const Geometry g = dtype == HS_F32 ? make_geometry_f32(rows, n_out, k_in) : make_geometry(rows, n_out, k_in);
+    if (gelu_x && !(dtype == HS_BF16 && on_gelu_tile(g)))
+        return fail(HS_ERR_UNSUPPORTED, "hs_linear_wgrad_gelu: bf16 and the 128 x 128 LDS-DMA tile only (n_out <= 128-class shapes)");
+    const bool strided = yb.ld != n_out || xb.ld != k_in || yb.col0 || xb.col0;
+    if (strided) {  // column blocks of wider matrices: LDS-DMA kernels only, 32-bit offsets inside a token slice
+        if (!g.dma || !slice_fits_dma(g, yb.ld > xb.ld ? yb.ld : xb.ld, 2))
+            return fail(HS_ERR_UNSUPPORTED, "hs_linear_wgrad_ld: a token slice exceeds the 2 GiB buffer-offset range");
+    }
+    float* part_w = workspace;
+    float* part_b = dbias ? workspace + (int64_t)n_out * k_in : nullptr;  // bias partials live behind each slice's weight partial
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)(8 * g.per_xcd));
+    const uint16_t* dyp = (const uint16_t*)dy;
+    const uint16_t* xp = (const uint16_t*)x;
+    if (dtype == HS_F32)
+        hipLaunchKernelGGL(wgrad_dma_f32_kernel, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, part_w, part_b, rows, n_out,
+                           k_in, g);
+    else if (g.dma) {  // a group of one: the same slices, tiles and summation order as before the kernels took a table
+        MemberTable tb{};
+        tb.count = 1;
+        tb.m[0] = Member{dyp, xp, part_w, part_b, n_out, k_in, yb.ld, xb.ld, yb.col0, xb.col0, g.tiles_k, 0, gelu_x ? 1 : 0};
+        launch_dma(dma_variant(g), gelu_x, grid, s, tb, rows, g);
+    } else if (g.tile_n == 256)
+        hipLaunchKernelGGL(wgrad_kernel<4>, grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g);
+    else
+        hipLaunchKernelGGL(wgrad_kernel<2>, grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g);
+    HS_LAUNCH_CHECK("linear_wgrad");
+    return sum_slices(part_w, g.slices, n_out, k_in, dw, dbias, accumulate, s);
 }
 
 }  // namespace
@@ -836,28 +848,22 @@ int64_t hs_linear_wgrad_workspace(int64_t rows, int n_out, int k_in) {
     // the larger of the bf16 and fp32 geometries (the call does not know the dtype)
     const hs::Geometry g = hs::make_geometry(rows, n_out, k_in), f = hs::make_geometry_f32(rows, n_out, k_in);
     const int64_t a = g.slices + (g.chunks > 1 ? g.chunks : 0), b = f.slices + (f.chunks > 1 ? f.chunks : 0);
-    return (a > b ? a : b) * ((int64_t)n_out * k_in + n_out);
-}
-
-namespace {
-int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, float* workspace, int64_t rows, int n_out, int k_in,
-                      int accumulate, int dtype, void* stream, int ldy, int ldx, int yc0, int xc0, bool gelu_x = false);
+    return (a > b ? a : b) * hs::record_floats(n_out, k_in);
 }
 
 int hs_linear_wgrad(const void* dy, const void* x, float* dw, float* dbias, float* workspace, int64_t rows, int n_out,
                     int k_in, int accumulate, int dtype, void* stream) {
-    return linear_wgrad_impl(dy, x, dw, dbias, workspace, rows, n_out, k_in, accumulate, dtype, stream, n_out, k_in, 0, 0);
+    return hs::linear_wgrad_impl(dy, x, dw, dbias, workspace, rows, n_out, k_in, accumulate, dtype, stream, {n_out, 0}, {k_in, 0}, false);
 }
 
 int hs_linear_wgrad_gelu_supported(int64_t rows, int n_out, int k_in, int dtype) {
-    if (dtype != HS_BF16 || rows <= 0 || n_out <= 0 || k_in <= 0 || n_out % 4 || k_in % 8) return 0;
-    const hs::Geometry g = hs::make_geometry(rows, n_out, k_in);
-    return g.dma && g.tile_k != 256 && g.tile_n != 256;
+    if (dtype != HS_BF16 || !hs::bf16_shape_ok(rows, n_out, k_in)) return 0;
+    return hs::on_gelu_tile(hs::make_geometry(rows, n_out, k_in));
 }
 
 int hs_linear_wgrad_gelu(const void* dy, const void* h, float* dw, float* dbias, float* workspace, int64_t rows, int n_out, int k_in,
                          int accumulate, int dtype, void* stream) {
-    return linear_wgrad_impl(dy, h, dw, dbias, workspace, rows, n_out, k_in, accumulate, dtype, stream, n_out, k_in, 0, 0, true);
+    return hs::linear_wgrad_impl(dy, h, dw, dbias, workspace, rows, n_out, k_in, accumulate, dtype, stream, {n_out, 0}, {k_in, 0}, true);
 }
 
 int hs_linear_wgrad_ld(const void* dy, int64_t ldy, int64_t ycol0, const void* x, int64_t ldx, int64_t xcol0, float* dw, float* dbias,
@@ -865,55 +871,12 @@ int hs_linear_wgrad_ld(const void* dy, int64_t ldy, int64_t ycol0, const void* x
     HS_CHECK_ARG(ycol0 >= 0 && xcol0 >= 0 && ycol0 + n_out <= ldy && xcol0 + k_in <= ldx && ldy % 8 == 0 && ldx % 8 == 0 &&
                  ycol0 % 8 == 0 && xcol0 % 8 == 0 && ldy < (1 << 20) && ldx < (1 << 20),
                  "hs_linear_wgrad_ld: column blocks must lie inside the rows; strides and offsets are multiples of 8 elements");
-    return linear_wgrad_impl(dy, x, dw, dbias, workspace, rows, n_out, k_in, accumulate, HS_BF16, stream, (int)ldy, (int)ldx, (int)ycol0,
-                             (int)xcol0);
+    return hs::linear_wgrad_impl(dy, x, dw, dbias, workspace, rows, n_out, k_in, accumulate, HS_BF16, stream, {(int)ldy, (int)ycol0},
+                                 {(int)ldx, (int)xcol0}, false);
 }
-
-namespace {
-int linear_wgrad_impl(const void* dy, const void* x, float* dw, float* dbias, float* workspace, int64_t rows, int n_out, int k_in,
-                      int accumulate, int dtype, void* stream, int ldy, int ldx, int yc0, int xc0, bool gelu_x) {
-    using namespace hs;
-    HS_CHECK_ARG(dy && x && dw && workspace, "null pointer");
-    // operands: 16-byte buffer-to-LDS chunks; dw / dbias: float4 read-modify-writes of the slice sum (csrc/reduce_many.hip)
-    HS_CHECK_ALIGNED("hs_linear_wgrad", 16, dy, x, dw, dbias, workspace);
-    if (int st = linear_wgrad_check_shape("hs_linear_wgrad", rows, n_out, k_in, dtype)) return st;
-    Geometry g = dtype == HS_F32 ? make_geometry_f32(rows, n_out, k_in) : make_geometry(rows, n_out, k_in);
-    if (gelu_x && !(dtype == HS_BF16 && g.dma && g.tile_k != 256 && g.tile_n != 256))
-        return fail(HS_ERR_UNSUPPORTED, "hs_linear_wgrad_gelu: bf16 and the 128 x 128 LDS-DMA tile only (n_out <= 128-class shapes)");
-    const bool strided = ldy != n_out || ldx != k_in || yc0 || xc0;
-    if (strided) {  // column blocks of wider matrices: LDS-DMA kernels only, 32-bit offsets inside a token slice
-        if (!g.dma || g.rows_per_slice * (int64_t)(ldy > ldx ? ldy : ldx) * 2 >= ((int64_t)1 << 31))
-            return fail(HS_ERR_UNSUPPORTED, "hs_linear_wgrad_ld: a token slice exceeds the 2 GiB buffer-offset range");
-    }
-    const int64_t n = (int64_t)n_out * k_in, rec = n + n_out;
-    float* part_w = workspace;
-    float* part_b = dbias ? workspace + n : nullptr;  // bias partials live behind each slice's weight partial
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(8 * g.per_xcd));
-    const uint16_t* dyp = (const uint16_t*)dy;
-    const uint16_t* xp = (const uint16_t*)x;
-    if (dtype == HS_F32)
-        hipLaunchKernelGGL(wgrad_dma_f32_kernel, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, part_w, part_b, rows, n_out,
-                           k_in, g);
-    else if (g.dma) {  // a group of one: the same slices, tiles and summation order as before the kernels took a table
-        MemberTable tb{};
-        tb.count = 1;
-        tb.m[0] = Member{dyp, xp, part_w, part_b, n_out, k_in, ldy, ldx, yc0, xc0, g.tiles_k, 0, gelu_x ? 1 : 0};
-        launch_dma(dma_variant(g), gelu_x, grid, s, tb, rows, g);
-    } else if (g.tile_n == 256)
-        hipLaunchKernelGGL(wgrad_kernel<4>, grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g);
-    else
-        hipLaunchKernelGGL(wgrad_kernel<2>, grid, dim3(256), 0, s, dyp, xp, part_w, part_b, rows, n_out, k_in, g);
-    HS_LAUNCH_CHECK("linear_wgrad");
-    const int64_t count = dbias ? rec : n;  // without a bias the tail of each record is never written nor read
-    if (accumulate & HS_ACC_DEFER)  // the slice sum joins the stream's queue of deferred reductions (csrc/reduce_many.hip)
-        return reduce_defer(part_w, rec, g.slices, n, count, dw, dbias, accumulate & 1, s);
-    return reduce_now(part_w, rec, g.slices, n, count, dw, dbias, accumulate & 1, s);
-}
-}  // namespace
 
 int hs_linear_wgrad_group_variant(int64_t rows, int n_out, int k_in, int dtype) {
-    if (dtype != HS_BF16 || rows <= 0 || n_out <= 0 || k_in <= 0 || n_out % 4 || k_in % 8) return 0;
+    if (dtype != HS_BF16 || !hs::bf16_shape_ok(rows, n_out, k_in)) return 0;
     return hs::dma_variant(hs::make_geometry(rows, n_out, k_in));
 }
 
@@ -936,7 +899,7 @@ int hs_linear_wgrad_group(const hs_wgrad_problem* problems, int count, float* wo
         for (int i = 0; i < count; ++i) {
             const hs_wgrad_problem& p = problems[i];
             if (int st = linear_wgrad_impl(p.dy, p.x, p.dw, p.dbias, workspace + pl.offset[i], rows, p.n_out, p.k_in, p.accumulate, dtype,
-                                           stream, p.n_out, p.k_in, 0, 0, p.gelu_x != 0))
+                                           stream, {p.n_out, 0}, {p.k_in, 0}, p.gelu_x != 0))
                 return st;
         }
         return HS_OK;
@@ -955,10 +918,7 @@ int hs_linear_wgrad_group(const hs_wgrad_problem* problems, int count, float* wo
     HS_LAUNCH_CHECK("linear_wgrad_group");
     for (int i = 0; i < count; ++i) {  // one slice sum per member, with the group's slice count
         const hs_wgrad_problem& p = problems[i];
-        const int64_t n = (int64_t)p.n_out * p.k_in, rec = n + p.n_out, cnt = p.dbias ? rec : n;
-        const int st = (p.accumulate & HS_ACC_DEFER) ? reduce_defer(tb.m[i].part_w, rec, pl.g.slices, n, cnt, p.dw, p.dbias, p.accumulate & 1, s)
-                                                     : reduce_now(tb.m[i].part_w, rec, pl.g.slices, n, cnt, p.dw, p.dbias, p.accumulate & 1, s);
-        if (st) return st;
+        if (int st = sum_slices(tb.m[i].part_w, pl.g.slices, p.n_out, p.k_in, p.dw, p.dbias, p.accumulate, s)) return st;
     }
     return HS_OK;
 }

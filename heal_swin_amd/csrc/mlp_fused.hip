@@ -37,13 +37,10 @@ HS_DEFINE_SEED_EPOCH_SETTER(set_seed_epoch_mlp_fused)
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef unsigned int u32x2v __attribute__((__vector_size__(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kT = 32;  // tokens per tile
 constexpr float kLnEps = 1e-5f;
-__device__ constexpr uint32_t kOob = 0x7FFFFF00u;  // beyond every descriptor: the DMA writes zeros
 
 struct MlpParams {
     const uint16_t* x;    // [M, C]  forward: the residual stream (LayerNorm input);  backward: dy
@@ -116,8 +113,6 @@ __device__ __forceinline__ void st64(uint32_t addr, uint32_t a, uint32_t b) {
 }
 __device__ __forceinline__ void st128(uint32_t addr, const u32x4& v) { asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
 __device__ __forceinline__ bf16x8 as_frag(const u32x4& v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ float lo_f(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float hi_f(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 // sum over the 16 lanes of a DPP row: quad xor 1, xor 2, then the two mirror steps (sums are symmetric, any pairing works)
 __device__ __forceinline__ float row16_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
@@ -249,8 +244,8 @@ __global__ void __launch_bounds__(C * 4, 1) mlp_fused_kernel(MlpParams p) {
                     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        f[2 * e] = valid ? lo_f(mw[e]) : 0.f;
-                        f[2 * e + 1] = valid ? hi_f(mw[e]) : 0.f;
+                        f[2 * e] = valid ? bf_lo(mw[e]) : 0.f;
+                        f[2 * e + 1] = valid ? bf_hi(mw[e]) : 0.f;
                     }
                     if constexpr (DROP) {  // Mlp.drop behind fc2: y = x + rs * LN(drop(m)), as hs_layernorm_drop_fwd
                         if (dropping) {
@@ -290,8 +285,8 @@ __global__ void __launch_bounds__(C * 4, 1) mlp_fused_kernel(MlpParams p) {
                 if (keep_raw || add_res) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        f[2 * e] += lo_f(res[j][e]);
-                        f[2 * e + 1] += hi_f(res[j][e]);
+                        f[2 * e] += bf_lo(res[j][e]);
+                        f[2 * e + 1] += bf_hi(res[j][e]);
                     }
                 }
                 const u32x4 o = {pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
@@ -330,8 +325,8 @@ __global__ void __launch_bounds__(C * 4, 1) mlp_fused_kernel(MlpParams p) {
                         float f[8], s1 = 0.f, s2 = 0.f;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            f[2 * e] = valid ? lo_f(v[e]) : 0.f;
-                            f[2 * e + 1] = valid ? hi_f(v[e]) : 0.f;
+                            f[2 * e] = valid ? bf_lo(v[e]) : 0.f;
+                            f[2 * e + 1] = valid ? bf_hi(v[e]) : 0.f;
                             s1 += f[2 * e] + f[2 * e + 1];
                         }
                         const float mean = row16_sum(s1) * (1.f / C);
@@ -462,7 +457,7 @@ __global__ void __launch_bounds__(C * 4, 1) mlp_fused_kernel(MlpParams p) {
                 } else {
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        const f32x2 hx = {lo_f(hw[i][g][t]), hi_f(hw[i][g][t])};
+                        const f32x2 hx = {bf_lo(hw[i][g][t]), bf_hi(hw[i][g][t])};
                         v[t] *= gelu_grad2(hx);
                         if constexpr (DROP) {
                             if (dropping) v[t] *= drop2(t);

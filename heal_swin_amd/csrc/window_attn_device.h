@@ -6,8 +6,6 @@
 
 namespace hs {
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 constexpr float kNormEps = 1e-12f;             // F.normalize eps, swin_hp_transformer.py:143
 constexpr float kMaskLog2 = -100.f * kLog2e;  // hp_shifting.py:25, in the log2 domain
 // 1 / max(|x|, eps) from the squared norm: v_rsq_f32 (1 ulp) + a clamp instead of the correctly rounded sqrt and division hipcc

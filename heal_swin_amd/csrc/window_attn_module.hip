@@ -44,12 +44,10 @@ namespace {
 
 typedef unsigned int u32x2v __attribute__((__vector_size__(8)));
 typedef unsigned int u32x4v __attribute__((__vector_size__(16)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kWs = 64;
 constexpr int kRowB = 256;  // bytes per LDS tile row (C <= 128 bf16; rows of C = 96 are padded)
 constexpr float kLnEps = 1e-5f;
-__device__ constexpr uint32_t kOob = 0x7FFFFF00u;
 
 struct ModParams {
     const uint16_t* x;
