@@ -138,6 +138,12 @@ _SIGNATURES = {
     "hs_mlp_fused_drop_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_float, ctypes.c_uint64, c_i64, c_int, c_int, c_int, c_ptr],
     "hs_adam_step": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_float, c_ptr, c_float, c_float, c_float, c_float, c_int, c_ptr, c_ptr],
     "hs_adam_advance": [c_ptr, c_ptr],
+    "hs_grad_stats": [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr],
+    "hs_grad_guard_finalize": [c_ptr, c_i64, c_ptr, c_int, c_int, c_float, c_ptr, c_ptr, c_ptr, c_ptr],
+    "hs_adam_step_guarded": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_float, c_ptr, c_float, c_float, c_float, c_float, c_int, c_ptr, c_float,
+                             c_ptr, c_int, c_ptr],
+    "hs_adam_advance_guarded": [c_ptr, c_ptr, c_int, c_ptr, c_ptr],
+    "hs_grad_scale": [c_ptr, c_i64, c_float, c_ptr, c_ptr],
     "hs_split_bf16x3": [c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr],
     "hs_gelu_split3": [c_ptr, c_ptr, c_ptr, c_i64, c_int, ctypes.c_float, ctypes.c_uint64, c_ptr],
     "hs_linear_wgrad_ld": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr],
@@ -185,6 +191,7 @@ _OTHER = {
     "hs_status_string": ([c_int], ctypes.c_char_p),
     "hs_device_count": ([], c_int),
     "hs_get_reserved_cus": ([], c_int),
+    "hs_grad_guard_piece": ([], c_int),
     "hs_get_seed_epoch": ([], c_ptr),
     "hs_reduce_pending": ([c_ptr], c_int),
     "hs_layernorm_bwd_workspace": ([c_i64, c_int], c_i64),

@@ -12,7 +12,10 @@
 //   m += (g - m) (1 - b1);   v = b2 v + (1 - b2) g^2;   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // with the step count t = *step + 1 read from DEVICE memory (hs_adam_advance increments it after the last bucket), so that a
 // captured HIP graph of the whole training step replays with the right bias corrections.
-#include "hs_device.h"
+//
+// hs_adam_step_guarded is the same step behind the guard record of csrc/grad_guard.hip: the gradient is clamped / scaled by the
+// clip coefficient on its way out of the load, and a step whose gradients are not finite writes nothing.
+#include "hs_grad_guard.h"
 
 namespace hs {
 namespace {
@@ -46,7 +49,9 @@ __device__ __forceinline__ float adam_one(float& p, float g, float& m, float& v,
     return p;
 }
 
-__global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
+// GUARDED: every gradient element goes through guard_grad(., clip_value, coef) first
+template <bool GUARDED>
+__device__ __forceinline__ void adam_body(const AdamArgs& a, float clip_value, float coef) {
     __shared__ float corr[2];
     const float lr = a.lr_dev ? *a.lr_dev : a.lr;
     if (threadIdx.x == 0) {  // bias corrections in double, once per workgroup (torch forms them on the host in double)
@@ -59,7 +64,11 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i + 3 < a.n) {
         float4 p = *(const float4*)(a.p + i), m = *(const float4*)(a.m + i), v = *(const float4*)(a.v + i);
-        const float4 g = *(const float4*)(a.g + i);
+        float4 g = *(const float4*)(a.g + i);
+        if constexpr (GUARDED) {
+            g.x = guard_grad(g.x, clip_value, coef), g.y = guard_grad(g.y, clip_value, coef);
+            g.z = guard_grad(g.z, clip_value, coef), g.w = guard_grad(g.w, clip_value, coef);
+        }
         adam_one(p.x, g.x, m.x, v.x, lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.decoupled, inv_bc1, inv_sqrt_bc2);
         adam_one(p.y, g.y, m.y, v.y, lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.decoupled, inv_bc1, inv_sqrt_bc2);
         adam_one(p.z, g.z, m.z, v.z, lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.decoupled, inv_bc1, inv_sqrt_bc2);
@@ -71,7 +80,9 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
     } else {
         for (int64_t j = i; j < a.n; ++j) {
             float p = a.p[j], m = a.m[j], v = a.v[j];
-            adam_one(p, a.g[j], m, v, lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.decoupled, inv_bc1, inv_sqrt_bc2);
+            float g = a.g[j];
+            if constexpr (GUARDED) g = guard_grad(g, clip_value, coef);
+            adam_one(p, g, m, v, lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.decoupled, inv_bc1, inv_sqrt_bc2);
             a.p[j] = p;
             a.m[j] = m;
             a.v[j] = v;
@@ -80,25 +91,68 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) { adam_body<false>(a, 0.f, 1.f); }
+
+__global__ void __launch_bounds__(256) adam_guarded_kernel(const AdamArgs a, float clip_value, const hs_grad_guard* guard, int skip_nonfinite) {
+    if (skip_nonfinite && !guard->finite) return;  // (the same for every thread of the grid: p, m, v and the bf16 copy stay as they are)
+    adam_body<true>(a, clip_value, guard->clip_coef);
+}
+
 __global__ void adam_advance_kernel(int64_t* step) { *step += 1; }
+
+__global__ void adam_advance_guarded_kernel(int64_t* step, const hs_grad_guard* guard, int skip_nonfinite, int64_t* skipped) {
+    const bool skip = skip_nonfinite && !guard->finite;
+    *step += skip ? 0 : 1;
+    *skipped += skip ? 1 : 0;
+}
 
 }  // namespace
 }  // namespace hs
+
+// the argument checks of hs_adam_step and hs_adam_step_guarded
+static int adam_check(const char* who, const hs::AdamArgs& a) {
+    HS_CHECK_ARG(a.p && a.g && a.m && a.v && a.step, "%s: null pointer", who);
+    HS_CHECK_ARG(a.n > 0 && a.n < ((int64_t)1 << 40), "%s: bad length", who);
+    HS_CHECK_ALIGNED(who, 16, a.p, a.g, a.m, a.v);
+    HS_CHECK_ALIGNED(who, 8, a.lowp);
+    HS_CHECK_ARG(a.beta1 >= 0.f && a.beta1 < 1.f && a.beta2 >= 0.f && a.beta2 < 1.f && a.eps >= 0.f, "%s: bad hyper-parameters", who);
+    return HS_OK;
+}
 
 extern "C" {
 
 int hs_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, const float* lr_dev, float beta1,
                  float beta2, float eps, float weight_decay, int decoupled, const int64_t* step, void* stream) {
     using namespace hs;
-    HS_CHECK_ARG(p && g && m && v && step, "hs_adam_step: null pointer");
-    HS_CHECK_ARG(n > 0 && n < ((int64_t)1 << 40), "hs_adam_step: bad length");
-    HS_CHECK_ALIGNED("hs_adam_step", 16, p, g, m, v);
-    HS_CHECK_ALIGNED("hs_adam_step (bf16 copy)", 8, p_bf16);
-    HS_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "hs_adam_step: bad hyper-parameters");
     AdamArgs a{p, g, m, v, (uint16_t*)p_bf16, n, lr, lr_dev, beta1, beta2, eps, weight_decay, decoupled, step};
+    if (const int st = adam_check("hs_adam_step", a)) return st;
     const int64_t blocks = (n + 1023) / 1024;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     HS_LAUNCH_CHECK("adam_step");
+    return HS_OK;
+}
+
+int hs_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, const float* lr_dev, float beta1,
+                         float beta2, float eps, float weight_decay, int decoupled, const int64_t* step, float clip_value,
+                         const hs_grad_guard* guard, int skip_nonfinite, void* stream) {
+    using namespace hs;
+    AdamArgs a{p, g, m, v, (uint16_t*)p_bf16, n, lr, lr_dev, beta1, beta2, eps, weight_decay, decoupled, step};
+    if (const int st = adam_check("hs_adam_step_guarded", a)) return st;
+    HS_CHECK_ARG(guard, "hs_adam_step_guarded: null pointer");
+    HS_CHECK_ALIGNED("hs_adam_step_guarded (guard)", 16, guard);
+    HS_CHECK_ARG(!(clip_value != clip_value), "hs_adam_step_guarded: clip_value is NaN");
+    const int64_t blocks = (n + 1023) / 1024;
+    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, clip_value, guard, skip_nonfinite);
+    HS_LAUNCH_CHECK("adam_step_guarded");
+    return HS_OK;
+}
+
+int hs_adam_advance_guarded(int64_t* step, const hs_grad_guard* guard, int skip_nonfinite, int64_t* skipped, void* stream) {
+    using namespace hs;
+    HS_CHECK_ARG(step && guard && skipped, "hs_adam_advance_guarded: null pointer");
+    HS_CHECK_ALIGNED("hs_adam_advance_guarded (guard)", 16, guard);
+    hipLaunchKernelGGL(adam_advance_guarded_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, guard, skip_nonfinite, skipped);
+    HS_LAUNCH_CHECK("adam_advance_guarded");
     return HS_OK;
 }
 

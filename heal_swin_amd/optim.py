@@ -15,18 +15,132 @@ one HIP graph (`graphs.GraphedTrainStep`, `bench.py --graph`).
 It is a torch.optim.Optimizer: learning-rate schedulers act on `param_groups[0]["lr"]` (read on the host at every `step()`; under
 graph replay pass `lr` as a 0-dim CUDA tensor and update it in place), `state_dict()` / `load_state_dict()` carry `exp_avg`,
 `exp_avg_sq` and `step` per parameter in torch.optim.Adam's layout.  One parameter group, GPU only -- there is no CPU path.
+
+Guard rails (the reference trainer's gradient_clip_val / gradient_clip_algorithm, track_grad_norm, terminate_on_nan:
+training/train_config.py:65-66,76,104): `max_grad_norm=` / `clip_value=`, `track_grad_norm=True`, `skip_nonfinite=True`.  With any of
+them `step()` first measures the buckets (`GradGuard`: one read-only pass, csrc/grad_guard.hip) and then runs the guarded Adam
+launches, which take the clip coefficient and the finite flag from device memory -- no host read, the step stays capturable.
 """
+import math
+
 import torch
 
 from . import _lib, ops
 from ._lib import check, lib, ptr, stream_ptr
 
 
+def grad_piece():
+    """PIECE: the most elements one item of the guard's table covers (a compile-time constant of csrc/grad_guard.hip)."""
+    return int(lib.hs_grad_guard_piece())
+
+
+def guard_tables(layout, piece):
+    """The tables `hs_grad_stats` / `hs_grad_guard_finalize` are driven by (pure host code).
+    layout: per bucket, a list of (parameter index, element offset in the bucket, numel); offsets are multiples of 4.
+    Returns (items, params): items[b] = [(start, len), ...] for bucket b -- every parameter cut into consecutive slices of at most
+    `piece` elements, no slice crossing a parameter boundary -- and params[i] = (first item, item count) of parameter i, items
+    numbered through all buckets in order."""
+    n_params = sum(len(bucket) for bucket in layout)
+    items, params, first = [], [None] * n_params, 0
+    for bucket in layout:
+        cur = []
+        for index, off, numel in sorted(bucket, key=lambda e: e[1]):
+            if off % 4 or piece % 4:
+                raise ValueError("a parameter's slot and the piece size must be multiples of 4 elements (16-byte loads)")
+            if not 0 <= index < n_params or params[index] is not None:
+                raise ValueError("parameter indices must be 0 ... n - 1, each once")
+            count = -(-numel // piece)
+            cur += [(off + k * piece, min(piece, numel - k * piece)) for k in range(count)]
+            params[index] = (first, count)
+            first += count
+        items.append(cur)
+    return items, params
+
+
+def _norm_kind(norm_type):
+    norm_type = float(norm_type)
+    if norm_type not in (2.0, math.inf):
+        raise ValueError("the gradient guard measures the 2-norm or the inf-norm")
+    return norm_type
+
+
+class GradGuard:
+    """Norms of the gradients in a parallel.GradBucketAllReduce's buckets, and the device record a guarded step acts on.
+
+    `measure()` is one `hs_grad_stats` launch per bucket plus `hs_grad_guard_finalize`, all on the current stream and capturable;
+    afterwards `total_norm` (0-dim fp32), `param_norms` ([n_params] fp32, in `sink.params` order), `clip_coef` and `finite` hold the
+    result ON THE DEVICE.  Sums are fp64 in an order fixed by the tables built here once: the same buckets give the same bits,
+    on every rank of a data-parallel run after the exchange."""
+
+    def __init__(self, sink, norm_type=2.0):
+        self.norm_type = _norm_kind(norm_type)
+        self.sink = sink
+        if not sink.buckets or not sink.buckets[0].is_cuda:
+            raise RuntimeError("GradGuard runs on the gradient buckets of an MI355X (HIP) device; there is no CPU path")
+        dev = sink.buckets[0].device
+        layout = [[] for _ in sink.buckets]
+        for i, p in enumerate(sink.params):
+            b = sink._where[p]
+            layout[b].append((i, sink._views[p].storage_offset() - sink.buckets[b].storage_offset(), p.numel()))
+        items, params = guard_tables(layout, grad_piece())
+        self._items = [torch.tensor(it, dtype=torch.int64, device=dev).reshape(len(it), 2) for it in items]
+        self._first = [sum(len(it) for it in items[:b]) for b in range(len(items))]
+        self.n_items = sum(len(it) for it in items)
+        self._params = torch.tensor(params, dtype=torch.int32, device=dev).reshape(len(params), 2)
+        self.partials = torch.zeros(max(self.n_items, 1), 2, dtype=torch.float64, device=dev)  # per item: sum of squares, max |g|
+        self._work = torch.zeros(len(params), 2, dtype=torch.float64, device=dev)
+        self.param_norms = torch.zeros(len(params), dtype=torch.float32, device=dev)
+        self.record = torch.zeros(4, dtype=torch.float32, device=dev)  # hs_grad_guard: total_norm, clip_coef, finite (int32), -
+        self.record[1] = 1.0
+        self.total_norm, self.clip_coef = self.record[0], self.record[1]
+        self.finite = self.record.view(torch.int32)[2]
+
+    def measure(self, max_norm=None):
+        """Launch the measurement of the buckets as they are now; max_norm: clip_coef = min(1, max_norm / (total_norm + 1e-6)),
+        None: 1.  Returns `total_norm` (a device tensor; nothing is read on the host)."""
+        s = stream_ptr(self.record.device)
+        for G, items, first in zip(self.sink.buckets, self._items, self._first):
+            if len(items):
+                check(lib.hs_grad_stats(ptr(G), G.numel(), ptr(items), len(items), ptr(self.partials[first:]), s), "hs_grad_stats")
+        check(lib.hs_grad_guard_finalize(ptr(self.partials), self.n_items, ptr(self._params), self._params.shape[0],
+                                         int(self.norm_type == math.inf), -1.0 if max_norm is None else float(max_norm),
+                                         ptr(self.param_norms), ptr(self._work), ptr(self.record), s), "hs_grad_guard_finalize")
+        return self.total_norm
+
+    def scale_(self, clip_value=None):
+        """Clamp the buckets to +-clip_value (if given) and scale them by the measured `clip_coef`, in place (`hs_grad_scale`)."""
+        s = stream_ptr(self.record.device)
+        for G in self.sink.buckets:
+            check(lib.hs_grad_scale(ptr(G), G.numel(), 0.0 if clip_value is None else float(clip_value), ptr(self.record), s), "hs_grad_scale")
+
+    def named_norms(self, model):
+        """{"grad_<p>_norm_<parameter name>": float, ..., "grad_<p>_norm_total": float} of the last `measure()`, <p> the norm type
+        (2.0 or inf): the keys Lightning's track_grad_norm logs.  SYNCHRONISES: the norms are copied to the host."""
+        names = {id(p): n for n, p in model.named_parameters()}
+        values = self.param_norms.tolist()
+        out = {f"grad_{self.norm_type}_norm_{names[id(p)]}": v for p, v in zip(self.sink.params, values) if id(p) in names}
+        out[f"grad_{self.norm_type}_norm_total"] = float(self.total_norm)
+        return out
+
+
 class FlatAdam(torch.optim.Optimizer):
     def __init__(self, params, grad_sink, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
-                 model=None, lowp_dtype=torch.bfloat16):
+                 model=None, lowp_dtype=torch.bfloat16, max_grad_norm=None, clip_value=None, norm_type=2.0, skip_nonfinite=False,
+                 track_grad_norm=False):
         """grad_sink: the parallel.GradBucketAllReduce that owns the gradients of exactly these parameters.
-        model: a SwinHPTransformerSys whose bf16 parameter copies this optimizer should keep current (optional)."""
+        model: a SwinHPTransformerSys whose bf16 parameter copies this optimizer should keep current (optional).
+        max_grad_norm: clip the gradients to this total norm (`norm_type` 2 or inf) as torch.nn.utils.clip_grad_norm_ does.
+        clip_value: or clamp every gradient element to +-clip_value as torch.nn.utils.clip_grad_value_ does (not both).
+        skip_nonfinite: a step whose gradients hold a NaN or an inf changes nothing and counts in `skipped_steps`; without it such
+        a gradient propagates as in torch.
+        track_grad_norm: measure the norms at every step (`grad_norm`, `param_grad_norms`, `guard.named_norms(model)`)."""
+        if max_grad_norm is not None and clip_value is not None:
+            raise ValueError("give max_grad_norm (clipping by norm) or clip_value (clipping by value), not both")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive")
+        if clip_value is not None and not (float(clip_value) > 0.0 and math.isfinite(float(clip_value))):
+            raise ValueError("clip_value must be positive and finite")
+        norm_type = _norm_kind(norm_type)
         params = [p for p in params if p.requires_grad]
         if not params or not all(p.is_cuda and p.dtype == torch.float32 for p in params):
             raise RuntimeError("FlatAdam runs on fp32 master parameters on an MI355X (HIP) device; there is no CPU path")
@@ -42,6 +156,12 @@ class FlatAdam(torch.optim.Optimizer):
         self.lowp_dtype = lowp_dtype if model is not None else None
         dev = params[0].device
         self._step = torch.zeros((), dtype=torch.int64, device=dev)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.clip_value = None if clip_value is None else float(clip_value)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._skipped = torch.zeros((), dtype=torch.int64, device=dev)
+        guarded = self.max_grad_norm is not None or self.clip_value is not None or self.skip_nonfinite or bool(track_grad_norm)
+        self.guard = GradGuard(grad_sink, norm_type) if guarded else None
         self._flat_p, self._flat_m, self._flat_v, self._flat_lowp = [], [], [], []
         self._lowp_view = {}
         with torch.no_grad():
@@ -76,6 +196,26 @@ class FlatAdam(torch.optim.Optimizer):
         """The bf16 view of parameter p that `step()` keeps current, or None (other dtype / foreign parameter)."""
         return self._lowp_view.get(id(p)) if dtype == self.lowp_dtype else None
 
+    @property
+    def grad_norm(self):
+        """Total gradient norm (before clipping) of the last guarded step: a 0-dim fp32 device tensor."""
+        return self._guard().total_norm
+
+    @property
+    def param_grad_norms(self):
+        """Per-parameter gradient norms of the last guarded step: [n_params] fp32 on the device, in the sink's parameter order."""
+        return self._guard().param_norms
+
+    @property
+    def skipped_steps(self):
+        """Steps `skip_nonfinite` has dropped so far: a 0-dim int64 device tensor (not part of state_dict())."""
+        return self._skipped
+
+    def _guard(self):
+        if self.guard is None:
+            raise RuntimeError("this FlatAdam measures no gradient norms: pass max_grad_norm, clip_value, skip_nonfinite or track_grad_norm")
+        return self.guard
+
     def zero_grad(self, set_to_none=False):  # gradients are the sink's bucket views: zeroed in place, never detached
         self.sink.zero_grad()
 
@@ -93,11 +233,20 @@ class FlatAdam(torch.optim.Optimizer):
         b1, b2 = grp["betas"]
         dev = self._step.device
         s = stream_ptr(dev)
-        for P, G, M, V, S in zip(self._flat_p, self.sink.buckets, self._flat_m, self._flat_v, self._flat_lowp):
-            check(lib.hs_adam_step(ptr(P), ptr(G), ptr(M), ptr(V), ptr(S), P.numel(), 0.0 if lr_dev is not None else float(lr), ptr(lr_dev),
-                                   float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]),
-                                   int(grp["decoupled_weight_decay"]), ptr(self._step), s), "hs_adam_step")
-        check(lib.hs_adam_advance(ptr(self._step), s), "hs_adam_advance")
+        hyper = (0.0 if lr_dev is not None else float(lr), ptr(lr_dev), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]),
+                 int(grp["decoupled_weight_decay"]), ptr(self._step))
+        buffers = zip(self._flat_p, self.sink.buckets, self._flat_m, self._flat_v, self._flat_lowp)
+        if self.guard is None:
+            for P, G, M, V, S in buffers:
+                check(lib.hs_adam_step(ptr(P), ptr(G), ptr(M), ptr(V), ptr(S), P.numel(), *hyper, s), "hs_adam_step")
+            check(lib.hs_adam_advance(ptr(self._step), s), "hs_adam_advance")
+        else:  # measure, then step on what the device record says: clip coefficient and finite flag never visit the host
+            self.guard.measure(self.max_grad_norm)
+            rec, skip = ptr(self.guard.record), int(self.skip_nonfinite)
+            for P, G, M, V, S in buffers:
+                check(lib.hs_adam_step_guarded(ptr(P), ptr(G), ptr(M), ptr(V), ptr(S), P.numel(), *hyper, self.clip_value or 0.0, rec, skip, s),
+                      "hs_adam_step_guarded")
+            check(lib.hs_adam_advance_guarded(ptr(self._step), rec, skip, ptr(self._skipped), s), "hs_adam_advance_guarded")
         # the update went through raw pointers (no parameter `_version` moved): caches keyed by weight contents -- the bf16x3
         # splits of fp32 weights, ops._weight_split -- are told here, also for layers used outside a model's forward
         ops.RT.weight_epoch += 1

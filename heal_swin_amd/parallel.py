@@ -33,6 +33,24 @@ def _graph_task_id():
     return fn() if fn is not None else None
 
 
+def clip_grad_norm_(sink, max_norm, norm_type=2.0):
+    """torch.nn.utils.clip_grad_norm_ over the gradients of a GradBucketAllReduce on a GPU: one read-only pass over the flat buckets
+    for the norm (optim.GradGuard), then the buckets are scaled in place by min(1, max_norm / (norm + 1e-6)) (`hs_grad_scale`; nothing
+    is written when that is 1).  For callers that keep another optimizer (torch.optim.Adam(fused=True) in the drop-in wiring); with
+    optim.FlatAdam pass `max_grad_norm=` instead and the scale rides in the step.  Returns the total norm before clipping as a
+    0-dim device tensor; nothing is read on the host."""
+    from .optim import GradGuard
+    if not float(max_norm) >= 0.0:
+        raise ValueError("max_norm must not be negative")
+    guards = sink.__dict__.setdefault("_grad_guards", {})
+    guard = guards.get(float(norm_type))
+    if guard is None:
+        guard = guards[float(norm_type)] = GradGuard(sink, norm_type)
+    guard.measure(max_norm)
+    guard.scale_()
+    return guard.total_norm.clone()
+
+
 class GradBucketAllReduce:
     def __init__(self, params, bucket_bytes=64 << 20, process_group=None, async_wgrad=False, direct_wgrad=True,
                  exchange_single_rank=False, comm_dtype=None, reserved_cus="auto", slot=None):

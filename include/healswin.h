@@ -23,9 +23,9 @@
  *   hs_gemm_nt, hs_mlp_fused_*, hs_window_attn_module_*, hs_layernorm_* / hs_add_layernorm_*, hs_ln_head_*,
  *   hs_expand_ln_head_* (labels, targets, class weights and predictions excepted: single elements), hs_patch_merge_*,
  *   hs_patch_expand_*, hs_linear_wgrad* (members of a group and the destinations of sums queued for hs_reduce_flush included),
- *   hs_gelu_*, hs_residual_drop and hs_adam_step (its bf16 copy: 8 bytes) must therefore be 16-byte aligned: activations,
- *   weights, biases, gamma / beta, workspaces and gradient destinations alike.  They check it before anything is launched and
- *   return HS_ERR_MISALIGNED; the entry points that chain others check every pointer first.
+ *   hs_gelu_*, hs_residual_drop, hs_adam_step / hs_adam_step_guarded (their bf16 copy: 8 bytes), hs_grad_stats and hs_grad_scale must
+ *   therefore be 16-byte aligned: activations, weights, biases, gamma / beta, workspaces and gradient destinations alike.  They
+ *   check it before anything is launched and return HS_ERR_MISALIGNED; the entry points that chain others check every pointer first.
  *   Entry points that address single elements take any naturally aligned pointer: hs_rel_bias_*, hs_cos_head_scale_*,
  *   hs_transpose_many_16 (whose job table lives on the device and cannot be checked), and those that choose between a vector
  *   and a scalar path from the pointer (hs_gather_rows, the flat / depth data paths, the evaluation kernels).
@@ -473,6 +473,54 @@ int hs_mlp_fused_drop_bwd(const void* dy, const void* h, const void* w2_t, const
 int hs_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, const float* lr_dev, float beta1,
                  float beta2, float eps, float weight_decay, int decoupled, const int64_t* step, void* stream);
 int hs_adam_advance(int64_t* step, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Guard rails of the flat optimizer step: gradient norms, clipping and the non-finite skip -- the reference trainer's
+ * gradient_clip_val / gradient_clip_algorithm, track_grad_norm and terminate_on_nan (training/train_config.py:65-66,76,104) --
+ * as ONE read-only pass over the flat gradient buckets, everything decided on the device (capturable in a HIP graph).
+ *
+ *   hs_grad_stats      one launch per bucket g [dev] f32[n], 16-byte aligned.  items [dev] int64[n_items][2] = (start, len) in
+ *                      elements of g: a slice of ONE parameter, start a multiple of 4, 0 < len <= hs_grad_guard_piece(),
+ *                      start + len <= n (an item outside g reads nothing and records NaN).  One wavefront per item; writes
+ *                      partials [dev] f64[n_items][2] = (sum of squares, max |g|), every element converted to double before it
+ *                      is squared, every sum in double.  A NaN element makes both records NaN.
+ *   hs_grad_guard_finalize   partials = the n_items records of ALL buckets, params [dev] int32[n_params][2] = (first item, item
+ *                      count) of each parameter in that numbering (a parameter outside the records reads nothing and gets NaN).
+ *                      Folds the items of a parameter (one wavefront each) and the parameters into the total, in an order fixed
+ *                      by the two tables alone: no atomics, nothing depends on the grid, the CU count or hs_set_reserved_cus, so
+ *                      two calls on the same gradients give the same bits -- on every rank of a data-parallel run that holds
+ *                      the same averaged buckets.  Writes
+ *                      param_norm [dev] f32[n_params] (norm_inf == 0: the 2-norm; != 0: max |g|, exact) and *guard:
+ *                          total_norm   the norm of all gradients, before clipping
+ *                          clip_coef    min(1, max_norm / (total_norm + 1e-6)) in fp32, evaluated as
+ *                                       torch.nn.utils.clip_grad_norm_ evaluates it (reciprocal, then product); 1 when
+ *                                       max_norm < 0 (no clipping by norm)
+ *                          finite       1 if the total sum of squares is finite, else 0
+ *                      work [dev] f64[n_params][2]: scratch.  Two small launches.
+ *   hs_adam_step_guarded     hs_adam_step on the gradient  clamp(g, -clip_value, clip_value) [clip_value > 0]  * guard->clip_coef
+ *                      (weight decay of the non-decoupled form is added after that: torch's clip_grad_*_ followed by step()).
+ *                      With skip_nonfinite != 0 and guard->finite == 0 the launch writes nothing.  With clip_coef == 1,
+ *                      finite == 1 and clip_value <= 0 the result is bit-identical to hs_adam_step.
+ *   hs_adam_advance_guarded  adds 1 to *step, or -- skip_nonfinite != 0 and guard->finite == 0 -- 0 to *step and 1 to *skipped.
+ *   hs_grad_scale      the same clamp and scale applied in place to a bucket (for callers that keep another optimizer).
+ * No allocation, no synchronisation.  HS_ERR_INVALID_ARG: null pointer, n <= 0; HS_ERR_MISALIGNED: g, p, m, v, partials, work,
+ * items not 16-byte aligned (p_bf16, params: 8; guard: 16).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    float total_norm;
+    float clip_coef;
+    int32_t finite;
+    int32_t reserved;
+} hs_grad_guard;
+int hs_grad_guard_piece(void);
+int hs_grad_stats(const float* g, int64_t n, const int64_t* items, int n_items, double* partials, void* stream);
+int hs_grad_guard_finalize(const double* partials, int64_t n_items, const int32_t* params, int n_params, int norm_inf, float max_norm,
+                           float* param_norm, double* work, hs_grad_guard* guard, void* stream);
+int hs_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, const float* lr_dev, float beta1,
+                         float beta2, float eps, float weight_decay, int decoupled, const int64_t* step, float clip_value,
+                         const hs_grad_guard* guard, int skip_nonfinite, void* stream);
+int hs_adam_advance_guarded(int64_t* step, const hs_grad_guard* guard, int skip_nonfinite, int64_t* skipped, void* stream);
+int hs_grad_scale(float* g, int64_t n, float clip_value, const hs_grad_guard* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused WindowAttention MODULE forward (inference form here, training form and the module backward below): the whole of WindowAttention.forward,
