@@ -210,6 +210,8 @@ int hs_gelu_split3(const float* dy, const float* x, void* out3, int64_t rows, in
     using namespace hs;
     HS_CHECK_ARG(x && out3 && rows > 0 && k > 0 && k % 4 == 0, "hs_gelu_split3: null pointer, or k not a positive multiple of 4");
     HS_CHECK_ARG(drop_p >= 0.f && drop_p <= 1.f, "drop_p must be in [0, 1]");
+    HS_CHECK_ALIGNED("hs_gelu_split3", 16, x, dy);  // float4 loads
+    HS_CHECK_ALIGNED("hs_gelu_split3", 8, out3);    // uint2 stores
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(grid_for(rows * k, 4)), block(256);
     const bool drop = drop_p > 0.f;

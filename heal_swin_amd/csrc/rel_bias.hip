@@ -126,13 +126,15 @@ int hs_rel_bias_gather_many(const void* const* tables, const int* heads, int cou
                             int table_rows, int window_size, void* stream) {
     HS_CHECK_ARG(tables && heads && rel_idx && bias_base && count > 0 && table_rows > 0 && window_size > 0, "hs_rel_bias_gather_many: bad arguments");
     const int ws2 = window_size * window_size;
+    // (every job is checked before the first chunk is launched: a bad job leaves all outputs untouched)
+    for (int j = 0; j < count; ++j)
+        HS_CHECK_ARG(tables[j] && heads[j] > 0, "hs_rel_bias_gather_many: null table or no heads (job %d)", j);
     int first = 0;
     for (int j0 = 0; j0 < count; j0 += kManyMax) {
         GatherJobs jobs{};
         const int n = count - j0 < kManyMax ? count - j0 : kManyMax;
         int max_heads = 0;
         for (int j = 0; j < n; ++j) {
-            HS_CHECK_ARG(tables[j0 + j] && heads[j0 + j] > 0, "hs_rel_bias_gather_many: null table or no heads (job %d)", j0 + j);
             jobs.table[j] = (const float*)tables[j0 + j];
             jobs.heads[j] = heads[j0 + j];
             jobs.first_head[j] = first;
@@ -150,12 +152,13 @@ int hs_rel_bias_scatter_grad_sorted_many(const void* const* dbias, void* const* 
                                          const int32_t* order, const int32_t* offsets, int table_rows, int window_size, void* stream) {
     HS_CHECK_ARG(dbias && dtables && heads && accumulate && order && offsets && count > 0 && table_rows > 0 && window_size > 0,
                  "hs_rel_bias_scatter_grad_sorted_many: bad arguments");
+    for (int j = 0; j < count; ++j)  // (before the first chunk is launched)
+        HS_CHECK_ARG(dbias[j] && dtables[j] && heads[j] > 0, "hs_rel_bias_scatter_grad_sorted_many: null pointer or no heads (job %d)", j);
     for (int j0 = 0; j0 < count; j0 += kManyMax) {
         ScatterJobs jobs{};
         const int n = count - j0 < kManyMax ? count - j0 : kManyMax;
         int max_heads = 0;
         for (int j = 0; j < n; ++j) {
-            HS_CHECK_ARG(dbias[j0 + j] && dtables[j0 + j] && heads[j0 + j] > 0, "hs_rel_bias_scatter_grad_sorted_many: null pointer or no heads (job %d)", j0 + j);
             jobs.dbias[j] = (const float*)dbias[j0 + j];
             jobs.dtable[j] = (float*)dtables[j0 + j];
             jobs.heads[j] = heads[j0 + j];
@@ -172,12 +175,13 @@ int hs_rel_bias_scatter_grad_sorted_many(const void* const* dbias, void* const* 
 int hs_cos_head_scale_many(const void* const* logit_scale, const void* const* dscale, void* const* out, const int* heads, const int* accumulate,
                            int count, void* stream) {
     HS_CHECK_ARG(logit_scale && out && heads && count > 0, "hs_cos_head_scale_many: bad arguments");
+    for (int j = 0; j < count; ++j)  // (before the first chunk is launched)
+        HS_CHECK_ARG(logit_scale[j] && out[j] && heads[j] > 0 && heads[j] <= 64,
+                     "hs_cos_head_scale_many: null pointer or head count outside [1, 64] (job %d)", j);
     for (int j0 = 0; j0 < count; j0 += kManyMax) {
         ScaleJobs jobs{};
         const int n = count - j0 < kManyMax ? count - j0 : kManyMax;
         for (int j = 0; j < n; ++j) {
-            HS_CHECK_ARG(logit_scale[j0 + j] && out[j0 + j] && heads[j0 + j] > 0 && heads[j0 + j] <= 64,
-                         "hs_cos_head_scale_many: null pointer or head count outside [1, 64] (job %d)", j0 + j);
             jobs.ls[j] = (const float*)logit_scale[j0 + j];
             jobs.dscale[j] = dscale ? (const float*)dscale[j0 + j] : nullptr;
             jobs.out[j] = (float*)out[j0 + j];

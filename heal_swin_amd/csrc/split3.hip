@@ -39,6 +39,8 @@ int hs_split_bf16x3(const float* x, void* out, int64_t rows, int k, int mode, vo
     HS_CHECK_ARG(x && out, "hs_split_bf16x3: null pointer");
     HS_CHECK_ARG(rows > 0 && k > 0 && k % 4 == 0, "hs_split_bf16x3: k must be a positive multiple of 4");
     HS_CHECK_ARG(mode == 0 || mode == 1, "hs_split_bf16x3: mode 0 ([hi|hi|lo]) or 1 ([hi|lo|hi])");
+    HS_CHECK_ALIGNED("hs_split_bf16x3", 16, x);  // float4 loads
+    HS_CHECK_ALIGNED("hs_split_bf16x3", 8, out);  // uint2 stores (a row is 6 k bytes, k a multiple of 4)
     const int64_t total = rows * (k / 4);
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;

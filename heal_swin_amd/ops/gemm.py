@@ -191,7 +191,7 @@ def _probe_mm_out_dtype(device):
 
 def split3(x2d, mode):
     """bf16 [rows, 3 k] = [hi | hi | lo] (mode 0) or [hi | lo | hi] (mode 1) of fp32 x2d [rows, k] (`hs_split_bf16x3`)."""
-    x2d = x2d.contiguous()
+    x2d = _aligned(x2d.contiguous())  # (float4 loads: a row slice of a wider tensor may start anywhere)
     key = (x2d.data_ptr(), tuple(x2d.shape), x2d._version, mode)
     for kk, _, t in _SPLIT_MEMO:
         if kk == key:
@@ -253,7 +253,7 @@ def _weight_split(w2d, transposed):
     hit = _WSPLIT.get(key)
     if hit is not None and hit[0] == w2d._version and hit[1] == RT.weight_epoch:
         return hit[3]
-    src = w2d.t().contiguous() if transposed else w2d.contiguous()
+    src = _aligned(w2d.t().contiguous() if transposed else w2d.contiguous())  # (a view into a flat parameter buffer)
     rows, k = src.shape
     out = torch.empty((rows, 3 * k), dtype=torch.bfloat16, device=src.device)
     check(lib.hs_split_bf16x3(ptr(src), ptr(out), rows, k, 1, stream_ptr(src.device)), "hs_split_bf16x3")

@@ -6,7 +6,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
-from .runtime import RT, _cast_param, _defer_flag, _defer_keep, _draw_seed, _extras, _f32, _require_gpu, _timed  # noqa: F401
+from .runtime import RT, _aligned, _cast_param, _defer_flag, _defer_keep, _draw_seed, _extras, _f32, _require_gpu, _timed  # noqa: F401
 from .norm import _norm_param_grads, _norm_param_result  # noqa: F401
 from .gemm import (_Split, _bf16x3_ok, _cast_param_t, _input_grad, _lib_linear, _lib_matmul, _param_grads, _split_of, gemm_nt, own_gemm_legal, own_gemm_ok)  # noqa: F401
 
@@ -36,6 +36,7 @@ class MlpFn(torch.autograd.Function):
             x3 = _split_of(x2)
             if _bf16x3_ok(h, w2.shape[0], hid) and w2c.dtype == torch.float32 and w2.shape[0] % 8 == 0 and hid % 8 == 0:
                 # fp32 run, fc2 a bf16x3 product: gelu(h) is written as that product's [hi | hi | lo] operand and never as fp32
+                h = _aligned(h)  # (float4 loads)
                 a3 = torch.empty((h.shape[0], 3 * hid), dtype=torch.bfloat16, device=h.device)
                 check(lib.hs_gelu_split3(None, ptr(h), ptr(a3), h.shape[0], hid, float(drop_p), int(seed), stream_ptr(h.device)),
                       "hs_gelu_split3")
@@ -89,7 +90,7 @@ class MlpFn(torch.autograd.Function):
             if _bf16x3_ok(da, c_in, hid) and w1.dtype == torch.float32 and c_in % 8 == 0 and hid % 8 == 0:
                 # fp32 run: dh is read by fc1's input- and weight-gradient products only, both bf16x3 -- written as their operand
                 dh3 = torch.empty((h.shape[0], 3 * hid), dtype=torch.bfloat16, device=h.device)
-                check(lib.hs_gelu_split3(ptr(da), ptr(h), ptr(dh3), h.shape[0], hid, p, seed, stream_ptr(h.device)), "hs_gelu_split3")
+                check(lib.hs_gelu_split3(ptr(_aligned(da)), ptr(_aligned(h)), ptr(dh3), h.shape[0], hid, p, seed, stream_ptr(h.device)), "hs_gelu_split3")
                 dh = _Split(dh3, hid)
             else:
                 dh = torch.empty_like(h)

@@ -23,8 +23,9 @@
  *   hs_gemm_nt, hs_mlp_fused_*, hs_window_attn_module_*, hs_layernorm_* / hs_add_layernorm_*, hs_ln_head_*,
  *   hs_expand_ln_head_* (labels, targets, class weights and predictions excepted: single elements), hs_patch_merge_*,
  *   hs_patch_expand_*, hs_linear_wgrad* (members of a group and the destinations of sums queued for hs_reduce_flush included),
- *   hs_gelu_*, hs_residual_drop, hs_adam_step / hs_adam_step_guarded (their bf16 copy: 8 bytes), hs_grad_stats and hs_grad_scale must
- *   therefore be 16-byte aligned: activations, weights, biases, gamma / beta, workspaces and gradient destinations alike.  They
+ *   hs_gelu_* and hs_split_bf16x3 (the bf16 output of hs_gelu_split3 and hs_split_bf16x3: 8 bytes), hs_residual_drop,
+ *   hs_adam_step / hs_adam_step_guarded (their bf16 copy: 8 bytes), hs_grad_stats and hs_grad_scale must therefore be 16-byte
+ *   aligned: activations, weights, biases, gamma / beta, workspaces and gradient destinations alike.  They
  *   check it before anything is launched and return HS_ERR_MISALIGNED; the entry points that chain others check every pointer first.
  *   Entry points that address single elements take any naturally aligned pointer: hs_rel_bias_*, hs_cos_head_scale_*,
  *   hs_transpose_many_16 (whose job table lives on the device and cannot be checked), and those that choose between a vector
@@ -163,7 +164,8 @@ int hs_cos_head_scale_bwd(const float* logit_scale, const float* dscale, float* 
  *   hs_rel_bias_gather_many: bias of job j = bias_base + (heads[0] + ... + heads[j-1]) * Ws*Ws, f32[heads[j], Ws, Ws];
  *   hs_rel_bias_scatter_grad_sorted_many: dtables[j] f32[T, heads[j]] overwritten, or added to where accumulate[j] != 0;
  *   hs_cos_head_scale_many: dscale == NULL: out[j][h] = exp(min(logit_scale[j][h], ln 100)); else out[j][h] (+)= the gradient above
- *   (heads[j] <= 64). */
+ *   (heads[j] <= 64).
+ * More than 48 jobs run as several launches; every job is checked first, so HS_ERR_INVALID_ARG means that nothing was launched. */
 int hs_rel_bias_gather_many(const void* const* tables, const int* heads, int count, const int32_t* rel_idx, float* bias_base,
                             int table_rows, int window_size, void* stream);
 int hs_rel_bias_scatter_grad_sorted_many(const void* const* dbias, void* const* dtables, const int* heads, const int* accumulate, int count,
@@ -856,7 +858,8 @@ int hs_split_bf16x3(const float* x, void* out, int64_t rows, int k, int mode, vo
 /* GELU fused with the split: out3 [rows, 3 k] bf16 = [hi | hi | lo] of dropout(gelu_erf(x)) (dy == NULL: the forward, x the
  * pre-activation) or of dy * dropout_mask * gelu_erf'(x) (the backward), x / dy [rows, k] fp32 -- for tensors that only
  * bf16 x 3 products read (the MLP hidden activation and its gradient): no fp32 copy is written.  Same dropout mask as
- * hs_gelu_fwd / hs_gelu_bwd for (seed, element index row * k + column). */
+ * hs_gelu_fwd / hs_gelu_bwd for (seed, element index row * k + column).
+ * Both entry points: k a positive multiple of 4; x / dy 16-byte aligned, out 8-byte aligned ("Pointer alignment"). */
 int hs_gelu_split3(const float* dy, const float* x, void* out3, int64_t rows, int k, float drop_p, uint64_t seed, void* stream);
 int hs_linear_wgrad_ld(const void* dy, int64_t ldy, int64_t ycol0, const void* x, int64_t ldx, int64_t xcol0, float* dw, float* dbias,
                        float* workspace, int64_t rows, int n_out, int k_in, int accumulate, void* stream);

@@ -11,10 +11,11 @@ Contract (include/healswin.h, "Pointer alignment"), asserted per entry point, op
 
 Covered through the C ABI: hs_gemm_nt, hs_mlp_fused_fwd / _bwd, hs_window_attn_module_fwd, hs_layernorm_bwd (destinations),
 hs_linear_wgrad / _ld / _gelu / _group and the deferred sums (hs_reduce_flush), hs_rel_bias_*, hs_cos_head_scale_*,
-hs_transpose_many_16, hs_gelu_*, hs_residual_drop, hs_adam_step.  hs_window_attn_module_fwd_train / _bwd_chain,
+hs_transpose_many_16, hs_gelu_* (hs_gelu_split3 included), hs_split_bf16x3, hs_residual_drop, hs_adam_step.  hs_window_attn_module_fwd_train / _bwd_chain,
 hs_expand_ln_head_ce / _ce_step / _depth_fwd, hs_ln_head_ce_bwd / _depth_bwd (refusal before launch).  Covered through ops (the route
 the model takes), forward and backward: linear, layer_norm, add_layer_norm and their _stream forms, window_attn_module and its training
-form, ln_head, expand_ln_head and its _ce / _ce_step / depth forms (class weights included), gelu_dropout, residual_drop, and the
+form, ln_head, expand_ln_head and its _ce / _ce_step / depth forms (class weights included), gelu_dropout, residual_drop, the bf16x3
+splits of fp32 operands (ops.gemm.split3 / _weight_split), and the
 direct deposit into gradient-sink views (Linear / LayerNorm: aligned or refused; position-bias table / logit_scale: any residue)."""
 import ctypes
 
@@ -923,3 +924,54 @@ def test_train_form_and_loss_tail_entry_points_refuse_before_launch():
                                                       L.HS_DEPTH_L2, 1.0, ptr(scale), 1, ptr(o["wfold"]), ptr(o["bvec"]), ptr(o["afold"]), ptr(dy),
                                                       ptr(dprime), ptr(part), rows, Ct, L.HS_BF16, S)
                     assert not c_call(st, f"hs_ln_head_{entry}_bwd {name}+{e}", [dy, dprime, part])
+
+
+# ----------------------------------------------------------------------------- bf16 x 3 splits (float4 loads, uint2 stores)
+def test_split3_entry_points_refuse_before_launch_and_their_ops_fall_back():
+    """hs_split_bf16x3 / hs_gelu_split3: x and dy need 16 bytes, the bf16 output 8.  Residues 4 and 8 of a source and residue 4 of the
+    output are refused before anything is launched; an output 8 bytes behind an aligned base is legal and gives the aligned call's
+    bits.  ops.gemm.split3 / _weight_split take a view one element into a buffer through an aligned copy."""
+    from heal_swin_amd.ops import gemm as G
+    L = _lib()
+    lib, ptr = L.lib, L.ptr
+    rows, k = 36, 24  # (both multiples of 4: the transposed weight split has k = rows)
+    x0 = torch.randn(rows, k, device=DEV)
+    dy0 = torch.randn(rows, k, device=DEV)
+
+    def out_buf():
+        return torch.full((rows, 3 * k), SENTINEL, dtype=BF, device=DEV)
+    want = {}
+    for mode in (0, 1):
+        want[mode] = out_buf()
+        L.check(lib.hs_split_bf16x3(ptr(x0), ptr(want[mode]), rows, k, mode, _stream()), "hs_split_bf16x3")
+    want_f, want_b = out_buf(), out_buf()
+    L.check(lib.hs_gelu_split3(None, ptr(x0), ptr(want_f), rows, k, 0.3, 5, _stream()), "hs_gelu_split3")
+    L.check(lib.hs_gelu_split3(ptr(dy0), ptr(x0), ptr(want_b), rows, k, 0.3, 5, _stream()), "hs_gelu_split3")
+    hi = x0.bfloat16()
+    assert torch.equal(want[1].view(torch.int16), torch.cat([hi, (x0 - hi.float()).bfloat16(), hi], 1).view(torch.int16))
+    for e in E_F32[1:]:  # sources at 4 and 8 bytes
+        x, dy = at_offset(x0, e), at_offset(dy0, e)
+        for mode in (0, 1):
+            y = out_buf()
+            assert not c_call(lib.hs_split_bf16x3(ptr(x), ptr(y), rows, k, mode, _stream()), f"hs_split_bf16x3 x+{e}", [y])
+        y = out_buf()
+        assert not c_call(lib.hs_gelu_split3(None, ptr(x), ptr(y), rows, k, 0.3, 5, _stream()), f"hs_gelu_split3 x+{e}", [y])
+        assert not c_call(lib.hs_gelu_split3(ptr(dy0), ptr(x), ptr(y), rows, k, 0.3, 5, _stream()), f"hs_gelu_split3 bwd x+{e}", [y])
+        assert not c_call(lib.hs_gelu_split3(ptr(dy), ptr(x0), ptr(y), rows, k, 0.3, 5, _stream()), f"hs_gelu_split3 dy+{e}", [y])
+    yo = at_offset(out_buf(), 2)  # output at 4 bytes
+    assert not c_call(lib.hs_split_bf16x3(ptr(x0), ptr(yo), rows, k, 1, _stream()), "hs_split_bf16x3 out+2", [yo])
+    assert not c_call(lib.hs_gelu_split3(None, ptr(x0), ptr(yo), rows, k, 0.3, 5, _stream()), "hs_gelu_split3 out+2", [yo])
+    yo = at_offset(out_buf(), 4)  # output at 8 bytes: what its uint2 stores need
+    assert c_call(lib.hs_split_bf16x3(ptr(x0), ptr(yo), rows, k, 1, _stream()), "hs_split_bf16x3 out+4")
+    assert torch.equal(yo.view(torch.int16), want[1].view(torch.int16))
+    assert c_call(lib.hs_gelu_split3(ptr(dy0), ptr(x0), ptr(yo), rows, k, 0.3, 5, _stream()), "hs_gelu_split3 out+4")
+    assert torch.equal(yo.view(torch.int16), want_b.view(torch.int16))
+    # the ops: a view one element into a buffer
+    buf = torch.zeros(rows * k + 1, device=DEV)
+    v = buf[1:].view(rows, k)
+    v.copy_(x0)
+    assert v.data_ptr() % 16 == 4
+    for mode in (0, 1):
+        assert torch.equal(G.split3(v, mode).view(torch.int16), want[mode].view(torch.int16)), f"ops.gemm.split3 mode {mode}"
+    assert torch.equal(G._weight_split(v, False).view(torch.int16), want[1].view(torch.int16))
+    assert torch.equal(G._weight_split(v, True).view(torch.int16), G.split3(x0.t().contiguous(), 1).view(torch.int16))
