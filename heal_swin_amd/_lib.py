@@ -48,6 +48,22 @@ def wgrad_problems(members):
         q.n_out, q.k_in, q.accumulate, q.gelu_x = int(n_out), int(k_in), int(acc), int(bool(gelu_x))
     return arr
 
+class AdamGroup(ctypes.Structure):
+    """`hs_adam_group` (include/healswin.h): the hyper-parameters of one parameter group of an hs_adam_step_groups call."""
+    _fields_ = [("lr_dev", c_ptr), ("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float),
+                ("decoupled", ctypes.c_int32)]
+
+
+def adam_groups(records):
+    """ctypes array of hs_adam_group from (lr: float or 0-dim fp32 device tensor, beta1, beta2, eps, weight_decay, decoupled) tuples."""
+    arr = (AdamGroup * len(records))()
+    for q, (lr, b1, b2, eps, wd, decoupled) in zip(arr, records):
+        on_device = hasattr(lr, "data_ptr")
+        q.lr_dev, q.lr = (lr.data_ptr() if on_device else None), (0.0 if on_device else float(lr))
+        q.beta1, q.beta2, q.eps, q.weight_decay, q.decoupled = float(b1), float(b2), float(eps), float(wd), int(bool(decoupled))
+    return arr
+
+
 # name -> argtypes; every function returns int status unless listed in _OTHER_RESTYPE
 _SIGNATURES = {
     "hs_nest2ring": [c_int, c_ptr, c_ptr, c_i64],
@@ -143,6 +159,9 @@ _SIGNATURES = {
     "hs_adam_step_guarded": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_float, c_ptr, c_float, c_float, c_float, c_float, c_int, c_ptr, c_float,
                              c_ptr, c_int, c_ptr],
     "hs_adam_advance_guarded": [c_ptr, c_ptr, c_int, c_ptr, c_ptr],
+    "hs_adam_step_groups": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_i64, c_ptr, c_ptr],
+    "hs_adam_step_groups_guarded": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_i64, c_ptr, c_float,
+                                    c_ptr, c_int, c_ptr],
     "hs_grad_scale": [c_ptr, c_i64, c_float, c_ptr, c_ptr],
     "hs_split_bf16x3": [c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr],
     "hs_gelu_split3": [c_ptr, c_ptr, c_ptr, c_i64, c_int, ctypes.c_float, ctypes.c_uint64, c_ptr],
@@ -192,6 +211,7 @@ _OTHER = {
     "hs_device_count": ([], c_int),
     "hs_get_reserved_cus": ([], c_int),
     "hs_grad_guard_piece": ([], c_int),
+    "hs_adam_max_groups": ([], c_int),
     "hs_get_seed_epoch": ([], c_ptr),
     "hs_reduce_pending": ([c_ptr], c_int),
     "hs_layernorm_bwd_workspace": ([c_i64, c_int], c_i64),

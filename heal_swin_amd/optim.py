@@ -12,9 +12,15 @@ second pass over all parameters per training step.  Same arithmetic as torch.opt
 `decoupled_weight_decay=True` = AdamW); the step counter lives on the device, so the whole training step stays capturable in
 one HIP graph (`graphs.GraphedTrainStep`, `bench.py --graph`).
 
-It is a torch.optim.Optimizer: learning-rate schedulers act on `param_groups[0]["lr"]` (read on the host at every `step()`; under
+It is a torch.optim.Optimizer: learning-rate schedulers act on `param_groups[i]["lr"]` (read on the host at every `step()`; under
 graph replay pass `lr` as a 0-dim CUDA tensor and update it in place), `state_dict()` / `load_state_dict()` carry `exp_avg`,
-`exp_avg_sq` and `step` per parameter in torch.optim.Adam's layout.  One parameter group, GPU only -- there is no CPU path.
+`exp_avg_sq` and `step` per parameter in torch.optim.Adam's layout.  GPU only -- there is no CPU path.
+
+Parameter groups: `params` may be a list of dicts with their own `lr` (float or device tensor, mixed freely), `betas`, `eps`,
+`weight_decay`, `decoupled_weight_decay`; `weight_decay_groups(model, wd)` makes the usual Swin split (no decay on biases, LayerNorm
+parameters, position tables, `logit_scale`) from the model's own `no_weight_decay()` / `no_weight_decay_keywords()`.  A step stays
+one launch per bucket (`hs_adam_step_groups`): the groups' hyper-parameters travel as kernel arguments, and a static table per
+bucket (`group_tables`) tells the kernel which group owns an element.  Groups are fixed at construction (up to `adam_max_groups()`).
 
 Guard rails (the reference trainer's gradient_clip_val / gradient_clip_algorithm, track_grad_norm, terminate_on_nan:
 training/train_config.py:65-66,76,104): `max_grad_norm=` / `clip_value=`, `track_grad_norm=True`, `skip_nonfinite=True`.  With any of
@@ -55,6 +61,74 @@ def guard_tables(layout, piece):
             first += count
         items.append(cur)
     return items, params
+
+
+def adam_max_groups():
+    """HS_ADAM_MAX_GROUPS: the most parameter groups one `hs_adam_step_groups` launch takes (a compile-time constant of csrc/adam.hip)."""
+    return int(lib.hs_adam_max_groups())
+
+
+def group_tables(layout, groups, block=1024, lengths=None):
+    """The tables `hs_adam_step_groups` finds an element's parameter group by (pure host code).
+    layout: as for `guard_tables` -- per bucket, a list of (parameter index, element offset in the bucket, numel) -- with offsets that
+    are multiples of 8 (the sink's slot rule: a float4 never straddles two parameters); groups: per group, the indices of its parameters;
+    lengths: the element count of every bucket (default: up to the end of its last slot, rounded up to 8).
+    Returns (runs, block_first): runs[b] = [(first element, group), ...] for bucket b -- consecutive slots of one group merged into
+    one run, the gap behind a slot belonging to the run in front of it, the first run starting at 0 -- and block_first[b][k] = the run that
+    holds element k * block of bucket b.  ValueError for what the kernel cannot load: a slot off an 8-element boundary, a parameter in no
+    group or in two, more groups than `adam_max_groups()`."""
+    max_groups = adam_max_groups()
+    groups = [list(members) for members in groups]
+    if not 1 <= len(groups) <= max_groups:
+        raise ValueError(f"{len(groups)} parameter groups: one launch takes 1 ... {max_groups}")
+    n_params = sum(len(bucket) for bucket in layout)
+    group_of = {}
+    for k, members in enumerate(groups):
+        for index in members:
+            if index in group_of:
+                raise ValueError(f"parameter {index} is in more than one group")
+            group_of[index] = k
+    if sorted(group_of) != list(range(n_params)):
+        raise ValueError("every parameter 0 ... n - 1 of the layout must be in exactly one group")
+    runs, block_first = [], []
+    for b, bucket in enumerate(layout):
+        cur, end = [], 0
+        for index, off, numel in sorted(bucket, key=lambda e: e[1]):
+            if off % 8 or off < end:
+                raise ValueError("a parameter's slot must start on a multiple of 8 elements, behind the slot in front of it")
+            if not cur or cur[-1][1] != group_of[index]:
+                cur.append((off if cur else 0, group_of[index]))
+            end = off + numel
+        length = -(-end // 8) * 8 if lengths is None else int(lengths[b])
+        if not cur or length < end:
+            raise ValueError("a bucket holds at least one parameter and all of its last one")
+        starts = [s for s, _ in cur]
+        first, r = [], 0
+        for e in range(0, length, block):
+            while r + 1 < len(starts) and starts[r + 1] <= e:
+                r += 1
+            first.append(r)
+        runs.append(cur)
+        block_first.append(first)
+    return runs, block_first
+
+
+def weight_decay_groups(model, weight_decay, no_decay_1d=True, **group_options):
+    """[decay group, no-decay group] for FlatAdam (or torch.optim.AdamW) from the model's own declarations, Swin's `set_weight_decay` rule:
+    without decay are the parameters whose name ends in an entry of `model.no_weight_decay()` (absolute_pos_embed) or contains an entry
+    of `model.no_weight_decay_keywords()` (the relative-position bias tables) and, with `no_decay_1d`, every parameter with ndim <= 1 --
+    biases, LayerNorm weights -- and the cosine attention's per-head `logit_scale`, a vector stored as [heads, 1, 1].  Parameters that
+    do not require a gradient are in neither.  group_options (lr=, betas=, ...) go into both groups.  Pure host code."""
+    skip = set(getattr(model, "no_weight_decay", set)())
+    keywords = set(getattr(model, "no_weight_decay_keywords", set)())
+    decay, no_decay = [], []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        named = any(name.endswith(s) for s in skip) or any(k in name for k in keywords)
+        one_d = no_decay_1d and (p.ndim <= 1 or name.endswith("logit_scale"))
+        (no_decay if named or one_d else decay).append(p)
+    return [dict(group_options, params=decay, weight_decay=float(weight_decay)), dict(group_options, params=no_decay, weight_decay=0.0)]
 
 
 def _norm_kind(norm_type):
@@ -127,7 +201,9 @@ class FlatAdam(torch.optim.Optimizer):
     def __init__(self, params, grad_sink, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False,
                  model=None, lowp_dtype=torch.bfloat16, max_grad_norm=None, clip_value=None, norm_type=2.0, skip_nonfinite=False,
                  track_grad_norm=False):
-        """grad_sink: the parallel.GradBucketAllReduce that owns the gradients of exactly these parameters.
+        """params: parameters, or parameter groups (dicts: "params" plus any of lr, betas, eps, weight_decay, decoupled_weight_decay; what a
+        group does not set comes from the arguments here).  Parameters that do not require a gradient are dropped from every group.
+        grad_sink: the parallel.GradBucketAllReduce that owns the gradients of exactly these parameters.
         model: a SwinHPTransformerSys whose bf16 parameter copies this optimizer should keep current (optional).
         max_grad_norm: clip the gradients to this total norm (`norm_type` 2 or inf) as torch.nn.utils.clip_grad_norm_ does.
         clip_value: or clamp every gradient element to +-clip_value as torch.nn.utils.clip_grad_value_ does (not both).
@@ -141,17 +217,35 @@ class FlatAdam(torch.optim.Optimizer):
         if clip_value is not None and not (float(clip_value) > 0.0 and math.isfinite(float(clip_value))):
             raise ValueError("clip_value must be positive and finite")
         norm_type = _norm_kind(norm_type)
-        params = [p for p in params if p.requires_grad]
-        if not params or not all(p.is_cuda and p.dtype == torch.float32 for p in params):
-            raise RuntimeError("FlatAdam runs on fp32 master parameters on an MI355X (HIP) device; there is no CPU path")
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, decoupled_weight_decay=bool(decoupled_weight_decay),
+                        capturable=True, fused=True)
+        params = list(params)
+        if params and all(isinstance(g, dict) for g in params):  # parameter groups: own lr, betas, eps, weight_decay, decoupled_weight_decay
+            groups = [dict(g, params=[p for p in g["params"] if p.requires_grad], capturable=True, fused=True) for g in params]
+            if not all(g["params"] for g in groups):
+                raise ValueError("a parameter group holds no parameter that requires a gradient")
+        else:
+            groups = [dict(params=[p for p in params if p.requires_grad])]
+        params = [p for g in groups for p in g["params"]]
+        if len(set(map(id, params))) != len(params):
+            raise ValueError("some parameters appear in more than one parameter group")
         if set(map(id, params)) != set(map(id, grad_sink.params)):
             raise ValueError("FlatAdam and its gradient sink must be built over the same parameters")
-        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or eps < 0.0 or weight_decay < 0.0:
-            raise ValueError("invalid Adam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
-                                      decoupled_weight_decay=bool(decoupled_weight_decay), capturable=True, fused=True))
-        if len(self.param_groups) != 1:
-            raise NotImplementedError("FlatAdam supports one parameter group")
+        if len(groups) > adam_max_groups():
+            raise ValueError(f"{len(groups)} parameter groups: FlatAdam steps at most {adam_max_groups()} in its one launch per bucket")
+        for g in groups:
+            b, e, wd = g.get("betas", betas), g.get("eps", eps), g.get("weight_decay", weight_decay)
+            if len(b) != 2 or not 0.0 <= b[0] < 1.0 or not 0.0 <= b[1] < 1.0 or e < 0.0 or wd < 0.0:
+                raise ValueError("invalid Adam hyper-parameters")
+            if "betas" in g:
+                g["betas"] = tuple(b)
+            if "decoupled_weight_decay" in g:
+                g["decoupled_weight_decay"] = bool(g["decoupled_weight_decay"])
+        if not params or not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+            raise RuntimeError("FlatAdam runs on fp32 master parameters on an MI355X (HIP) device; there is no CPU path")
+        self._sealed = False
+        super().__init__(groups, defaults)
+        self._sealed = True  # (the sink fixes the flat layout: add_param_group is for Optimizer.__init__ alone)
         self.sink = grad_sink
         self.lowp_dtype = lowp_dtype if model is not None else None
         dev = params[0].device
@@ -187,10 +281,27 @@ class FlatAdam(torch.optim.Optimizer):
                 self._flat_m.append(M)
                 self._flat_v.append(V)
                 self._flat_lowp.append(S)
+        self._group_tables = None
+        if len(self.param_groups) > 1:  # who owns which element of a bucket: static, on the device (csrc/adam.hip)
+            index = {id(p): i for i, p in enumerate(grad_sink.params)}
+            layout = [[] for _ in grad_sink.buckets]
+            for p in grad_sink.params:
+                b = grad_sink._where[p]
+                layout[b].append((index[id(p)], grad_sink._views[p].storage_offset() - grad_sink.buckets[b].storage_offset(), p.numel()))
+            runs, first = group_tables(layout, [[index[id(p)] for p in g["params"]] for g in self.param_groups],
+                                       lengths=[f.numel() for f in grad_sink.buckets])
+            self._group_tables = [(torch.tensor(r, dtype=torch.int32, device=dev).reshape(len(r), 2), torch.tensor(f, dtype=torch.int32, device=dev))
+                                  for r, f in zip(runs, first)]
         self._model = model
         if model is not None:  # the model's cast cache takes its bf16 shadows from here (built at its next forward)
             model.__dict__["_shadow_provider"] = self.lowp_copy
             model.__dict__.pop("_cast_cache", None)
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_sealed", False):
+            raise ValueError("FlatAdam takes its parameter groups at construction: the gradient sink fixes the flat layout of parameters, "
+                             "moments and ownership tables; build a new sink and optimizer over the new set of parameters")
+        super().add_param_group(param_group)
 
     def lowp_copy(self, p, dtype):
         """The bf16 view of parameter p that `step()` keeps current, or None (other dtype / foreign parameter)."""
@@ -225,17 +336,22 @@ class FlatAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        for grp in self.param_groups:
+            lr = grp["lr"]
+            if isinstance(lr, torch.Tensor) and not (lr.is_cuda and lr.dtype == torch.float32 and lr.numel() == 1):
+                raise ValueError("a tensor learning rate must be a 0-dim float32 CUDA tensor")
+        dev = self._step.device
+        s = stream_ptr(dev)
+        buffers = zip(self._flat_p, self.sink.buckets, self._flat_m, self._flat_v, self._flat_lowp)
+        if self._group_tables is not None:
+            self._step_groups(buffers, s)
+            return self._stepped(loss)
         grp = self.param_groups[0]
         lr = grp["lr"]
         lr_dev = lr if isinstance(lr, torch.Tensor) else None
-        if lr_dev is not None and not (lr_dev.is_cuda and lr_dev.dtype == torch.float32 and lr_dev.numel() == 1):
-            raise ValueError("a tensor learning rate must be a 0-dim float32 CUDA tensor")
         b1, b2 = grp["betas"]
-        dev = self._step.device
-        s = stream_ptr(dev)
         hyper = (0.0 if lr_dev is not None else float(lr), ptr(lr_dev), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]),
                  int(grp["decoupled_weight_decay"]), ptr(self._step))
-        buffers = zip(self._flat_p, self.sink.buckets, self._flat_m, self._flat_v, self._flat_lowp)
         if self.guard is None:
             for P, G, M, V, S in buffers:
                 check(lib.hs_adam_step(ptr(P), ptr(G), ptr(M), ptr(V), ptr(S), P.numel(), *hyper, s), "hs_adam_step")
@@ -247,6 +363,27 @@ class FlatAdam(torch.optim.Optimizer):
                 check(lib.hs_adam_step_guarded(ptr(P), ptr(G), ptr(M), ptr(V), ptr(S), P.numel(), *hyper, self.clip_value or 0.0, rec, skip, s),
                       "hs_adam_step_guarded")
             check(lib.hs_adam_advance_guarded(ptr(self._step), rec, skip, ptr(self._skipped), s), "hs_adam_advance_guarded")
+        return self._stepped(loss)
+
+    def _step_groups(self, buffers, s):
+        """Several parameter groups: `hs_adam_step_groups`, still once per bucket -- the groups' records go by value (read here, on the
+        host, at every step: a scheduler's change of `param_groups[i]["lr"]` costs no copy), ownership comes from the device tables."""
+        records = _lib.adam_groups([(g["lr"], *g["betas"], g["eps"], g["weight_decay"], g["decoupled_weight_decay"]) for g in self.param_groups])
+        if self.guard is None:
+            for (P, G, M, V, S), (runs, first) in zip(buffers, self._group_tables):
+                check(lib.hs_adam_step_groups(ptr(P), ptr(G), ptr(M), ptr(V), ptr(S), P.numel(), records, len(records), ptr(runs), runs.shape[0],
+                                              ptr(first), first.numel(), P.numel(), ptr(self._step), s), "hs_adam_step_groups")
+            check(lib.hs_adam_advance(ptr(self._step), s), "hs_adam_advance")
+        else:  # one measurement, one clip coefficient and one finite flag for all groups
+            self.guard.measure(self.max_grad_norm)
+            rec, skip = ptr(self.guard.record), int(self.skip_nonfinite)
+            for (P, G, M, V, S), (runs, first) in zip(buffers, self._group_tables):
+                check(lib.hs_adam_step_groups_guarded(ptr(P), ptr(G), ptr(M), ptr(V), ptr(S), P.numel(), records, len(records), ptr(runs),
+                                                      runs.shape[0], ptr(first), first.numel(), P.numel(), ptr(self._step), self.clip_value or 0.0,
+                                                      rec, skip, s), "hs_adam_step_groups_guarded")
+            check(lib.hs_adam_advance_guarded(ptr(self._step), rec, skip, ptr(self._skipped), s), "hs_adam_advance_guarded")
+
+    def _stepped(self, loss):
         # the update went through raw pointers (no parameter `_version` moved): caches keyed by weight contents -- the bf16x3
         # splits of fp32 weights, ops._weight_split -- are told here, also for layers used outside a model's forward
         ops.RT.weight_epoch += 1
@@ -259,10 +396,14 @@ class FlatAdam(torch.optim.Optimizer):
         """Moments and step count are COPIED into the flat buffers (the views must keep pointing there)."""
         own = {id(p): st for p, st in self.state.items()}
         keep = {id(p): dict(st) for p, st in self.state.items()}
-        super().load_state_dict(state_dict)
+        decoupled = [g["decoupled_weight_decay"] for g in self.param_groups]
+        super().load_state_dict(state_dict)  # (torch's layout: parameter ids numbered through the groups, options restored per group)
+        for g, own_decoupled in zip(self.param_groups, decoupled):
+            g.setdefault("decoupled_weight_decay", own_decoupled)  # (a state dict of an optimizer without that option)
+            g["capturable"] = g["fused"] = True
         with torch.no_grad():
             step = None
-            for p in self.param_groups[0]["params"]:
+            for p in (p for g in self.param_groups for p in g["params"]):
                 new, old = self.state.get(p, {}), keep[id(p)]
                 for k in ("exp_avg", "exp_avg_sq"):
                     if k not in new:

@@ -24,7 +24,8 @@
  *   hs_expand_ln_head_* (labels, targets, class weights and predictions excepted: single elements), hs_patch_merge_*,
  *   hs_patch_expand_*, hs_linear_wgrad* (members of a group and the destinations of sums queued for hs_reduce_flush included),
  *   hs_gelu_* and hs_split_bf16x3 (the bf16 output of hs_gelu_split3 and hs_split_bf16x3: 8 bytes), hs_residual_drop,
- *   hs_adam_step / hs_adam_step_guarded (their bf16 copy: 8 bytes), hs_grad_stats and hs_grad_scale must therefore be 16-byte
+ *   hs_adam_step / hs_adam_step_guarded / hs_adam_step_groups / hs_adam_step_groups_guarded (their bf16 copy and the run table of
+ *   the grouped forms: 8 bytes), hs_grad_stats and hs_grad_scale must therefore be 16-byte
  *   aligned: activations, weights, biases, gamma / beta, workspaces and gradient destinations alike.  They
  *   check it before anything is launched and return HS_ERR_MISALIGNED; the entry points that chain others check every pointer first.
  *   Entry points that address single elements take any naturally aligned pointer: hs_rel_bias_*, hs_cos_head_scale_*,
@@ -477,6 +478,44 @@ int hs_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, int
 int hs_adam_advance(int64_t* step, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same step with PARAMETER GROUPS (torch's param_groups: per-group lr, betas, eps, weight decay), still one launch per buffer.
+ *   groups [HOST] hs_adam_group[n_groups], 1 <= n_groups <= HS_ADAM_MAX_GROUPS: read during the call and passed to the kernel by
+ *                 value -- no copy to the device, capturable; a captured launch keeps the values it was captured with, so under
+ *                 graph replay a learning rate that changes is a group's lr_dev ([dev] f32[1], overrides lr when non-NULL; groups
+ *                 with and without one mix freely).
+ *   runs   [dev] int32[n_runs][2] = (first element, group) of each run, 8-byte aligned: a run is a maximal stretch of consecutive
+ *                 parameter slots of ONE group, the alignment gap behind a slot included.  First elements ascend from 0 and are
+ *                 multiples of 8 (parallel.GradBucketAllReduce's slot rule: a float4 never straddles two runs); run r ends where
+ *                 run r + 1 starts, the last one at `covered`, the element count the table was built for, which must equal n.
+ *                 1 <= n_runs <= ceil(n / 8); n < 2^31.
+ *   block_first [dev] int32[n_blocks], n_blocks == ceil(n / 1024): the run that holds element 1024 b.  A thread starts there and
+ *                 walks forward to the run of its own element.
+ *   Static per buffer: optim.group_tables builds both once.  The kernel cannot be sent outside the two tables by their contents
+ *   (a run index is clamped, a group index taken modulo n_groups); what they assign wrongly is stepped with the wrong group.
+ *   Each workgroup resolves the n_groups records into LDS first -- lr, and the two bias corrections of ITS betas in double -- and
+ *   every element is then stepped with the arithmetic of hs_adam_step and the record of its run's group: with equal records the
+ *   result is bit-identical to hs_adam_step.  The zero gaps of the buffers (p = g = m = v = 0) stay zero for every record.
+ *   hs_adam_step_groups_guarded is hs_adam_step_guarded in the same way (the guard section below): ONE clip coefficient, from the
+ *   norm over all groups, one clip_value, one finite flag -- a skipped step skips every group -- and one step counter, advanced by
+ *   hs_adam_advance / hs_adam_advance_guarded as before.
+ * HS_ERR_INVALID_ARG (nothing is launched): null pointer, n <= 0 or >= 2^31, n_groups outside 1 ... HS_ADAM_MAX_GROUPS, a group
+ * with beta outside [0, 1), eps < 0, weight_decay < 0 or a NaN lr, n_runs or n_blocks that do not fit n, covered != n, clip_value
+ * NaN; HS_ERR_MISALIGNED ("Pointer alignment"): p, g, m, v, guard not 16-byte aligned, p_bf16 or runs not 8-byte aligned,
+ * block_first or an lr_dev not 4-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_ADAM_MAX_GROUPS 32
+typedef struct {
+    const float* lr_dev; /* [dev] f32[1] or NULL */
+    float lr;
+    float beta1, beta2, eps, weight_decay;
+    int32_t decoupled; /* 0: g += wd p (Adam); != 0: p *= 1 - lr wd (AdamW) */
+} hs_adam_group;
+int hs_adam_max_groups(void); /* HS_ADAM_MAX_GROUPS of the library that was loaded */
+int hs_adam_step_groups(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, const hs_adam_group* groups, int n_groups,
+                        const int32_t* runs, int n_runs, const int32_t* block_first, int n_blocks, int64_t covered, const int64_t* step,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Guard rails of the flat optimizer step: gradient norms, clipping and the non-finite skip -- the reference trainer's
  * gradient_clip_val / gradient_clip_algorithm, track_grad_norm and terminate_on_nan (training/train_config.py:65-66,76,104) --
  * as ONE read-only pass over the flat gradient buckets, everything decided on the device (capturable in a HIP graph).
@@ -503,6 +542,7 @@ int hs_adam_advance(int64_t* step, void* stream);
  *                      (weight decay of the non-decoupled form is added after that: torch's clip_grad_*_ followed by step()).
  *                      With skip_nonfinite != 0 and guard->finite == 0 the launch writes nothing.  With clip_coef == 1,
  *                      finite == 1 and clip_value <= 0 the result is bit-identical to hs_adam_step.
+ *   hs_adam_step_groups_guarded   the same for hs_adam_step_groups (the section above).
  *   hs_adam_advance_guarded  adds 1 to *step, or -- skip_nonfinite != 0 and guard->finite == 0 -- 0 to *step and 1 to *skipped.
  *   hs_grad_scale      the same clamp and scale applied in place to a bucket (for callers that keep another optimizer).
  * No allocation, no synchronisation.  HS_ERR_INVALID_ARG: null pointer, n <= 0; HS_ERR_MISALIGNED: g, p, m, v, partials, work,
@@ -521,6 +561,9 @@ int hs_grad_guard_finalize(const double* partials, int64_t n_items, const int32_
 int hs_adam_step_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, const float* lr_dev, float beta1,
                          float beta2, float eps, float weight_decay, int decoupled, const int64_t* step, float clip_value,
                          const hs_grad_guard* guard, int skip_nonfinite, void* stream);
+int hs_adam_step_groups_guarded(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, const hs_adam_group* groups,
+                                int n_groups, const int32_t* runs, int n_runs, const int32_t* block_first, int n_blocks, int64_t covered,
+                                const int64_t* step, float clip_value, const hs_grad_guard* guard, int skip_nonfinite, void* stream);
 int hs_adam_advance_guarded(int64_t* step, const hs_grad_guard* guard, int skip_nonfinite, int64_t* skipped, void* stream);
 int hs_grad_scale(float* g, int64_t n, float clip_value, const hs_grad_guard* guard, void* stream);
 
