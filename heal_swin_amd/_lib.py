@@ -187,6 +187,7 @@ _SIGNATURES = {
     "hs_gemm_nt": [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
                    ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_gemm_nt_set_tile": [c_int],
+    "hs_gemm_nt_tile_variant": [c_i64, c_int, c_int, c_int, c_int],
     "hs_set_reserved_cus": [c_int],
     "hs_transpose_many_16": [c_ptr, c_int, c_int, c_ptr],
     "hs_debug_occupy_cus": [c_int, c_int, c_int, ctypes.c_double, c_ptr],

@@ -2,9 +2,24 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "hs_common.h"
 
 namespace hs {
+
+// compile-time indices: Int<N>{} as an argument, static_for<N>(f) calls f(Int<0>{}) ... f(Int<N - 1>{}) in order
+template <int N>
+using Int = std::integral_constant<int, N>;
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(Int<I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
 
 struct bf16_t {
     uint16_t bits;
@@ -30,6 +45,13 @@ __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 
 // operand and accumulator registers of v_mfma_f32_32x32x16_bf16
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+template <int A, int B>
+__device__ __forceinline__ void zero(f32x16 (&acc)[A][B]) {
+#pragma unroll
+    for (int i = 0; i < A; ++i)
+#pragma unroll
+        for (int j = 0; j < B; ++j) acc[i][j] = 0.f;
+}
 // 16 bytes of packed words (a b128 LDS / global access, four bf16 pairs)
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 // LDS-DMA (buffer_load ... lds): the destination type of the builtin, and a byte offset outside every descriptor (a lane pointed
@@ -105,6 +127,10 @@ struct ElemRng {
         const uint32_t u = ck * m;
         return u ^ (u >> 16);
     }
+    // multiplier of pair t (0 / 1) of the first / second half of a chunk: what a lane that owns 4 consecutive elements needs
+    static __device__ __forceinline__ uint32_t half_mult(bool second, int t) {
+        return t == 0 ? (second ? kM2 : kM0) : (second ? kM3 : kM1);
+    }
     __device__ __forceinline__ float keep_lo(uint32_t h) const { return (h & 0xffffu) >= thresh16 ? keep_scale : 0.f; }
     __device__ __forceinline__ float keep_hi(uint32_t h) const { return (h >> 16) >= thresh16 ? keep_scale : 0.f; }
     // multiplier of element i: 0 (dropped) or 1/(1-p)
@@ -138,7 +164,7 @@ struct ElemRng {
                     m = pr == 0 ? kM0 : pr == 1 ? kM1 : pr == 2 ? kM2 : kM3;
                 } else {
                     const bool second = ((uint32_t)e0 >> 2) & 1u;
-                    m = pr == 0 ? (second ? kM2 : kM0) : (second ? kM3 : kM1);
+                    m = half_mult(second, pr);
                 }
                 h = pair_bits(ck, m);
                 return keep_lo(h);
@@ -152,7 +178,7 @@ struct ElemRng {
     __device__ __forceinline__ void mult4(int64_t i0, float (&out)[4]) const {
         const uint32_t ck = chunk_key((uint64_t)i0 >> 3);
         const bool second = ((uint32_t)i0 >> 2) & 1u;
-        const uint32_t ha = pair_bits(ck, second ? kM2 : kM0), hb = pair_bits(ck, second ? kM3 : kM1);
+        const uint32_t ha = pair_bits(ck, half_mult(second, 0)), hb = pair_bits(ck, half_mult(second, 1));
         out[0] = keep_lo(ha), out[1] = keep_hi(ha), out[2] = keep_lo(hb), out[3] = keep_hi(hb);
     }
 };

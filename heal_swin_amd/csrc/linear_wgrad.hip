@@ -119,15 +119,6 @@ __device__ __forceinline__ bool block_to_work(const Geometry& g, int b, int& sli
 }
 
 // ---------------------------------------------------------------------------------------- pieces every kernel below shares
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // token rows [m_begin, m_begin + m_len) of a slice; a kernel with T-token stages runs (m_len + T - 1) / T of them
 struct SliceRows {
     int64_t m_begin;
@@ -138,12 +129,6 @@ __device__ __forceinline__ SliceRows slice_rows(const Geometry& g, int slice, in
     int64_t m_end = m_begin + g.rows_per_slice;
     if (m_end > rows) m_end = rows;
     return {m_begin, m_end > m_begin ? (int)(m_end - m_begin) : 0};
-}
-
-template <int NB>
-__device__ __forceinline__ void zero(f32x16 (&acc)[NB][2]) {
-#pragma unroll
-    for (int i = 0; i < NB; ++i) acc[i][0] = acc[i][1] = 0.f;
 }
 
 // A wave's NB x 2 accumulators (32 x 32 each, origin (n_wave, k_wave)) -> the slice's partial record `dst` [n_out][k_in];

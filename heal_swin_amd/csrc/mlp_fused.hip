@@ -440,7 +440,7 @@ __global__ void __launch_bounds__(C * 4, 1) mlp_fused_kernel(MlpParams p) {
                     if (dropping) ck = rng_h.chunk_key(cbase + (uint32_t)(4 * i + g));
                 }
                 auto drop2 = [&](int t) {
-                    const uint32_t hh = ElemRng::pair_bits(ck, t == 0 ? (half ? ElemRng::kM2 : ElemRng::kM0) : (half ? ElemRng::kM3 : ElemRng::kM1));
+                    const uint32_t hh = ElemRng::pair_bits(ck, ElemRng::half_mult(half, t));
                     return f32x2{rng_h.keep_lo(hh), rng_h.keep_hi(hh)};
                 };
                 if constexpr (!BWD) {

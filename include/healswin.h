@@ -659,8 +659,10 @@ int hs_window_attn_module_bwd_chain(const void* dout, const void* x, const void*
  *            HS_EPI_RESID: c = acc + bias + aux                              (aux = a residual term [read])
  *   The dropout mask is the one hs_gelu_fwd/bwd draw for the same (seed, element index m*n_cols + n).
  *   k, k2, lda, ldb multiples of 8; n a multiple of 4; dtype must be HS_BF16 (fp32 runs keep the library GEMM).
- * hs_gemm_nt_set_tile: measurement hook (0 = built-in choice, 1 = 128x128 tiles, 2 = 256x128 x 3 stages, 3 = 256x256 with
- * 8 waves, 4 = 256x256 with 4 waves of 128x128 and the accumulators in AGPRs: never chosen by 0, kept for A/B runs).
+ * hs_gemm_nt_set_tile: measurement hook (0 = built-in choice, 1 = 128x128 tiles, 2 = 256x128 x 3 stages, 3 = 256x256 x 2
+ * stages; any other value runs the 128x128 tiles).
+ * hs_gemm_nt_tile_variant: the tile variant (1 / 2 / 3) a call with this shape and epilogue would launch now: the value forced by
+ * hs_gemm_nt_set_tile or the built-in choice, and 2 in place of 3 where HS_EPI_DGELU / _RESID meet n % 8 != 0 (pure host code).
  * ---------------------------------------------------------------------------------------------- */
 #define HS_EPI_BIAS 0
 #define HS_EPI_GELU 1
@@ -670,6 +672,7 @@ int hs_gemm_nt(const void* a, int64_t lda, const void* b, int64_t ldb, int k, co
                int64_t ldb2, int k2, const float* bias, void* c, void* aux, int64_t m, int n, int epilogue, float drop_p,
                uint64_t seed, int dtype, void* stream);
 int hs_gemm_nt_set_tile(int variant);
+int hs_gemm_nt_tile_variant(int64_t m, int n, int k, int k2, int epilogue);
 
 /* ------------------------------------------------------------------------------------------------
  * Fisheye image -> HEALPix projection, the input pipeline in front of the model.  Replaces, per image, the

@@ -76,26 +76,45 @@ def test_gemm_nt_two_segments_equal_the_concatenated_product(m, n, k1, k2):
     assert_close(c, ref, 6e-3, "two segments")
 
 
-def test_gemm_nt_dropout_mask_equals_the_gelu_kernels():
-    """Same (seed, element index) -> same keep decision as hs_gelu_fwd, so a model may mix fused and unfused MLPs, and the
-    backward epilogue regenerates the forward's mask."""
+def _check_dropout_mask(m, n, k, tile):
     from heal_swin_amd import _lib, ops
-    m, n, k, p, seed = 512, 384, 128, 0.3, 123456789012345
+    p, seed = 0.3, 123456789012345
     g = torch.Generator().manual_seed(1)
     a = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)
     b = (torch.randn(n, k, generator=g) * 0.1).to(torch.bfloat16).to(DEV)
     bias = torch.full((n,), 3.0, device=DEV)  # pre-activations well away from 0: every surviving gelu(h) is non-zero
-    h, act = _gemm(a, b, bias, epi=_lib.HS_EPI_GELU, p=p, seed=seed)
-    plain = ops.GeluDropoutFn.apply(h, p, seed)
-    assert torch.equal(act == 0, plain == 0)
-    assert abs(float((act != 0).float().mean()) - (1 - p)) < 5e-3
-    keep = (act != 0)
-    assert_close(act[keep], plain[keep], 1e-2, "survivors")
-    da = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)  # reuse shapes: d = (da b^T) * mask/(1-p) * gelu'(h)
-    d, _ = _gemm(da, b, None, epi=_lib.HS_EPI_DGELU, aux=h, p=p, seed=seed)
-    assert torch.equal(d == 0, act == 0)
-    ref = (da.float() @ b.float().t()) * _dgelu(h.float()) / (1 - p)
-    assert_close(d[keep], ref[keep], 1e-2, "dgelu survivors")
+    _lib.lib.hs_gemm_nt_set_tile(tile)
+    try:
+        h, act = _gemm(a, b, bias, epi=_lib.HS_EPI_GELU, p=p, seed=seed)
+        plain = ops.GeluDropoutFn.apply(h, p, seed)
+        assert torch.equal(act == 0, plain == 0)
+        if (m, n) == (512, 384):  # (3.7 standard deviations of the rate there; the small shape's 39 600 elements would leave two)
+            assert abs(float((act != 0).float().mean()) - (1 - p)) < 5e-3
+        keep = (act != 0)
+        assert_close(act[keep], plain[keep], 1e-2, "survivors")
+        da = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)  # reuse shapes: d = (da b^T) * mask/(1-p) * gelu'(h)
+        d, _ = _gemm(da, b, None, epi=_lib.HS_EPI_DGELU, aux=h, p=p, seed=seed)
+        assert torch.equal(d == 0, act == 0)
+        ref = (da.float() @ b.float().t()) * _dgelu(h.float()) / (1 - p)
+        assert_close(d[keep], ref[keep], 1e-2, "dgelu survivors")
+    finally:
+        _lib.lib.hs_gemm_nt_set_tile(0)
+
+
+def test_gemm_nt_dropout_mask_equals_the_gelu_kernels():
+    """Same (seed, element index) -> same keep decision as hs_gelu_fwd, so a model may mix fused and unfused MLPs, and the
+    backward epilogue regenerates the forward's mask.  (The built-in tile choice at 512 x 384 x 128; the other tiles and the
+    ragged shape: test_gemm_nt_dropout_mask_on_every_tile.)"""
+    _check_dropout_mask(512, 384, 128, 0)
+
+
+# the case above on the forced tiles, and (300, 132, 96) on every tile: n % 8 == 4 (the direct 8-byte store path; odd rows begin in
+# the middle of a generator chunk; under tile 3 the GELU' call falls back to the 256 x 128 tile), k % 64 != 0 (the K-tail kernels),
+# partial tiles in m and n
+@pytest.mark.parametrize("m,n,k,tile", [(512, 384, 128, 1), (512, 384, 128, 2), (512, 384, 128, 3), (300, 132, 96, 0), (300, 132, 96, 1),
+                                        (300, 132, 96, 2), (300, 132, 96, 3)])
+def test_gemm_nt_dropout_mask_on_every_tile(m, n, k, tile):
+    _check_dropout_mask(m, n, k, tile)
 
 
 def test_gemm_nt_rejects_unsupported_arguments():

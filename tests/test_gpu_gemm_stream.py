@@ -52,22 +52,14 @@ def _gemm(a, b, bias=None, epi=0, aux=None, a2=None, b2=None, p=0.0, seed=0):
 
 
 def _variant(forced, m, n, k, k2, epi):
-    """The tile variant hs_gemm_nt launches (the built-in choice of csrc/gemm_nt.hip restated, so that the case knows its tile grid)."""
+    """The tile variant hs_gemm_nt launches under hs_gemm_nt_set_tile(forced) (asked of the library, so that the case knows its
+    tile grid); leaves the built-in choice set."""
     L = _lib()
-    v = forced
-    if not v:
-        tiles2, tiles3 = -(-m // 256) * -(-n // 128), -(-m // 256) * -(-n // 256)
-        if tiles2 < 256:
-            v = 1
-        elif (n >= 512) if epi in (L.HS_EPI_GELU, L.HS_EPI_DGELU) else (n >= 1024 and k + k2 >= 512):
-            v = 3
-        elif n >= 256 and tiles3 >= 768 and k % 64 == 0 and k2 % 64 == 0:
-            v = 3
-        else:
-            v = 2
-    if v == 3 and epi in (L.HS_EPI_DGELU, L.HS_EPI_RESID) and n % 8:
-        v = 2
-    return v
+    L.lib.hs_gemm_nt_set_tile(forced)
+    try:
+        return int(L.lib.hs_gemm_nt_tile_variant(m, n, k, k2, epi))
+    finally:
+        L.lib.hs_gemm_nt_set_tile(0)
 
 
 class _Layout:
@@ -154,6 +146,7 @@ def test_gemm_nt_multi_tile_workgroups_vs_fp64(tile, k, k2, reserved):
     ns = [n for n in NS[tile] if all(_Layout(_variant(tile, m, n, k, k2, e), m, n, reserved).reaches() for e in epis)]
     assert ns, (tile, k, k2, reserved)
     n = ns[ki % len(ns)]
+    lays = {e: _Layout(_variant(tile, m, n, k, k2, e), m, n, reserved) for e in epis}
     g = torch.Generator(device=DEV).manual_seed(1000 * ki + 10 * ri + tile)
     kt = k + k2
     # A: a column slice of a wider buffer (lda = k + 8) for the BIAS and RESID launches, a contiguous copy for the others
@@ -177,11 +170,8 @@ def test_gemm_nt_multi_tile_workgroups_vs_fp64(tile, k, k2, reserved):
         L.lib.hs_gemm_nt_set_tile(tile)
         tag = f"gemm_nt stream tile={tile} m={m} n={n} k={k}+{k2} reserved={reserved}"
 
-        def layout(epi):
-            return _Layout(_variant(tile, m, n, k, k2, epi), m, n, reserved)
-
         # BIAS (strided A), twice: no atomics, so two launches agree to the bit
-        lay = layout(L.HS_EPI_BIAS)
+        lay = lays[L.HS_EPI_BIAS]
         c, _ = _gemm(a_s, b, bias, a2=a2, b2=b2)
         _check(bad, c, hb, 6e-3, tag + " bias (lda = k + 8)", lay, bias64)
         c2, _ = _gemm(a_s, b, bias, a2=a2, b2=b2)
@@ -190,7 +180,7 @@ def test_gemm_nt_multi_tile_workgroups_vs_fp64(tile, k, k2, reserved):
         del c, c2
 
         # GELU, p = 0: h and gelu(h)
-        lay = layout(L.HS_EPI_GELU)
+        lay = lays[L.HS_EPI_GELU]
         h, act = _gemm(a, b, bias, epi=L.HS_EPI_GELU, a2=a2, b2=b2)
         _check(bad, h, hb, 6e-3, tag + " gelu: h", lay, bias64)
         gref = torch.nn.functional.gelu(hb)
@@ -214,7 +204,7 @@ def test_gemm_nt_multi_tile_workgroups_vs_fp64(tile, k, k2, reserved):
         del h, act, h2, act2, gref
 
         # DGELU, p = 0 and 0.25 (no bias: c = acc * mask * gelu'(aux))
-        lay = layout(L.HS_EPI_DGELU)
+        lay = lays[L.HS_EPI_DGELU]
         hs = (torch.randn((m, n), generator=g, device=DEV) * 1.5).to(BF)
         dref = ref * _dgelu(hs.double())
         d, _ = _gemm(a, b, None, epi=L.HS_EPI_DGELU, aux=hs, a2=a2, b2=b2)
@@ -229,7 +219,7 @@ def test_gemm_nt_multi_tile_workgroups_vs_fp64(tile, k, k2, reserved):
         del hs, dref, d, keep
 
         # RESID (strided A): c = acc + bias + aux
-        lay = layout(L.HS_EPI_RESID)
+        lay = lays[L.HS_EPI_RESID]
         res = torch.randn((m, n), generator=g, device=DEV).to(BF)
         r, _ = _gemm(a_s, b, bias, epi=L.HS_EPI_RESID, aux=res, a2=a2, b2=b2)
         _check(bad, r, hb + res.double(), 6e-3, tag + " resid (lda = k + 8)", lay, bias64)

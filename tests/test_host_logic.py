@@ -223,3 +223,43 @@ def test_weight_split_cache_hits_for_fresh_views_and_follows_the_weight_epoch(mo
         ops._weight_split(torch.zeros(8, 8), False)
     assert len(ops._WSPLIT) <= ops._WSPLIT_CAPACITY
     ops._WSPLIT.clear()
+
+
+# (m, n, k, k2, epilogue, variant): the boundaries of hs_gemm_nt's tile rule (csrc/gemm_nt.hip: gemm_nt_tile_variant)
+GEMM_TILE_RULE = [
+    (65280, 128, 128, 0, "BIAS", 1),    # 255 x 1 tiles of 256 x 128 < 256: does not fill the chip
+    (65281, 128, 128, 0, "BIAS", 2),    # 256 tiles, n < 256
+    (32768, 512, 128, 0, "GELU", 3),    # a GELU epilogue with n >= 512
+    (32768, 504, 128, 0, "GELU", 2),    # n < 512, and 256 tiles of 256 x 256 < 768
+    (8192, 1024, 512, 0, "BIAS", 3),    # n >= 1024 and k >= 512
+    (8192, 1024, 448, 64, "BIAS", 3),   # k + k2 counts
+    (8192, 1024, 448, 0, "BIAS", 2),    # k < 512, 128 tiles of 256 x 256
+    (196608, 256, 64, 0, "BIAS", 3),    # 768 tiles of 256 x 256, no K tail
+    (196352, 256, 64, 0, "BIAS", 2),    # 767 tiles
+    (196608, 256, 96, 0, "BIAS", 2),    # k % 64 != 0
+    (196608, 256, 64, 32, "BIAS", 2),   # k2 % 64 != 0
+    (32768, 516, 128, 0, "DGELU", 2),   # n % 8 != 0 with an epilogue input: the 256 x 256 tile's DMA ring cannot take it
+    (8192, 1028, 512, 0, "RESID", 2),   # the same
+    (32768, 516, 128, 0, "GELU", 3),    # no fallback without an epilogue input
+]
+
+
+def test_gemm_nt_tile_rule_boundaries_and_forced_variants():
+    from heal_swin_amd import _lib as L
+    epi = {"BIAS": L.HS_EPI_BIAS, "GELU": L.HS_EPI_GELU, "DGELU": L.HS_EPI_DGELU, "RESID": L.HS_EPI_RESID}
+    query = L.lib.hs_gemm_nt_tile_variant
+    try:
+        L.lib.hs_gemm_nt_set_tile(0)
+        for m, n, k, k2, e, want in GEMM_TILE_RULE:
+            assert int(query(m, n, k, k2, epi[e])) == want, (m, n, k, k2, e)
+        # a forced variant is returned as it is, whatever the rule says for the shape ...
+        for forced in (1, 2, 3):
+            L.lib.hs_gemm_nt_set_tile(forced)
+            for m, n, k, k2, e, _ in GEMM_TILE_RULE:
+                fallback = forced == 3 and e in ("DGELU", "RESID") and n % 8
+                assert int(query(m, n, k, k2, epi[e])) == (2 if fallback else forced), (forced, m, n, k, k2, e)
+        # ... except through the n % 8 fallback (rows 12 and 13 above under forced 3), which has run
+        assert sum(1 for _, n, _, _, e, _ in GEMM_TILE_RULE if e in ("DGELU", "RESID") and n % 8) == 2
+    finally:
+        L.lib.hs_gemm_nt_set_tile(0)
+    assert [int(query(m, n, k, k2, epi[e])) for m, n, k, k2, e, _ in GEMM_TILE_RULE] == [r[-1] for r in GEMM_TILE_RULE]
