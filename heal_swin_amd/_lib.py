@@ -163,6 +163,9 @@ _SIGNATURES = {
     "hs_adam_step_groups_guarded": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_i64, c_ptr, c_float,
                                     c_ptr, c_int, c_ptr],
     "hs_grad_scale": [c_ptr, c_i64, c_float, c_ptr, c_ptr],
+    "hs_weight_avg_update": [c_ptr, c_ptr, c_i64, c_int, c_float, c_ptr, c_ptr, c_int, c_ptr],
+    "hs_weight_avg_advance": [c_ptr, c_ptr, c_int, c_ptr],
+    "hs_weight_avg_swap": [c_ptr, c_ptr, c_ptr, c_i64, c_ptr],
     "hs_split_bf16x3": [c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr],
     "hs_gelu_split3": [c_ptr, c_ptr, c_ptr, c_i64, c_int, ctypes.c_float, ctypes.c_uint64, c_ptr],
     "hs_linear_wgrad_ld": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr],

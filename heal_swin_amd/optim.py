@@ -26,7 +26,12 @@ Guard rails (the reference trainer's gradient_clip_val / gradient_clip_algorithm
 training/train_config.py:65-66,76,104): `max_grad_norm=` / `clip_value=`, `track_grad_norm=True`, `skip_nonfinite=True`.  With any of
 them `step()` first measures the buckets (`GradGuard`: one read-only pass, csrc/grad_guard.hip) and then runs the guarded Adam
 launches, which take the clip coefficient and the finite flag from device memory -- no host read, the step stays capturable.
+
+Weight averaging (the reference trainer's stochastic_weight_avg, training/train_config.py:112, and its every-step form, EMA):
+`FlatWeightAverage(optimizer, "swa" | "ema")` keeps the average in one more flat buffer per bucket, updates it with one
+`hs_weight_avg_update` launch per bucket (csrc/weight_avg.hip) and swaps it into the model for validation, bf16 copies included.
 """
+import contextlib
 import math
 
 import torch
@@ -332,6 +337,8 @@ class FlatAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if getattr(self, "_averaged_in_place", None) is not None:
+            raise RuntimeError("FlatAdam.step() inside FlatWeightAverage.applied(): the parameters are the averaged weights until the block ends")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -417,3 +424,139 @@ class FlatAdam(torch.optim.Optimizer):
             # no step count in the loaded state = a state that never stepped: moments (zeroed above) and bias correction agree
             self._step.fill_(int(float(step)) if step is not None else 0)
         ops.RT.weight_epoch += 1
+
+
+_AVG_KINDS = {"swa": 0, "ema": 1}
+
+
+class FlatWeightAverage:
+    """A running average of a FlatAdam's parameters, kept in flat buffers next to them: torch.optim.swa_utils.AveragedModel without the
+    second module.
+
+        avg = FlatWeightAverage(opt, "ema", decay=0.999)       # updated at the end of every opt.step(), also under graph replay
+        avg = FlatWeightAverage(opt, "swa")                    # avg.update() once per epoch, from the trainer's swa_epoch_start on
+        with avg.applied():                                    # the model IS the averaged model inside: validate, export
+            validate(model)
+        avg.copy_to_model()                                    # the end of an SWA run
+
+    kind "swa": the equal average of AveragedModel's default (`avg += (p - avg) / (n_averaged + 1)`); "ema": `avg = decay * avg +
+    (1 - decay) * p` (`get_ema_multi_avg_fn(decay)`).  The first update copies the parameters.  Both are ATen's lerp in fp32, one
+    `hs_weight_avg_update` launch per bucket; `n_averaged` is a 0-dim int64 DEVICE tensor the kernels read and `hs_weight_avg_advance`
+    increments, so `update()` allocates nothing, never synchronises and is capturable.  With a `skip_nonfinite` optimizer an update follows
+    the guard record of the last step: a skipped step is not averaged.
+    every_step: register `update` as a step post-hook of the optimizer (None: True for "ema", False for "swa"); `detach()` removes it.
+    model: the module whose bf16 parameter copies must follow a swap (default: the optimizer's `model=`).
+    The model has only LayerNorms and constant buffers: there is no `update_bn` and no buffer averaging to do."""
+
+    def __init__(self, optimizer, kind="swa", decay=0.999, every_step=None, model=None):
+        if not isinstance(optimizer, FlatAdam):
+            raise ValueError("FlatWeightAverage averages the flat parameter buffers of a heal_swin_amd.optim.FlatAdam")
+        if kind not in _AVG_KINDS:
+            raise ValueError(f"kind must be 'swa' or 'ema', got {kind!r}")
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError("decay must be in [0, 1]")
+        self.optimizer, self.kind, self.decay = optimizer, kind, float(decay)
+        self._model = model if model is not None else optimizer._model
+        self.n_averaged = torch.zeros((), dtype=torch.int64, device=optimizer._step.device)
+        self._flat_avg = [torch.zeros_like(P) for P in optimizer._flat_p]  # (the alignment gaps: p = 0 there, so avg stays 0)
+        self._view = {}
+        sink = optimizer.sink
+        for p in sink.params:
+            b = sink._where[p]
+            off = sink._views[p].storage_offset() - sink.buckets[b].storage_offset()
+            self._view[id(p)] = self._flat_avg[b][off:off + p.numel()].view_as(p)
+        self._hook = None
+        if (kind == "ema") if every_step is None else every_step:
+            self._hook = optimizer.register_step_post_hook(lambda *a, **k: self.update())
+
+    def of(self, p):
+        """The average of parameter p: a view into the flat buffer (same shape as p)."""
+        return self._view[id(p)]
+
+    def detach(self):
+        """Stop following the optimizer's steps (`every_step`)."""
+        if self._hook is not None:
+            self._hook.remove()
+            self._hook = None
+
+    def _refuse_inside_applied(self, what):
+        if getattr(self.optimizer, "_averaged_in_place", None) is not None:
+            raise RuntimeError(f"FlatWeightAverage.{what} inside applied(): parameters and average have changed places until the block ends")
+
+    @torch.no_grad()
+    def update(self):
+        """Take the optimizer's parameters as they are now into the average (on the current stream)."""
+        self._refuse_inside_applied("update()")
+        opt = self.optimizer
+        guarded = opt.guard is not None and opt.skip_nonfinite
+        rec, skip = (ptr(opt.guard.record) if guarded else None), int(guarded)
+        s, count = stream_ptr(self.n_averaged.device), ptr(self.n_averaged)
+        for A, P in zip(self._flat_avg, opt._flat_p):
+            check(lib.hs_weight_avg_update(ptr(A), ptr(P), P.numel(), _AVG_KINDS[self.kind], self.decay, count, rec, skip, s), "hs_weight_avg_update")
+        check(lib.hs_weight_avg_advance(count, rec, skip, s), "hs_weight_avg_advance")
+
+    def _parameters_changed(self):
+        # as FlatAdam._stepped: the parameters changed through raw pointers.  The bf16 copies FlatAdam owns were written with them;
+        # a cast cache with copies of its own (or an optimizer without a model) has to re-make them at the next forward
+        ops.RT.weight_epoch += 1
+        cache = None if self._model is None else self._model.__dict__.get("_cast_cache")
+        if cache is not None:
+            if self.optimizer.lowp_dtype is not None and cache.all_external:
+                cache.mark_refreshed_externally()
+            else:
+                cache.invalidate()
+
+    def _swap(self):
+        opt = self.optimizer
+        s = stream_ptr(self.n_averaged.device)
+        for P, A, S in zip(opt._flat_p, self._flat_avg, opt._flat_lowp):
+            check(lib.hs_weight_avg_swap(ptr(P), ptr(A), ptr(S), P.numel(), s), "hs_weight_avg_swap")
+        self._parameters_changed()
+
+    @contextlib.contextmanager
+    def applied(self):
+        """Inside, the model's parameters (and the optimizer's bf16 copies of them) are the averaged weights and `of(p)` holds the trained
+        ones: one `hs_weight_avg_swap` per bucket on the way in, one on the way out -- also when the block raises.  Two swaps restore
+        every bit.  `optimizer.step()` and `update()` inside raise RuntimeError."""
+        self._refuse_inside_applied("applied()")
+        with torch.no_grad():
+            self._swap()
+        self.optimizer._averaged_in_place = self
+        try:
+            yield self
+        finally:
+            self.optimizer._averaged_in_place = None
+            with torch.no_grad():
+                self._swap()
+
+    @torch.no_grad()
+    def copy_to_model(self):
+        """The end of an SWA run: parameters and their bf16 copies become the average (which is kept)."""
+        self._refuse_inside_applied("copy_to_model()")
+        for P, A, S in zip(self.optimizer._flat_p, self._flat_avg, self.optimizer._flat_lowp):
+            P.copy_(A)
+            if S is not None:
+                S.copy_(A)
+        self._parameters_changed()
+
+    def state_dict(self):
+        """kind, decay, n_averaged (an int: SYNCHRONISES) and a copy of every parameter's average, in the sink's parameter order."""
+        return {"kind": self.kind, "decay": self.decay, "n_averaged": int(self.n_averaged),
+                "averages": [self.of(p).detach().clone() for p in self.optimizer.sink.params]}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """The averages are COPIED into the flat buffers (the views keep pointing there); kind must match, decay is taken over."""
+        params = self.optimizer.sink.params
+        averages = state_dict["averages"]
+        if state_dict["kind"] != self.kind:
+            raise ValueError(f"the state holds a {state_dict['kind']!r} average, this is {self.kind!r}")
+        if not 0.0 <= float(state_dict["decay"]) <= 1.0:
+            raise ValueError("decay must be in [0, 1]")
+        if len(averages) != len(params) or any(a.shape != p.shape for a, p in zip(averages, params)):
+            raise ValueError("the state holds the averages of other parameters")
+        self._refuse_inside_applied("load_state_dict()")
+        self.decay = float(state_dict["decay"])
+        for a, p in zip(averages, params):
+            self.of(p).copy_(a)
+        self.n_averaged.fill_(int(state_dict["n_averaged"]))

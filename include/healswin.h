@@ -568,6 +568,32 @@ int hs_adam_advance_guarded(int64_t* step, const hs_grad_guard* guard, int skip_
 int hs_grad_scale(float* g, int64_t n, float clip_value, const hs_grad_guard* guard, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Weight averaging over the flat buffers: SWA -- the reference trainer's stochastic_weight_avg (training/train_config.py:112), i.e.
+ * torch.optim.swa_utils.AveragedModel with its default equal average -- and EMA, the same thing at every step.  The average avg
+ * [dev] f32[n] is laid out like the parameters p [dev] f32[n] of hs_adam_step (both 16-byte aligned); n_averaged [dev] int64[1]
+ * counts the updates taken so far and is read ON THE DEVICE, so a captured step replays with the right weight.
+ *
+ *   hs_weight_avg_update    one launch per buffer, 8 B read + 4 B written per element:
+ *                               *n_averaged == 0:  avg = p   (AveragedModel.update_parameters' first call; bit for bit)
+ *                               otherwise:         avg = w < 0.5 ? avg + w (p - avg) : p - (p - avg)(1 - w)    (ATen's lerp, fp32)
+ *                               kind 0 (SWA): w = 1.f / (float)(*n_averaged + 1);   kind 1 (EMA): w = 1.f - decay
+ *                           guard may be NULL.  With guard, skip_nonfinite != 0 and guard->finite == 0 -- the optimizer step this
+ *                           update follows was dropped (hs_adam_step_guarded) -- the launch writes nothing.
+ *   hs_weight_avg_advance   adds 1 to *n_averaged unless the update was skipped by the same rule; after the last buffer of an update,
+ *                           as hs_adam_advance.
+ *   hs_weight_avg_swap      exchanges p and avg in place, 8 B read + 8 B written per element (10 with the copy).  p_bf16 [dev] bf16[n]
+ *                           (may be NULL; 8-byte aligned) receives the NEW p rounded to bf16, as hs_adam_step writes it.  Bits are
+ *                           moved, not computed: two swaps restore p, avg and the copy exactly.
+ * No allocation, no synchronisation, capturable.  Every refusal is HS_ERR_INVALID_ARG and is decided before anything is launched: a
+ * null avg, p or n_averaged, n <= 0 or >= 2^40, kind outside {0, 1}, decay outside [0, 1] (a NaN included), avg or p off a 16-byte
+ * boundary, p_bf16 off an 8-byte one, n_averaged or guard off its natural alignment, p == avg in the swap.
+ * ---------------------------------------------------------------------------------------------- */
+int hs_weight_avg_update(float* avg, const float* p, int64_t n, int kind, float decay, const int64_t* n_averaged, const hs_grad_guard* guard,
+                         int skip_nonfinite, void* stream);
+int hs_weight_avg_advance(int64_t* n_averaged, const hs_grad_guard* guard, int skip_nonfinite, void* stream);
+int hs_weight_avg_swap(float* p, float* avg, void* p_bf16, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused WindowAttention MODULE forward (inference form here, training form and the module backward below): the whole of WindowAttention.forward,
  * models_torch/swin_hp_transformer.py:124-174 -- qkv Linear, head split, (cosine | scaled) scores, relative-position bias,
  * shift mask, softmax, P V, head merge, proj Linear -- with the shift / window partition / reverse / shift back of
