@@ -97,6 +97,8 @@ struct DropRng {
 // fp32-VALU path: any power-of-two Ws in [4, 256], head_dim <= 128; fp32 or bf16 I/O
 int launch_attn_fwd_generic(const AttnParams& p, int dtype, hipStream_t stream);
 int launch_attn_bwd_generic(const AttnParams& p, int dtype, hipStream_t stream);
+// host-side: whether the backward serves (Ws, head_dim) -- its LDS footprint is twice the forward's; nothing is launched or written
+int check_attn_bwd_generic(const AttnParams& p);
 
 // MFMA path: Ws == 64, head_dim == 32, bf16 I/O
 bool attn_mfma_supported(const AttnParams& p, int dtype);

@@ -112,6 +112,9 @@ int hs_window_attn_bwd(const void* qkv, const void* out, const void* dout, const
     hipStream_t s = (hipStream_t)stream;
     const Route route = route_of(p, dtype, flags);
     if (route == Route::kMfmaBf16) return hs::launch_attn_bwd_mfma(p, workspace, s);
+    // (what the VALU backward cannot serve is refused before the zero fill below: a failing call writes nothing)
+    if (route == Route::kGeneric)
+        if (int st = hs::check_attn_bwd_generic(p)) return st;
     // HS_ATTN_OVERWRITE_GRADS is a contract of the ENTRY POINT: the bf16 MFMA path writes dbias / dhead_scale, every other path
     // accumulates -- so a caller that set the flag (and handed over uninitialised buffers) gets them zeroed here first
     if (flags & HS_ATTN_OVERWRITE_GRADS) {

@@ -116,8 +116,13 @@ __global__ void __launch_bounds__(256) attn_fwd_generic_kernel(AttnParams p) {
 
 // Backward.  Phase A: thread = query row (dq, bias/scale gradients).  Phase B: thread = key row
 // (dk, dv), re-deriving the probabilities from the saved log-sum-exp.
+// D_i = dO_i . O_i: fp32 I/O reads the saved output.  With bf16 I/O that output is ROUNDED, and its rounding would enter every
+// gradient through D (up to 50 bf16 ulp on an element of dqkv, 4e-2 of dhead_scale at a few hundred rows); the bf16 instantiation
+// forms D_i = sum_j P_ij m_ij dP_ij in fp32 in a first walk over the keys instead (as the bf16 MFMA kernel) and never reads `out`:
+// both instantiations then run the same fp32 arithmetic on the same values.
 template <typename T, int HD>
 __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(AttnParams p) {
+    constexpr bool kOwnDsum = !std::is_same<T, float>::value;
     apply_seed_epoch(p);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int LD = HD + 1;
@@ -127,7 +132,7 @@ __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(AttnParams p) {
     float* v_s = k_s + nthr * LD;
     float* do_s = v_s + nthr * LD;
     float* lse_s = do_s + nthr * LD;
-    float* dsum_s = lse_s + nthr;   // D_i = dO_i . O_i
+    float* dsum_s = lse_s + nthr;   // D_i
     int* lab_s = (int*)(dsum_s + nthr);
 
     const int64_t g = (int64_t)blockIdx.x * nthr + t;
@@ -152,7 +157,7 @@ __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(AttnParams p) {
             const float kv = in ? io<T>::load(p.qkv, base + p.C + d) : 0.f;
             const float vv = in ? io<T>::load(p.qkv, base + 2 * p.C + d) : 0.f;
             const float dov = in ? io<T>::load(p.dout, obase + d) : 0.f;
-            const float ov = in ? io<T>::load(p.out, obase + d) : 0.f;
+            const float ov = (in && !kOwnDsum) ? io<T>::load(p.out, obase + d) : 0.f;
             q_s[t * LD + d] = qv;
             k_s[t * LD + d] = kv;
             v_s[t * LD + d] = vv;
@@ -173,18 +178,17 @@ __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(AttnParams p) {
             }
         }
         lse_s[t] = p.lse[((int64_t)b * p.nH + h) * p.N + j];
-        dsum_s[t] = dsum;
+        if constexpr (!kOwnDsum) dsum_s[t] = dsum;
         lab_s[t] = p.labels ? (int)p.labels[j] : 0;
     }
     __syncthreads();
 
     float dscale_acc = 0.f;
+    const int i = (int)(j % Ws);
+    const int t0 = t - i;
+    const int my_lab = valid ? lab_s[t] : 0;
+    const int64_t base = tok * 3 * p.C + (int64_t)h * hd;
     if (valid) {
-        const int i = (int)(j % Ws);
-        const int t0 = t - i;
-        const int my_lab = lab_s[t];
-        const int64_t base = tok * 3 * p.C + (int64_t)h * hd;
-
         // ---------------- phase A: this thread is query row i
         {
             float qh[HD], dov[HD], dq[HD];
@@ -194,15 +198,17 @@ __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(AttnParams p) {
                 dov[d] = do_s[t * LD + d];
                 dq[d] = 0.f;
             }
-            const float my_lse = lse_s[t], my_dsum = dsum_s[t];
+            const float my_lse = lse_s[t];
             const bool dropping = p.drop_p > 0.f;
             const DropRng rng(p, ((int64_t)b * p.nH + h) * p.N + j);
             const float* bias_row = p.bias ? p.bias + ((int64_t)h * Ws + i) * Ws : nullptr;
             float* dbias_row = p.dbias ? p.dbias + ((int64_t)h * Ws + i) * Ws : nullptr;
-            for (int jj = 0; jj < Ws; ++jj) {
+            // probability of key jj; dot = q_hat . k_hat and dp = mask * dO . v of the pair
+            auto prob = [&](int jj, float& dot, float& dp) __attribute__((always_inline)) {
                 const float* kr = k_s + (t0 + jj) * LD;
                 const float* vr = v_s + (t0 + jj) * LD;
-                float dot = 0.f, dp = 0.f;
+                dot = 0.f;
+                dp = 0.f;
 #pragma unroll
                 for (int d = 0; d < HD; ++d) {
                     dot = fmaf(qh[d], kr[d], dot);
@@ -211,8 +217,24 @@ __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(AttnParams p) {
                 float s = hscale * dot;
                 if (bias_row) s += bias_row[jj];
                 if (lab_s[t0 + jj] != my_lab) s += kMaskValue;
-                const float pr = expf(s - my_lse);
                 if (dropping) dp *= rng.mult(jj);  // d(out)/d(P) passes through the mask
+                return expf(s - my_lse);
+            };
+            float my_dsum = 0.f;
+            if constexpr (kOwnDsum) {
+                for (int jj = 0; jj < Ws; ++jj) {
+                    float dot, dp;
+                    const float pr = prob(jj, dot, dp);
+                    my_dsum = fmaf(pr, dp, my_dsum);
+                }
+                dsum_s[t] = my_dsum;  // (phase B reads it behind the barrier below)
+            } else {
+                my_dsum = dsum_s[t];
+            }
+            for (int jj = 0; jj < Ws; ++jj) {
+                const float* kr = k_s + (t0 + jj) * LD;
+                float dot, dp;
+                const float pr = prob(jj, dot, dp);
                 const float ds = pr * (dp - my_dsum);
                 const float dsk = ds * hscale;
 #pragma unroll
@@ -232,6 +254,9 @@ __global__ void __launch_bounds__(256) attn_bwd_generic_kernel(AttnParams p) {
             for (int d = 0; d < HD; ++d)
                 if (d < hd) io<T>::store(p.dqkv, base + d, dq[d]);
         }
+    }
+    if constexpr (kOwnDsum) __syncthreads();
+    if (valid) {
         // ---------------- phase B: this thread is key row i
         {
             float kh[HD], vv[HD], dk[HD], dv[HD];
@@ -308,11 +333,16 @@ int launch_fwd(const AttnParams& p, hipStream_t stream) {
     return HS_OK;
 }
 
+// LDS bytes of the backward kernel and the head-dim template that serves head_dim (0: none)
+size_t bwd_lds_bytes(int Ws, int HD) { return (size_t)(Ws > 64 ? Ws : 64) * (4 * (HD + 1) + 3) * sizeof(float); }
+constexpr int template_hd(int hd) {
+    return hd <= 2 ? 2 : hd <= 4 ? 4 : hd <= 8 ? 8 : hd <= 16 ? 16 : hd <= 32 ? 32 : hd <= 64 ? 64 : hd <= 128 ? 128 : 0;
+}
+
 template <typename T, int HD>
-int launch_bwd(const AttnParams& p, hipStream_t stream) {
+int launch_bwd(const AttnParams& p, hipStream_t stream) {  // (check_attn_bwd_generic has passed)
     const int nthr = p.Ws > 64 ? p.Ws : 64;
-    const size_t smem = (size_t)nthr * (4 * (HD + 1) + 3) * sizeof(float);
-    if (smem > 160 * 1024) return fail(HS_ERR_UNSUPPORTED, "window %d x head_dim %d needs %zu B of LDS (backward)", p.Ws, p.hd, smem);
+    const size_t smem = bwd_lds_bytes(p.Ws, HD);
     auto kern = attn_bwd_generic_kernel<T, HD>;
     if (smem > 48 * 1024) HS_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const int64_t rows = (int64_t)p.B * p.N;
@@ -336,15 +366,15 @@ int dispatch_fwd(const AttnParams& p, hipStream_t s) {
 }
 template <typename T>
 int dispatch_bwd(const AttnParams& p, hipStream_t s) {
-    const int hd = p.hd;
-    if (hd <= 2) return launch_bwd<T, 2>(p, s);
-    if (hd <= 4) return launch_bwd<T, 4>(p, s);
-    if (hd <= 8) return launch_bwd<T, 8>(p, s);
-    if (hd <= 16) return launch_bwd<T, 16>(p, s);
-    if (hd <= 32) return launch_bwd<T, 32>(p, s);
-    if (hd <= 64) return launch_bwd<T, 64>(p, s);
-    if (hd <= 128) return launch_bwd<T, 128>(p, s);
-    return fail(HS_ERR_UNSUPPORTED, "head_dim %d > 128 (backward)", hd);
+    switch (template_hd(p.hd)) {
+        case 2: return launch_bwd<T, 2>(p, s);
+        case 4: return launch_bwd<T, 4>(p, s);
+        case 8: return launch_bwd<T, 8>(p, s);
+        case 16: return launch_bwd<T, 16>(p, s);
+        case 32: return launch_bwd<T, 32>(p, s);
+        case 64: return launch_bwd<T, 64>(p, s);
+        default: return launch_bwd<T, 128>(p, s);
+    }
 }
 
 }  // namespace
@@ -352,7 +382,15 @@ int dispatch_bwd(const AttnParams& p, hipStream_t s) {
 int launch_attn_fwd_generic(const AttnParams& p, int dtype, hipStream_t stream) {
     return dtype == HS_BF16 ? dispatch_fwd<bf16_t>(p, stream) : dispatch_fwd<float>(p, stream);
 }
+int check_attn_bwd_generic(const AttnParams& p) {
+    const int HD = template_hd(p.hd);
+    if (!HD) return fail(HS_ERR_UNSUPPORTED, "head_dim %d > 128 (backward)", p.hd);
+    const size_t smem = bwd_lds_bytes(p.Ws, HD);
+    if (smem > 160 * 1024) return fail(HS_ERR_UNSUPPORTED, "window %d x head_dim %d needs %zu B of LDS (backward)", p.Ws, p.hd, smem);
+    return HS_OK;
+}
 int launch_attn_bwd_generic(const AttnParams& p, int dtype, hipStream_t stream) {
+    if (int st = check_attn_bwd_generic(p)) return st;
     return dtype == HS_BF16 ? dispatch_bwd<bf16_t>(p, stream) : dispatch_bwd<float>(p, stream);
 }
 

@@ -262,9 +262,10 @@ class WindowAttnCoreFn(torch.autograd.Function):
         dscale = zeros[nb:].view(hs.shape)
         nws = int(lib.hs_window_attn_bwd_workspace(B, N, C, nh, ws, dt))
         wsp = torch.empty(nws, dtype=torch.float32, device=qkv.device) if nws else None
-        # algorithmic traffic: qkv (3C) + dout (C) read, dqkv (3C) written -- plus out (C) in the fp32 / VALU kernels; the bf16
-        # MFMA kernel forms D = rowsum(P o dP) from its own registers and never reads `out`; flops: 5 contractions of 2*Ws*hd
-        streams = 7 if mfma_bf16 else 8
+        # algorithmic traffic: qkv (3C) + dout (C) read, dqkv (3C) written -- plus out (C) in the fp32 kernels; the bf16
+        # kernels (MFMA and VALU) form D = rowsum(P o dP) in fp32 themselves and never read the rounded `out`; flops: 5 contractions
+        # of 2*Ws*hd
+        streams = 7 if qkv.dtype == torch.bfloat16 else 8
         with _timed("window_attn_bwd", qkv.device, streams * B * N * C * qkv.element_size(), 10 * B * N * C * ws):
             check(lib.hs_window_attn_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(dbias), ptr(dscale), ptr(wsp),
                                          ptr(bias_c), ptr(hs), ptr(idx), roll, ptr(labels),

@@ -62,7 +62,8 @@ typedef enum { HS_F32 = 0, HS_BF16 = 1 } hs_dtype;
 #define HS_ATTN_FORCE_VALU 2u  /* run the generic fp32-VALU kernels even where an MFMA kernel exists (cross-checks, A/B) */
 #define HS_ATTN_RESIDUAL 4u    /* hs_window_attn_module_fwd: out = x + module(x) (the block's residual add, :316) */
 #define HS_ATTN_OVERWRITE_GRADS 8u /* hs_window_attn_bwd, bf16 MFMA path (window 64, head_dim 32): dbias / dhead_scale are WRITTEN instead of
-                                    added into (no zero fill needed); the fp32 and VALU paths ignore the flag and accumulate */
+                                    added into (no zero fill needed); on the fp32 and VALU paths, which accumulate, the entry point
+                                    zeroes both first, so the flag means the same on every path */
 
 const char* hs_version(void);
 /* human-readable message of the last failing call on this thread ("" if none) */
@@ -198,8 +199,10 @@ int hs_cos_head_scale_many(const void* const* logit_scale, const void* const* ds
  *                    probability attn_drop, survivors scaled by 1/(1-attn_drop); the mask is a pure function of
  *                    (seed, image, head, query, key), so hs_window_attn_bwd called with the same seed reproduces it.
  *                    attn_drop = 0 (eval mode / p = 0) disables it.
- * Supported: Ws in {4,16,64,256}, Ws <= N, N % Ws == 0, head_dim in {1,2,4,8,16,32,64,128}.
- * (Ws = 64, head_dim = 32, bf16 takes the MFMA path; everything else the fp32-VALU path.)
+ * Supported: Ws any power of two in [4, 256], Ws <= N, N % Ws == 0, head_dim <= 128 (any value; padded to a power of two in
+ * registers).  (Ws = 64, head_dim = 32 takes the MFMA paths; everything else the fp32-VALU path, whose K / V rows of a
+ * workgroup must fit the LDS: the forward serves every pair but (256, head_dim > 64), the backward head_dim <= 128 up to
+ * Ws 64, <= 64 at Ws 128 and <= 32 at Ws 256.  Anything else returns HS_ERR_UNSUPPORTED before anything is launched or written.)
  */
 int hs_window_attn_fwd(const void* qkv, void* out, float* lse,
                        const float* bias, const float* head_scale,
