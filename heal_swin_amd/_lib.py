@@ -26,6 +26,7 @@ HS_DEPTH_L1, HS_DEPTH_L2, HS_DEPTH_HUBER, HS_DEPTH_LOGVAR = 0, 1, 2, 3
 HS_DT_NONE, HS_DT_LOG, HS_DT_INV = 0, 1, 2
 HS_DT_ZERO_BKG, HS_DT_1000_BKG, HS_DT_AFFINE, HS_DT_INVERSE = 1, 2, 4, 8
 HS_DEPTH_STATS_WORDS = 15
+HS_HISTOGRAM_MAX_BINS = 4096
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -135,6 +136,8 @@ _SIGNATURES = {
     "hs_depth_target": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_float, c_float, c_ptr],
     "hs_depth_stats_update": [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr],
     "hs_depth_stats_merge": [c_ptr, c_int, c_ptr, c_ptr],
+    "hs_histogram_update": [c_ptr, c_i64, c_int, c_int, c_ptr, c_int, c_ptr, c_ptr],
+    "hs_select_rows": [c_ptr, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr],
     "hs_gelu_fwd": [c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_gelu_bwd": [c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
     "hs_residual_drop": [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
@@ -224,6 +227,7 @@ _OTHER = {
     "hs_depth_points_workspace": ([c_i64, c_i64], c_i64),
     "hs_depth_metrics_partials": ([c_i64], c_i64),
     "hs_depth_stats_partials": ([c_i64], c_i64),
+    "hs_select_rows_workspace": ([c_int], c_i64),
     "hs_flat_resize_lds_bytes": ([c_int, c_int, c_int, c_int, c_int, c_int], c_i64),
     "hs_ln_head_partials": ([c_i64], c_i64),
     "hs_expand_ln_head_blocks": ([c_i64], c_i64),

@@ -13,11 +13,13 @@
 //                              reduction: per-thread shifted sums, Chan merges in a fixed tree per workgroup, then one workgroup
 //                              merges the partials, in workgroup order, into the caller's state.  No float atomics: the same
 //                              inputs in the same calls give a bit-identical state.
+//   hs_histogram_update        the script's np.histogram(all_data, bins): the same per-element value, widened to float64 and counted
+//                              against numpy's own edge table; integer counts, integer atomics.
 //
 // Transcendentals are formed in float64 and rounded once (fp32(log(double x)), fp32(exp(double x)), fp32(1 / double x)): a
 // float32 result that does not depend on the math library's float32 accuracy.  The affine steps are float32, unfused, as the
 // reference's tensor-with-scalar arithmetic.
-#include "hs_device.h"
+#include "hs_histogram.h"
 
 #pragma clang fp contract(off)
 
@@ -27,6 +29,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kStatsBlocksMax = 1024;
+constexpr int kHistBlocksMax = 512;  // every workgroup reads the edge table once
 
 struct Corner {
     bool ok;
@@ -142,15 +145,24 @@ struct ThreadStats {
     double shift, s1, s2, mn, mx, fg_mx;
 };
 
+// the value the statistics and the histogram take from one raw depth: false if it is dropped (background under masking), else
+// x = the fp32 transform
+template <int TRANSFORM>
+__device__ __forceinline__ bool stats_value(float raw, bool masking, float& x) {
+    if (masking && raw == 1000.f) return false;
+    x = raw;
+    if (TRANSFORM == HS_DT_LOG) x = (float)log((double)raw);
+    else if (TRANSFORM == HS_DT_INV) x = (float)(1.0 / (double)raw);  // the script's plain 1 / x
+    return true;
+}
+
 template <int TRANSFORM>
 __device__ __forceinline__ void stats_add(ThreadStats& t, float raw, bool masking) {
     const bool bkg = raw == 1000.f;
     t.c[HS_DSTAT_TOTAL] += 1;
     t.c[HS_DSTAT_BACKGROUND] += bkg;
-    if (masking && bkg) return;
-    float x = raw;
-    if (TRANSFORM == HS_DT_LOG) x = (float)log((double)raw);
-    else if (TRANSFORM == HS_DT_INV) x = (float)(1.0 / (double)raw);  // the script's plain 1 / x
+    float x;
+    if (!stats_value<TRANSFORM>(raw, masking, x)) return;
     t.c[HS_DSTAT_VALUES] += 1;
     t.c[HS_DSTAT_FG_VALUES] += !bkg;
     if (isnan(x)) {
@@ -234,6 +246,56 @@ __global__ void __launch_bounds__(kThreads) depth_stats_merge_kernel(const Stats
         stats_merge(a, s);
         *state = a;
     }
+}
+
+// ------------------------------------------------------------------ histogram
+// np.histogram over given edges: uint32 counters and the float64 edge table in LDS, merged into the int64 state with integer
+// atomics.  Every lane runs every iteration (wave_count needs the whole wave); a lane without a value carries live = false.
+template <int TRANSFORM>
+__global__ void __launch_bounds__(kThreads) depth_histogram_kernel(const float* __restrict__ x, int64_t n, int vec4, int masking,
+                                                                   const double* __restrict__ edges, int bins,
+                                                                   unsigned long long* __restrict__ counts) {
+    __shared__ uint32_t hist[HS_HISTOGRAM_MAX_BINS];
+    __shared__ double edge[HS_HISTOGRAM_MAX_BINS + 1];
+    for (int j = threadIdx.x; j < bins; j += kThreads) hist[j] = 0;
+    for (int j = threadIdx.x; j <= bins; j += kThreads) edge[j] = edges[j];
+    __syncthreads();
+    const double lo = edge[0], hi = edge[bins], scale = (double)bins / (hi - lo);
+    auto add = [&](bool valid, float raw) {
+        float xf = 0.f;
+        bool live = valid && stats_value<TRANSFORM>(raw, masking, xf);
+        const double v = (double)xf;
+        live = live && v >= lo && v <= hi;  // NaN, +-inf and values outside the range are dropped
+        int i = 0;
+        if (live) {
+            i = (int)((v - lo) * scale);  // an estimate only: the table decides
+            i = i < 0 ? 0 : i > bins - 1 ? bins - 1 : i;
+            while (i > 0 && v < edge[i]) --i;
+            while (i < bins - 1 && v >= edge[i + 1]) ++i;
+        }
+        hs::wave_count(hist, live, (uint32_t)i);
+    };
+    const int64_t first = (int64_t)blockIdx.x * kThreads, stride = (int64_t)gridDim.x * kThreads;
+    int64_t done = 0;
+    if (vec4) {
+        const int64_t n4 = n / 4;
+        for (int64_t base = first; base < n4; base += stride) {
+            const bool valid = base + threadIdx.x < n4;
+            const float4 v = valid ? ((const float4*)x)[base + threadIdx.x] : make_float4(0.f, 0.f, 0.f, 0.f);
+            add(valid, v.x);
+            add(valid, v.y);
+            add(valid, v.z);
+            add(valid, v.w);
+        }
+        done = n4 * 4;
+    }
+    for (int64_t base = done + first; base < n; base += stride) {
+        const bool valid = base + threadIdx.x < n;
+        add(valid, valid ? x[base + threadIdx.x] : 0.f);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < bins; j += kThreads)
+        if (hist[j] != 0) atomicAdd(&counts[j], (unsigned long long)hist[j]);
 }
 
 }  // namespace
@@ -323,6 +385,29 @@ int hs_depth_stats_merge(const int64_t* states, int count, int64_t* state, void*
     hipLaunchKernelGGL(depth_stats_merge_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const Stats*)states, count,
                        (Stats*)state);
     HS_LAUNCH_CHECK("depth_stats_merge");
+    return HS_OK;
+}
+
+int hs_histogram_update(const float* depth, int64_t n, int transform, int use_masking, const double* edges, int bins, int64_t* counts,
+                        void* stream) {
+    HS_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 40), "hs_histogram_update: bad size");
+    HS_CHECK_ARG(transform == HS_DT_NONE || transform == HS_DT_LOG || transform == HS_DT_INV, "hs_histogram_update: transform %d",
+                 transform);
+    HS_CHECK_ARG(bins >= 1 && bins <= HS_HISTOGRAM_MAX_BINS, "hs_histogram_update: bins %d outside [1, %d]", bins, HS_HISTOGRAM_MAX_BINS);
+    if (n == 0) return HS_OK;
+    HS_CHECK_ARG(depth && edges && counts, "hs_histogram_update: null pointer");
+    const int64_t want = (n + kThreads * 16 - 1) / (kThreads * 16);
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(want, kHistBlocksMax))), block(kThreads);
+    const int vec4 = (uintptr_t)depth % 16 == 0;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* c = (unsigned long long*)counts;
+    if (transform == HS_DT_LOG)
+        hipLaunchKernelGGL(depth_histogram_kernel<HS_DT_LOG>, grid, block, 0, s, depth, n, vec4, use_masking, edges, bins, c);
+    else if (transform == HS_DT_INV)
+        hipLaunchKernelGGL(depth_histogram_kernel<HS_DT_INV>, grid, block, 0, s, depth, n, vec4, use_masking, edges, bins, c);
+    else
+        hipLaunchKernelGGL(depth_histogram_kernel<HS_DT_NONE>, grid, block, 0, s, depth, n, vec4, use_masking, edges, bins, c);
+    HS_LAUNCH_CHECK("depth_histogram");
     return HS_OK;
 }
 

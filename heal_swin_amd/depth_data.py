@@ -13,6 +13,7 @@ depth in metres again, and the dataset statistics behind the normalization const
                                   zero_is_background=False), utils/depth_utils.py:140-170 (transform_and_normalize,
                                   unnormalize_and_retransform)                                              `hs_depth_target`
   DepthStatsAccumulator           compute_depth_stats.py's max / min / mean / std / counts           `hs_depth_stats_*`
+  DepthHistogram                  its np.histogram(all_data, bins=1000) -> bin_counts, bin_edges      `hs_histogram_update`
 
 Every transform is float32 with log / exp / 1/x formed in float64 and rounded once; the reference's torch calls on float32 agree
 to an ulp or so.  Normalization is float32 (x - shift) / scale forward and x * scale + shift backward with shift / scale the
@@ -29,7 +30,7 @@ import numpy as np
 import torch
 
 from ._lib import (HS_DEPTH_STATS_WORDS, HS_DT_1000_BKG, HS_DT_AFFINE, HS_DT_INV, HS_DT_INVERSE, HS_DT_LOG, HS_DT_NONE,
-                   HS_DT_ZERO_BKG, check, lib, ptr, stream_ptr)
+                   HS_DT_ZERO_BKG, HS_HISTOGRAM_MAX_BINS, check, lib, ptr, stream_ptr)
 from .evaluation import _device
 from .projection import _coords, _device_u8, hp_grid, project_s2_points_to_img
 
@@ -331,3 +332,62 @@ class DepthStatsAccumulator:
         name = f"depth data stats (data_transform={self.data_transform}, use_masking={self.use_masking})"
         return DataStats(name=name, max=mx, min=mn, mean=mean, std=std, total_pixels=c[_TOTAL], total_background=c[_BKG],
                          max_foreground=fg_mx)
+
+
+class DepthHistogram:
+    """compute_depth_stats.py's np.histogram(all_data, bins=1000) as a streaming count: update(depth) adds raw float32 depth
+    maps (any shape) on the GPU; compute() -> (bin_counts int64 [bins], bin_edges float64 [bins + 1]), np.histogram's on the
+    same values (the float32 transformed values as float64, as the script's concatenation makes them) with the same bins and
+    range: NaN, +-inf and values outside the range are dropped, the last bin is closed.  The edges are numpy's own
+    (np.histogram_bin_edges), so a degenerate range widens and an invalid one raises as numpy's does.  data_transform and
+    use_masking as DepthStatsAccumulator.  The script's range is the data's (min, max): from_stats takes it from a first pass
+    with the accumulator.  Integer counts: the same updates in any order give the same result."""
+
+    def __init__(self, bins=1000, range=None, data_transform=None, use_masking=False, device="cuda"):  # noqa: A002
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)):
+            raise TypeError(f"bins must be an integer (equal-width bins), got {type(bins).__name__}")
+        if not 1 <= bins <= HS_HISTOGRAM_MAX_BINS:
+            raise ValueError(f"bins must be in [1, {HS_HISTOGRAM_MAX_BINS}], got {bins}")
+        if range is None:
+            raise ValueError("range=(lo, hi) is required: a streaming histogram cannot take it from the data "
+                             "(DepthHistogram.from_stats takes the accumulator's min and max)")
+        lo, hi = (float(v) for v in range)
+        self.bins, self.range = int(bins), (lo, hi)
+        self.data_transform = _transform_name(data_transform)
+        self.use_masking = bool(use_masking)
+        self.bin_edges = np.histogram_bin_edges(np.empty(0, np.float64), self.bins, (lo, hi)).astype(np.float64, copy=False)
+        if torch.device(device).type != "cuda":
+            raise RuntimeError("DepthHistogram runs on the GPU only (HIP kernel, no CPU path)")
+        self.device = _device(device)
+        self._edges = torch.from_numpy(self.bin_edges).to(self.device)
+        self.counts = torch.zeros(self.bins, dtype=torch.int64, device=self.device)
+
+    @classmethod
+    def from_stats(cls, stats, bins=1000, data_transform=None, use_masking=False, device="cuda"):
+        """The histogram over [stats.min, stats.max] of a DataStats that DepthStatsAccumulator.compute() gave for the same data,
+        transform and masking: np.histogram(all_data, bins) without a range."""
+        return cls(bins, (stats.min, stats.max), data_transform, use_masking, device)
+
+    def reset(self):
+        self.counts.zero_()
+
+    def update(self, depth):
+        if not torch.is_tensor(depth) or depth.dtype != torch.float32 or depth.device != self.device:
+            raise TypeError(f"depth must be a float32 tensor on {self.device}")
+        d = depth.contiguous().reshape(-1)
+        check(lib.hs_histogram_update(ptr(d), d.numel(), TRANSFORMS[self.data_transform], int(self.use_masking), ptr(self._edges),
+                                      self.bins, ptr(self.counts), stream_ptr(self.device)), "hs_histogram_update")
+
+    def all_reduce(self, group=None):
+        """Sum the counts of all ranks."""
+        import torch.distributed as dist
+
+        dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self):
+        return self.counts.cpu().numpy(), self.bin_edges.copy()
+
+    def save(self, path):
+        """The script's np.savez(..., bin_counts=, bin_edges=)."""
+        bin_counts, bin_edges = self.compute()
+        np.savez(path, bin_counts=bin_counts, bin_edges=bin_edges)

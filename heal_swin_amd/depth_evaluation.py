@@ -32,7 +32,9 @@ Differences from the reference, by construction:
   * a point is fp32(d * (R u)) with R u a float64 table, where the reference forms fp32(R (d u)) in float64: at most an ulp.
   * theta of an image point: a float64 Newton instead of newton_krylov (see evaluation.py), <= 1e-6 rad.
   * the Chamfer term is mean(dist_a) + mean(dist_b) in float64 (the reference's torch.mean is fp32).
-  * MeanSTDMedian takes torch.median (the lower median) on the device; it is the one metric not computed by hs_depth_metrics.
+  * MeanSTDMedian is the lower median of the fp32 standard deviations by an exact radix select (order_stats.row_median,
+    `hs_select_rows`): torch.median's value bit for bit, with the rows split over the chip.  float64 standard deviations
+    take torch.median.
 """
 import math
 
@@ -41,6 +43,7 @@ import torch
 
 from ._lib import HS_BF16, HS_F32, HS_F64, check, lib, np_ptr, ptr, stream_ptr
 from .evaluation import _device, get_uv_from_hw, project_img_points_to_s2
+from .order_stats import row_median
 from .projection import _camera_rotation, hp_grid
 
 MAX_BACKGROUND = 4
@@ -338,9 +341,7 @@ class DepthMetrics:
                                           len(self.distance_ranges), ptr(partial), ptr(self.state), stream_ptr(self.device)),
               "hs_depth_metrics_gather")
         if self.use_logvar:  # MeanSTDMedian needs the projected log variance itself
-            stds = torch.sqrt(torch.exp(projector.depth(pred, channel=1)))
-            self.median[0] += stds.median(1).values.double().sum()
-            self.median[1] += b
+            self._add_stds(torch.sqrt(torch.exp(projector.depth(pred, channel=1))))
 
     def update(self, pred, target, projector=None):
         if projector is not None:
@@ -377,18 +378,23 @@ class DepthMetrics:
                                    np_ptr(rng) if rng.size else None,
                                    len(self.distance_ranges), ptr(partial), ptr(self.state), stream_ptr(self.device)),
               "hs_depth_metrics")
-        if self.use_logvar:  # MeanSTDMedian: torch's lower median per sample, on the device
+        if self.use_logvar:  # MeanSTDMedian: the lower median per sample, on the device
             lv = pred[:, 1]
-            stds = torch.sqrt(torch.exp(lv if lv.dtype == torch.float64 else lv.float())).reshape(b, -1)
-            self.median[0] += stds.median(1).values.double().sum()
-            self.median[1] += b
+            self._add_stds(torch.sqrt(torch.exp(lv if lv.dtype == torch.float64 else lv.float())).reshape(b, -1))
+
+    def _add_stds(self, stds):
+        """stds [B, n]: one lower median per sample (torch.median's value: the select for fp32, torch.median itself for float64)."""
+        if stds.dtype == torch.float32 and stds.shape[0] > 0:
+            medians = row_median(stds if stds.stride(1) == 1 else stds.contiguous())
+        else:
+            medians = stds.median(1).values
+        self.median[0] += medians.double().sum()
+        self.median[1] += stds.shape[0]
 
     def add_median(self, log_var):
         """MeanSTDMedian's part of update() alone, for a caller whose kernel has already added the sums to `state` (the decoder
         tail's depth step): log_var fp32 [B, n], one lower median of sqrt(exp(.)) per sample."""
-        stds = torch.sqrt(torch.exp(log_var.float()))
-        self.median[0] += stds.median(1).values.double().sum()
-        self.median[1] += log_var.shape[0]
+        self._add_stds(torch.sqrt(torch.exp(log_var.float())))
 
     def all_reduce(self, group=None):
         """Sum the states of all ranks (torchmetrics' dist_reduce_fx='sum')."""

@@ -1071,7 +1071,7 @@ class SwinHPTransformerSys(nn.Module):
         transform.prepare(depth); transform is a depth_data.DepthTargetTransform or None (the identity); the other arguments as
         forward_depth_loss.  Where ops.expand_ln_head_depth_ok (bf16, C in {64, 96, 128}, a head the loss kind accepts) all of it
         is ONE decoder-tail launch (`hs_expand_ln_head_depth_step_fwd`) plus the one-workgroup merge of the metric records, with a
-        gradient and without: the head rows are never written; median_std (metrics.use_logvar) takes torch.median on the written
+        gradient and without: the head rows are never written; median_std (metrics.use_logvar) takes the radix-select median of the written
         log variance (preds[:, 1], or 4 bytes per pixel of scratch).  Elsewhere the same results are composed from the head rows
         (losses.depth_step_from_rows).  No synchronisation with the host.
         Deviation from the reference (as forward_depth_loss): it takes the loss on transform_and_normalize(

@@ -868,7 +868,15 @@ int hs_depth_metrics_gather(const void* pred, int pred_kind, int64_t batch, int6
  *                       HS_DEPTH_STATS_WORDS * hs_depth_stats_partials(n) words of scratch.  Deterministic: no float atomics.
  *   hs_depth_stats_merge  state (+)= states[0], ..., states[count - 1] (each HS_DEPTH_STATS_WORDS words, [dev]), in that order.
  *                       A state starts as zero counts, mean = M2 = 0, min = +inf, max = fg max = -inf.
+ *   hs_histogram_update  compute_depth_stats.py's np.histogram: ADDS the counts of one float32 array depth [dev] f32[n] into
+ *                       counts [dev] i64[bins], 1 <= bins <= HS_HISTOGRAM_MAX_BINS.  The value counted is the one
+ *                       hs_depth_stats_update forms (same transform, same use_masking), widened to float64: bin i holds
+ *                       edges[i] <= v < edges[i + 1], the last bin is closed at edges[bins]; NaN, +-inf and values outside
+ *                       [edges[0], edges[bins]] are dropped.  edges [dev] f64[bins + 1], increasing (numpy's own
+ *                       np.histogram_bin_edges): the bin is estimated arithmetically and corrected against the table.
+ *                       Integer adds only: the counts do not depend on the order of arrival.
  * ---------------------------------------------------------------------------------------------- */
+#define HS_HISTOGRAM_MAX_BINS 4096
 #define HS_DT_NONE 0
 #define HS_DT_LOG 1
 #define HS_DT_INV 2
@@ -897,6 +905,28 @@ int hs_depth_target(const float* in, int64_t in_stride_b, int64_t in_stride_p, f
 int64_t hs_depth_stats_partials(int64_t n);
 int hs_depth_stats_update(const float* depth, int64_t n, int transform, int use_masking, int64_t* partial, int64_t* state, void* stream);
 int hs_depth_stats_merge(const int64_t* states, int count, int64_t* state, void* stream);
+int hs_histogram_update(const float* depth, int64_t n, int transform, int use_masking, const double* edges, int bins, int64_t* counts,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Order statistics of rows (heal_swin_amd/order_stats.py): MeanSTDMedian's torch.median (evaluation/custom_metrics.py) without
+ * the sort.
+ *   hs_select_rows      out[r] = the k-th smallest (0-based) of x[r * row_stride .. r * row_stride + n), r < rows (<= 65535),
+ *                       0 <= k < n < 2^31, row_stride >= n, in torch.sort's order: -inf < finite < +inf < NaN, every NaN
+ *                       (either sign, any payload) last, -0.0 and +0.0 equal (either may be returned).  nan_propagates: a row
+ *                       that holds a NaN gives NaN (torch.median's rule; torch.kthvalue's is nan_propagates = 0).  x [dev] f32,
+ *                       4-byte aligned: a scalar head and tail around the 16-byte body of every row.  Radix select, four 8-bit
+ *                       digits from the top, on the order-preserving key (NaN -> 0xFFFFFFFF, else bits ^ (sign ? 0xFFFFFFFF :
+ *                       0x80000000)): `splits` workgroups per row (0: chosen from rows and n) count the digit of the elements
+ *                       that match the prefix and add their bins into workspace with integer atomics; every workgroup of the
+ *                       next pass finds prefix and rank from those bins itself.  Four pass launches and one that writes out;
+ *                       the result is bit-identical for every `splits` and arrival order.  workspace [dev]
+ *                       hs_select_rows_workspace(rows) bytes, zeroed in the call on `stream`.  Never waits for the device; can
+ *                       be captured in a graph (a replay selects from the current contents of x).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t hs_select_rows_workspace(int rows);
+int hs_select_rows(const float* x, int rows, int64_t n, int64_t row_stride, int64_t k, int nan_propagates, int splits, void* workspace,
+                   float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Decoder tail: LayerNorm(C) of FinalPatchExpand_X4 + the 1x1 class head in one pass, so that the normalised

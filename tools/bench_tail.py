@@ -18,7 +18,7 @@ and --grad train|valid one of the two (one form and one mode per process under r
 1 048 576 tokens x 96 -> 4 194 304 pixel rows), f_out 1 and 2 (--f-out), with and without a gradient, the forms alternating:
    loss        ops.expand_ln_head_depth       (hs_expand_ln_head_depth_fwd: the loss alone; exists on the parent commit)
    composed    ops.expand_ln_head + losses.depth_step_from_rows' parts: the rows written, hs_depth_loss_fwd, hs_depth_target twice,
-               hs_depth_metrics (+ torch.median with the log variance): the parent commit's validation route
+               hs_depth_metrics (+ the hs_select_rows median with the log variance): the validation route without the fused step
    step        ops.expand_ln_head_depth_step  (hs_expand_ln_head_depth_step_fwd + the merge of the records), predictions returned
    step_nop    the same without the predictions
 Each line gives min / median / max over the rounds and the HBM bytes the form writes."""
