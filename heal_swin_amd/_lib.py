@@ -65,6 +65,12 @@ def adam_groups(records):
     return arr
 
 
+class FisheyeCamera(ctypes.Structure):
+    """`hs_fisheye_camera` (include/healswin.h): the polynomial fisheye model hs_hp_rotated_coords projects with."""
+    _fields_ = [("k", ctypes.c_double * 8), ("cx_offset", ctypes.c_double), ("cy_offset", ctypes.c_double), ("aspect_ratio", ctypes.c_double),
+                ("poly_order", c_int), ("width", c_int), ("height", c_int)]
+
+
 # name -> argtypes; every function returns int status unless listed in _OTHER_RESTYPE
 _SIGNATURES = {
     "hs_nest2ring": [c_int, c_ptr, c_ptr, c_i64],
@@ -117,6 +123,9 @@ _SIGNATURES = {
     "hs_ln_head_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr],
     "hs_sample_bilinear_u8": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_sample_mask_u8": [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr],
+    "hs_hp_rotated_coords": [c_int, c_i64, c_i64, ctypes.POINTER(FisheyeCamera), c_ptr, c_int, c_ptr, c_ptr, c_ptr],
+    "hs_sample_bilinear_u8_per_sample": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "hs_sample_mask_u8_per_sample": [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr],
     "hs_hp_interp_weights_nest": [c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_backproject_labels": [c_ptr, c_int, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr],
     "hs_backproject_image": [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
@@ -133,6 +142,8 @@ _SIGNATURES = {
                                 c_int, ctypes.c_double, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     "hs_sample_bilinear_u8_f32": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_sample_nearest_f32": [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_float, c_ptr, c_ptr],
+    "hs_sample_bilinear_u8_f32_per_sample": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
+    "hs_sample_nearest_f32_per_sample": [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_float, c_ptr, c_ptr],
     "hs_depth_target": [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_float, c_float, c_ptr],
     "hs_depth_stats_update": [c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr],
     "hs_depth_stats_merge": [c_ptr, c_int, c_ptr, c_ptr],

@@ -4,6 +4,8 @@
 //     hp_mask = sample_mask(mask, v, u, s2_bkgd_class)           (:76-80)
 // for every image of a camera, against ONE coordinate table (u, v) per calibration (the reference caches it, :141-183).
 // One thread per HEALPix pixel: the coordinate arithmetic is done once and applied to all batch x channel planes.
+// hs_sample_*_per_sample: the same kernels against one coordinate row PER SAMPLE (rx, ry [batch, n], the output of
+// hs_hp_rotated_coords, projection_aug.hip): one thread per (sample, pixel), applied to that sample's planes.
 //
 // Bit-exact by construction: float64 throughout, the reference's operation order
 //     fx1 = (i1 - r) s00 + (r - i0) s10;  fx2 = (i1 - r) s01 + (r - i0) s11;  out = (j1 - q) fx1 + (q - j0) fx2
@@ -27,11 +29,18 @@ __device__ __forceinline__ Corner corner(double fx, double fy, int h, int w) {
     return {ok, ok ? (int64_t)fx * w + (int64_t)fy : 0};
 }
 
+// PER_SAMPLE: the grid's y index is the sample, which reads row y of rx, ry [batch, n] and owns its `planes` (= channels) image
+// planes; otherwise one (rx, ry) [n] serves all `planes` (= batch x channels).  The arithmetic below is the same code.
+template <bool PER_SAMPLE>
 __global__ void __launch_bounds__(256) sample_bilinear_u8_kernel(const uint8_t* __restrict__ img, int planes, int h, int w,
                                                                  const double* __restrict__ rx, const double* __restrict__ ry,
                                                                  int64_t n, uint8_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (PER_SAMPLE) {
+        const int64_t b = blockIdx.y;
+        rx += b * n, ry += b * n, img += b * planes * ((int64_t)h * w), out += b * planes * n;
+    }
     const double x = rx[i], y = ry[i];
     const double x0 = floor(x), x1 = ceil(x), y0 = floor(y), y1 = ceil(y);
     const Corner c00 = corner(x0, y0, h, w), c10 = corner(x1, y0, h, w), c01 = corner(x0, y1, h, w), c11 = corner(x1, y1, h, w);
@@ -49,14 +58,50 @@ __global__ void __launch_bounds__(256) sample_bilinear_u8_kernel(const uint8_t* 
     }
 }
 
+template <bool PER_SAMPLE>
 __global__ void __launch_bounds__(256) sample_mask_u8_kernel(const uint8_t* __restrict__ mask, int planes, int h, int w,
                                                              const double* __restrict__ rx, const double* __restrict__ ry,
                                                              int64_t n, int background, uint8_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (PER_SAMPLE) {
+        const int64_t b = blockIdx.y;
+        rx += b * n, ry += b * n, mask += b * planes * ((int64_t)h * w), out += b * planes * n;
+    }
     const Corner c = corner(rint(rx[i]), rint(ry[i]), h, w);  // np.around: round half to even
     const int64_t plane = (int64_t)h * w;
     for (int p = 0; p < planes; ++p) out[p * n + i] = c.ok ? mask[p * plane + c.off] : (uint8_t)background;
+}
+
+// one argument check and one launch for the shared-table and the per-sample entry points
+template <bool PER_SAMPLE>
+int sample_bilinear_u8(const void* img, int batch, int channels, int height, int width, const double* rx, const double* ry, int64_t n,
+                       void* out, void* stream) {
+    HS_CHECK_ARG(batch > 0 && channels > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
+    HS_CHECK_ARG((int64_t)batch * channels < (1 << 20), "too many image planes");
+    HS_CHECK_ARG(!PER_SAMPLE || batch <= 65535, "per-sample tables: batch <= 65535");
+    if (n == 0) return HS_OK;
+    HS_CHECK_ARG(img && rx && ry && out, "null pointer");
+    hipLaunchKernelGGL(sample_bilinear_u8_kernel<PER_SAMPLE>, dim3((unsigned)((n + 255) / 256), PER_SAMPLE ? (unsigned)batch : 1u), dim3(256),
+                       0, (hipStream_t)stream, (const uint8_t*)img, PER_SAMPLE ? channels : batch * channels, height, width, rx, ry, n,
+                       (uint8_t*)out);
+    HS_LAUNCH_CHECK("sample_bilinear_u8");
+    return HS_OK;
+}
+
+template <bool PER_SAMPLE>
+int sample_mask_u8(const void* mask, int batch, int height, int width, const double* rx, const double* ry, int64_t n, int background,
+                   void* out, void* stream) {
+    HS_CHECK_ARG(batch > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
+    HS_CHECK_ARG(background >= 0 && background <= 255, "background class must fit uint8");
+    HS_CHECK_ARG(!PER_SAMPLE || batch <= 65535, "per-sample tables: batch <= 65535");
+    if (n == 0) return HS_OK;
+    HS_CHECK_ARG(mask && rx && ry && out, "null pointer");
+    hipLaunchKernelGGL(sample_mask_u8_kernel<PER_SAMPLE>, dim3((unsigned)((n + 255) / 256), PER_SAMPLE ? (unsigned)batch : 1u), dim3(256), 0,
+                       (hipStream_t)stream, (const uint8_t*)mask, PER_SAMPLE ? 1 : batch, height, width, rx, ry, n, background,
+                       (uint8_t*)out);
+    HS_LAUNCH_CHECK("sample_mask_u8");
+    return HS_OK;
 }
 
 }  // namespace
@@ -65,26 +110,22 @@ extern "C" {
 
 int hs_sample_bilinear_u8(const void* img, int batch, int channels, int height, int width, const double* rx, const double* ry,
                           int64_t n, void* out, void* stream) {
-    HS_CHECK_ARG(batch > 0 && channels > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
-    HS_CHECK_ARG((int64_t)batch * channels < (1 << 20), "too many image planes");
-    if (n == 0) return HS_OK;
-    HS_CHECK_ARG(img && rx && ry && out, "null pointer");
-    hipLaunchKernelGGL(sample_bilinear_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint8_t*)img, batch * channels, height, width, rx, ry, n, (uint8_t*)out);
-    HS_LAUNCH_CHECK("sample_bilinear_u8");
-    return HS_OK;
+    return sample_bilinear_u8<false>(img, batch, channels, height, width, rx, ry, n, out, stream);
+}
+
+int hs_sample_bilinear_u8_per_sample(const void* img, int batch, int channels, int height, int width, const double* rx,
+                                     const double* ry, int64_t n, void* out, void* stream) {
+    return sample_bilinear_u8<true>(img, batch, channels, height, width, rx, ry, n, out, stream);
 }
 
 int hs_sample_mask_u8(const void* mask, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
                       int background, void* out, void* stream) {
-    HS_CHECK_ARG(batch > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
-    HS_CHECK_ARG(background >= 0 && background <= 255, "background class must fit uint8");
-    if (n == 0) return HS_OK;
-    HS_CHECK_ARG(mask && rx && ry && out, "null pointer");
-    hipLaunchKernelGGL(sample_mask_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint8_t*)mask, batch, height, width, rx, ry, n, background, (uint8_t*)out);
-    HS_LAUNCH_CHECK("sample_mask_u8");
-    return HS_OK;
+    return sample_mask_u8<false>(mask, batch, height, width, rx, ry, n, background, out, stream);
+}
+
+int hs_sample_mask_u8_per_sample(const void* mask, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
+                                 int background, void* out, void* stream) {
+    return sample_mask_u8<true>(mask, batch, height, width, rx, ry, n, background, out, stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,122 @@
+// Per-sample rotation augmentation of the fisheye -> HEALPix projection: the coordinate table of projection.py, recomputed on
+// the device for every sample of a batch under its own 3x3 matrix.
+//     g   = centre of nested pixel p as a unit vector            (the steps of hs_pix2ang_nest, healpix_tables.cpp)
+//     d   = M_b g                                                (M_b row-major, read from device memory: a captured step
+//                                                                 changes the rotations between replays)
+//     r   = hypot(d.x, d.y), theta = atan2(r, d.z), cos phi = d.x / r, sin phi = d.y / r  (1, 0 where r == 0)
+//     rho = sum_i k_i theta^i                                    (project_s2_points_to_img, the WoodScape polynomial model)
+//     u   = rho cos phi + cx_offset + width / 2 - 1/2,  v = rho sin phi aspect_ratio + cy_offset + height / 2 - 1/2
+// theta and phi do not depend on the length of d, so any real matrix is accepted.  The rotation acts on the sampling
+// coordinates: a rotated sample costs one interpolation (hs_sample_*_per_sample against this kernel's output), not two.
+//
+// float64 throughout, no FMA contraction, the reference's expression order for rho, u and v.  The result agrees with the host
+// table (arccos / cos phi / sin phi of the angles) to rounding, not bit for bit: the exact path is the resident table.
+// One thread per (sample, pixel): bound by float64 transcendental throughput (sincos, hypot, atan2, two divisions), 16 B out.
+#include "hs_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kThreads = 256;
+
+__device__ __forceinline__ uint32_t compact_bits(uint64_t v) {  // keeps the even bits
+    v &= 0x5555555555555555ull;
+    v = (v | (v >> 1)) & 0x3333333333333333ull;
+    v = (v | (v >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    v = (v | (v >> 4)) & 0x00FF00FF00FF00FFull;
+    v = (v | (v >> 8)) & 0x0000FFFF0000FFFFull;
+    v = (v | (v >> 16)) & 0x00000000FFFFFFFFull;
+    return (uint32_t)v;
+}
+
+struct Vec3 {
+    double x, y, z;
+};
+
+// centre of nested pixel p: hs_pix2ang_nest's (face, ix, iy) -> ring jr -> zone, with the vector built from z and sin(theta)
+// directly (caps: sqrt(tmp (2 - tmp)), belt: sqrt((1 - z)(1 + z))) instead of through acos
+__device__ __forceinline__ Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p) {
+    const int face = (int)(p >> log2_npface);
+    const uint64_t in_face = (uint64_t)(p & (((int64_t)1 << log2_npface) - 1));
+    const int64_t ix = compact_bits(in_face), iy = compact_bits(in_face >> 1);
+    // ring index (units of nside) of the base pixel's northern corner, and its longitude offset (kJrll, kJpll of the host tables)
+    const int jrll = 2 + (face >> 2), jpll = (face >> 2) == 1 ? 2 * (face & 3) : 2 * (face & 3) + 1;
+    const int64_t jr = jrll * nside - ix - iy - 1;
+    const double fact2 = 4.0 / (double)(12 * nside * nside), fact1 = (double)(2 * nside) * fact2, halfpi = 0.5 * M_PI;
+    int64_t nr;
+    double z, sth;
+    if (jr < nside) {  // north polar cap
+        nr = jr;
+        const double tmp = (double)(nr * nr) * fact2;
+        z = 1.0 - tmp;
+        sth = sqrt(tmp * (2.0 - tmp));
+    } else if (jr > 3 * nside) {  // south polar cap
+        nr = 4 * nside - jr;
+        const double tmp = (double)(nr * nr) * fact2;
+        z = tmp - 1.0;
+        sth = sqrt(tmp * (2.0 - tmp));
+    } else {  // equatorial belt
+        nr = nside;
+        z = (double)(2 * nside - jr) * fact1;
+        sth = sqrt((1.0 - z) * (1.0 + z));
+    }
+    int64_t t = jpll * nr + ix - iy;
+    if (t < 0) t += 8 * nr;
+    const double phi = nr == nside ? 0.75 * halfpi * (double)t * fact1 : (0.5 * halfpi * (double)t) / (double)nr;
+    double s, c;
+    sincos(phi, &s, &c);
+    return {sth * c, sth * s, z};
+}
+
+// grid (pixel blocks, samples)
+__global__ void __launch_bounds__(kThreads) hp_rotated_coords_kernel(int64_t nside, int log2_npface, int64_t first_pix, int64_t count,
+                                                                     hs_fisheye_camera cam, const double* __restrict__ rot,
+                                                                     double* __restrict__ u, double* __restrict__ v) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    const int64_t b = blockIdx.y;
+    const double* m = rot + 9 * b;  // uniform over the workgroup
+    const Vec3 g = pixel_centre(nside, log2_npface, first_pix + i);
+    const double dx = m[0] * g.x + m[1] * g.y + m[2] * g.z;
+    const double dy = m[3] * g.x + m[4] * g.y + m[5] * g.z;
+    const double dz = m[6] * g.x + m[7] * g.y + m[8] * g.z;
+    const double r = hypot(dx, dy);
+    const double theta = atan2(r, dz);
+    const double cphi = r == 0.0 ? 1.0 : dx / r, sphi = r == 0.0 ? 0.0 : dy / r;
+    double rho = 0.0, tp = 1.0;
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        tp = tp * theta;
+        if (o < cam.poly_order) rho = rho + cam.k[o] * tp;
+    }
+    u[b * count + i] = rho * cphi + cam.cx_offset + (double)cam.width / 2.0 - 0.5;
+    v[b * count + i] = rho * sphi * cam.aspect_ratio + cam.cy_offset + (double)cam.height / 2.0 - 0.5;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hs_hp_rotated_coords(int nside, int64_t first_pix, int64_t count, const hs_fisheye_camera* cam, const double* rot, int batch,
+                         double* u, double* v, void* stream) {
+    HS_CHECK_ARG(nside >= 1 && hs::is_pow2(nside), "nside must be a power of two, got %d", nside);
+    HS_CHECK_ARG(nside <= (1 << 29), "nside %d above HEALPix's limit 2^29", nside);
+    const int64_t npix = 12 * (int64_t)nside * nside;
+    HS_CHECK_ARG(first_pix >= 0 && count >= 0 && first_pix <= npix && count <= npix - first_pix, "pixel range outside [0, 12 nside^2)");
+    HS_CHECK_ARG(count <= (int64_t)INT32_MAX * kThreads, "too many pixels for one launch");
+    HS_CHECK_ARG(batch > 0 && batch <= 65535, "batch must be in [1, 65535], got %d", batch);
+    HS_CHECK_ARG(cam, "null pointer");
+    HS_CHECK_ARG(cam->poly_order >= 1 && cam->poly_order <= 8, "poly_order must be in [1, 8], got %d", cam->poly_order);
+    HS_CHECK_ARG(cam->width > 0 && cam->height > 0, "image size must be positive");
+    if (count == 0) return HS_OK;
+    HS_CHECK_ARG(rot && u && v, "null pointer");
+    int log2_npface = 0;
+    while (((int64_t)1 << log2_npface) < (int64_t)nside * nside) ++log2_npface;
+    hipLaunchKernelGGL(hp_rotated_coords_kernel, dim3((unsigned)((count + kThreads - 1) / kThreads), (unsigned)batch), dim3(kThreads), 0,
+                       (hipStream_t)stream, (int64_t)nside, log2_npface, first_pix, count, *cam, rot, u, v);
+    HS_LAUNCH_CHECK("hp_rotated_coords");
+    return HS_OK;
+}
+
+}  // extern "C"

@@ -32,7 +32,8 @@ import torch
 from ._lib import (HS_DEPTH_STATS_WORDS, HS_DT_1000_BKG, HS_DT_AFFINE, HS_DT_INV, HS_DT_INVERSE, HS_DT_LOG, HS_DT_NONE,
                    HS_DT_ZERO_BKG, HS_HISTOGRAM_MAX_BINS, check, lib, ptr, stream_ptr)
 from .evaluation import _device
-from .projection import _coords, _device_u8, hp_grid, project_s2_points_to_img
+from .projection import (_coords, _device_u8, _per_sample_count, _pole_rotation, _rotated_coords, camera_record, hp_grid,
+                         project_s2_points_to_img)
 
 IMG_KEY, MASK_KEY = "hp_img", "hp_mask"
 TRANSFORMS = {None: HS_DT_NONE, "None": HS_DT_NONE, "log": HS_DT_LOG, "inv": HS_DT_INV}
@@ -62,37 +63,51 @@ def _device_f32(t, ndim, what):
     return (t[None] if lead else t).contiguous(), bool(lead)
 
 
-def sample_bilinear_f32(img, rx, ry):
+def sample_bilinear_f32(img, rx, ry, per_sample=False):
     """`sample_bilinear(img, rx, ry).astype(np.float32)`: img uint8 [C, H, W] or [B, C, H, W] on the GPU, rx along H, ry along
-    W -> float32 [(B,) C, n]; NaN where a coordinate is not finite, 0 at integer coordinates (the reference's floor / ceil)."""
+    W -> float32 [(B,) C, n]; NaN where a coordinate is not finite, 0 at integer coordinates (the reference's floor / ceil).
+    per_sample=False: one coordinate table for the whole batch (rx, ry of any shape are flattened).  per_sample=True: rx, ry
+    are [B, n] and sample b reads row b (`hs_sample_bilinear_u8_f32_per_sample`, the same kernel and arithmetic)."""
+    n = _per_sample_count(img, 4, rx, ry) if per_sample else None
     img, squeeze = _device_u8(img, 4, "img")
     rx, ry = _coords(rx, img.device), _coords(ry, img.device)
     if rx.shape != ry.shape:
         raise ValueError("rx and ry must have the same shape")
+    n = rx.numel() if n is None else n
     b, c, h, w = img.shape
-    out = torch.empty((b, c, rx.numel()), dtype=torch.float32, device=img.device)
-    check(lib.hs_sample_bilinear_u8_f32(ptr(img), b, c, h, w, ptr(rx), ptr(ry), rx.numel(), ptr(out), stream_ptr(img.device)),
-          "hs_sample_bilinear_u8_f32")
+    out = torch.empty((b, c, n), dtype=torch.float32, device=img.device)
+    fn = lib.hs_sample_bilinear_u8_f32_per_sample if per_sample else lib.hs_sample_bilinear_u8_f32
+    check(fn(ptr(img), b, c, h, w, ptr(rx), ptr(ry), n, ptr(out), stream_ptr(img.device)), "hs_sample_bilinear_u8_f32")
     return out[0] if squeeze else out
 
 
-def sample_depth(depth, rx, ry, background=0.0):
+def sample_depth(depth, rx, ry, background=0.0, per_sample=False):
     """`sample_mask(depth, rx, ry, background)`: depth float32 [H, W] or [B, H, W] on the GPU -> float32 [(B,) n], the nearest
-    pixel's value (round half to even), `background` outside the image."""
+    pixel's value (round half to even), `background` outside the image.  per_sample as in sample_bilinear_f32
+    (`hs_sample_nearest_f32_per_sample`)."""
+    n = _per_sample_count(depth, 3, rx, ry) if per_sample else None
     depth, squeeze = _device_f32(depth, 3, "depth")
     rx, ry = _coords(rx, depth.device), _coords(ry, depth.device)
     if rx.shape != ry.shape:
         raise ValueError("rx and ry must have the same shape")
+    n = rx.numel() if n is None else n
     b, h, w = depth.shape
-    out = torch.empty((b, rx.numel()), dtype=torch.float32, device=depth.device)
-    check(lib.hs_sample_nearest_f32(ptr(depth), b, h, w, ptr(rx), ptr(ry), rx.numel(), float(np.float32(background)), ptr(out),
-                                    stream_ptr(depth.device)), "hs_sample_nearest_f32")
+    out = torch.empty((b, n), dtype=torch.float32, device=depth.device)
+    fn = lib.hs_sample_nearest_f32_per_sample if per_sample else lib.hs_sample_nearest_f32
+    check(fn(ptr(depth), b, h, w, ptr(rx), ptr(ry), n, float(np.float32(background)), ptr(out), stream_ptr(depth.device)),
+          "hs_sample_nearest_f32")
     return out[0] if squeeze else out
 
 
 class HPDepthProjector:
     """project_depth_dataset_hp for the frames of one camera: `proj(imgs, depths)` -> (hp_img float32 [B, 3, Npix], hp_mask
-    float32 [B, Npix]) on the GPU.  The coordinate table is built once on the host and stays on the device."""
+    float32 [B, Npix]) on the GPU.  The coordinate table is built once on the host and stays on the device.
+
+    `proj(imgs, depths, rotations=A)` with A [B, 3, 3] (projection.random_rotations) is the augmented projection: one coordinate
+    launch (projection.rotated_coords) plus the per-sample sampling launches; depth is still sampled nearest, and samples outside
+    the image are 0 in the frame and `s2_bkgd_class` in the depth as without rotations.  `rotations=None` is the exact path: the
+    resident table, the reference's bytes.  Identity rotations go through the device arithmetic and agree with it to coordinate
+    rounding only (about 1e-12 px), not bit for bit."""
 
     def __init__(self, cal_info, nside, base_pix=8, rotate_pole=False, s2_bkgd_class=0, used_size=None, device="cuda"):
         self.nside, self.base_pix = int(nside), int(base_pix)
@@ -101,16 +116,23 @@ class HPDepthProjector:
         u, v = project_depth_s2_points_to_img(theta, phi, cal_info, rotate_pole, used_size)
         self.device = torch.device(device)
         self.u, self.v = _coords(u, self.device), _coords(v, self.device)
+        self._cam = camera_record(cal_info, used_size)
+        self._pole = torch.from_numpy(_pole_rotation(cal_info)).to(self.device) if rotate_pole else None
 
     @property
     def npix(self):
         return self.u.numel()
 
-    def proj(self, imgs, depths=None):
-        hp_img = sample_bilinear_f32(imgs, self.v, self.u)
+    def proj(self, imgs, depths=None, rotations=None):
+        if rotations is None:
+            u, v, per_sample = self.u, self.v, False
+        else:
+            u, v = _rotated_coords(self.nside, self.base_pix, self._cam, rotations, self._pole, self.device)
+            per_sample = True
+        hp_img = sample_bilinear_f32(imgs, v, u, per_sample)
         if depths is None:
             return hp_img
-        return hp_img, sample_depth(depths, self.v, self.u, self.s2_bkgd_class)
+        return hp_img, sample_depth(depths, v, u, self.s2_bkgd_class, per_sample)
 
     __call__ = proj
 

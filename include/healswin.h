@@ -723,6 +723,41 @@ int hs_sample_mask_u8(const void* mask, int batch, int height, int width, const 
                       int background, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-sample rotation augmentation of the projection (heal_swin_amd/projection.py: random_rotations, rotated_coords,
+ * HPProjector(..., rotations=)).  The reference projects once, offline, and has no augmentation; here the sphere is re-sampled
+ * differently for every sample of a batch by rotating the sampling coordinates, so a rotated sample costs one interpolation.
+ *   hs_hp_rotated_coords  u, v [dev] f64[batch, count]: image coordinates of the nested pixels first_pix .. first_pix + count - 1
+ *                       for each of `batch` samples.  Per (sample b, pixel p), in float64 without FMA contraction:
+ *                         g = centre of p as a unit vector (the steps of hs_pix2ang_nest; z and sin theta formed directly),
+ *                         d = M_b g, M_b = rot[9 b .. 9 b + 8] row-major ([dev]: a captured step may overwrite the matrices
+ *                         between replays); any real matrix is accepted, the angles do not depend on |d|,
+ *                         r = hypot(d.x, d.y), theta = atan2(r, d.z), cos phi = d.x / r, sin phi = d.y / r (1, 0 where r == 0),
+ *                         rho = sum_{i = 1 .. poly_order} k[i - 1] theta^i,
+ *                         u = rho cos phi + cx_offset + width / 2 - 1/2, v = rho sin phi aspect_ratio + cy_offset + height / 2 - 1/2
+ *                       (project_s2_points_to_img, data/segmentation/project_on_s2.py:141-183).  Convention: output pixel p shows
+ *                       the camera-frame direction M_b g_p, i.e. the map shows the scene rotated by M_b^-1.  With the identity
+ *                       the result equals the host table of projection.py to rounding (about 1e-12 px), not bit for bit.
+ *                       cam [host] is read during the call and travels by value.  HS_ERR_INVALID_ARG before any launch: nside
+ *                       no power of two, [first_pix, first_pix + count) outside [0, 12 nside^2), batch outside 1 .. 65535,
+ *                       poly_order outside 1 .. 8, width or height <= 0, null pointer.  count == 0 returns HS_OK.
+ *   hs_sample_*_per_sample  hs_sample_bilinear_u8 / hs_sample_mask_u8 (and, below, hs_sample_bilinear_u8_f32 /
+ *                       hs_sample_nearest_f32) with one coordinate row per sample: rx, ry [dev] f64[batch, n], sample b reads row
+ *                       b (batch <= 65535).  Same argument lists, same kernels and arithmetic: with every row equal, the result
+ *                       is the shared-table entry point's bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hs_fisheye_camera {
+    double k[8];                                /* rho = sum k[i - 1] theta^i, i = 1 .. poly_order */
+    double cx_offset, cy_offset, aspect_ratio;
+    int poly_order, width, height;              /* 1 <= poly_order <= 8 (WoodScape: 4); the size of the image sampled */
+} hs_fisheye_camera;
+int hs_hp_rotated_coords(int nside, int64_t first_pix, int64_t count, const hs_fisheye_camera* cam, const double* rot, int batch,
+                         double* u, double* v, void* stream);
+int hs_sample_bilinear_u8_per_sample(const void* img, int batch, int channels, int height, int width, const double* rx,
+                                     const double* ry, int64_t n, void* out, void* stream);
+int hs_sample_mask_u8_per_sample(const void* mask, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
+                                 int background, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation: HEALPix predictions scored and back-projected onto the fisheye image plane (heal_swin_amd/evaluation.py).
  * The tables of a calibration (nearest pixel, four interpolation pixels and weights per image-plane pixel) are built once on
  * the host; the per-batch work is the three gathers below.
@@ -900,6 +935,11 @@ int hs_sample_bilinear_u8_f32(const void* img, int batch, int channels, int heig
                               int64_t n, float* out, void* stream);
 int hs_sample_nearest_f32(const float* src, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
                           float background, float* out, void* stream);
+/* rx, ry [dev] f64[batch, n], one row per sample (see hs_hp_rotated_coords above) */
+int hs_sample_bilinear_u8_f32_per_sample(const void* img, int batch, int channels, int height, int width, const double* rx,
+                                         const double* ry, int64_t n, float* out, void* stream);
+int hs_sample_nearest_f32_per_sample(const float* src, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
+                                     float background, float* out, void* stream);
 int hs_depth_target(const float* in, int64_t in_stride_b, int64_t in_stride_p, float* out, int64_t out_stride_b, int64_t out_stride_p,
                     int64_t batch, int64_t n, int flags, int transform, float shift, float scale, void* stream);
 int64_t hs_depth_stats_partials(int64_t n);
