@@ -203,6 +203,11 @@ _SIGNATURES = {
     "hs_depth_loss_bwd": [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_float, c_int, c_ptr],
     "hs_gemm_nt": [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int,
                    ctypes.c_float, ctypes.c_uint64, c_int, c_ptr],
+    "hs_lib_gemm_supported": [],
+    "hs_lib_gemm_set_supported": [c_int],
+    "hs_lib_gemm_nt": [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr],
+    "hs_lib_gemm_pick": [c_i64, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.c_char_p, c_int],
+    "hs_lib_gemm_set_pick": [c_i64, c_int, c_int, c_int, c_int],
     "hs_gemm_nt_set_tile": [c_int],
     "hs_gemm_nt_tile_variant": [c_i64, c_int, c_int, c_int, c_int],
     "hs_set_reserved_cus": [c_int],

@@ -65,7 +65,9 @@ class GraphedTrainStep:
 
     def _warm_up_and_capture(self, warmup):
         # warm-up on a side stream (PyTorch's capture protocol): lazy initialisations -- kernel attributes, the bf16 weight
-        # shadows, optimizer state, the allocator's blocks -- happen here, not inside the capture
+        # shadows, optimizer state, the allocator's blocks -- happen here, not inside the capture.  The capture then records on the
+        # SAME stream: what the library keeps per stream (hs_lib_gemm_nt's hipBLASLt workspace) exists by then and is not
+        # allocated, which a capture forbids.
         side = torch.cuda.Stream(device=self.inputs.device)
         side.wait_stream(torch.cuda.current_stream(self.inputs.device))
         with torch.cuda.stream(side):
@@ -78,15 +80,15 @@ class GraphedTrainStep:
 
         self.graph = torch.cuda.CUDAGraph()
         if not self._dp:
-            with torch.cuda.graph(self.graph):
+            with torch.cuda.graph(self.graph, stream=side):
                 self.loss = self._eager()
             return
         # data parallel: [graph 1: zero_grad, forward, loss, backward into the local buckets] -> eager exchange -> [graph 2: optimizer]
         self.graph_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with torch.cuda.graph(self.graph, stream=side):
             self.loss = self._fwd_bwd_local()
         self.grad_sink.finish()  # (an exchange between the two captures keeps every rank's collective sequence aligned with the replays')
-        with torch.cuda.graph(self.graph_opt):
+        with torch.cuda.graph(self.graph_opt, stream=side):
             self._opt_step()
 
     def _eager(self):

@@ -395,6 +395,8 @@ class SwinTransformerBlock(nn.Module):
             C = self.dim
             proj_own = ops.own_gemm_ok(_lib.HS_EPI_BIAS, C, C, x.dtype, m=x.numel() // C)
             fc2_own = ops.own_gemm_ok(_lib.HS_EPI_BIAS, C, self.mlp.fc1.weight.shape[0], x.dtype, m=x.numel() // C)
+            # ... and where fc2 runs in the library (long K: stages 1-3), on the library product's C operand (ops.LIB_RESID)
+            fc2_res = fc2_own or ops.lib_resid_ok(C, self.mlp.fc1.weight.shape[0], x.dtype)
             if pending is None and self.attn.trainable_fused(x, self.window_size):
                 # norm1 -> qkv -> attention -> proj -> residual add in ONE launch that also writes what the backward reads
                 idx, roll, labels = self._shift_args(x)
@@ -407,10 +409,10 @@ class SwinTransformerBlock(nn.Module):
                     if x2 is not None:
                         return x2, None, None
                     n2, x1 = ops.layer_norm_passthrough(x1, self.norm2.weight, self.norm2.bias)
-                if fc2_own:
+                if fc2_res:
                     return self.mlp(n2, apply_out_drop=False, residual=x1), None, None
                 return x1, (self.mlp(n2, apply_out_drop=False), None, 0.0), None
-            if proj_own or fc2_own:
+            if proj_own or fc2_res:
                 if pending is None:
                     n1, xs = ops.layer_norm_passthrough(x, self.norm1.weight, self.norm1.bias)
                 else:
@@ -424,7 +426,7 @@ class SwinTransformerBlock(nn.Module):
                     n2, x1 = ops.layer_norm_passthrough(x1, self.norm2.weight, self.norm2.bias)
                 else:
                     x1, n2 = ops.add_layer_norm(xs, self._attention_branch(n1, apply_proj_drop=False), self.norm2.weight, self.norm2.bias)
-                if fc2_own:
+                if fc2_res:
                     return self.mlp(n2, apply_out_drop=False, residual=x1), None, None
                 return x1, (self.mlp(n2, apply_out_drop=False), None, 0.0), None
         if pending is None:  # x feeds norm1 AND the residual add below: the alias keeps the two gradients in one kernel

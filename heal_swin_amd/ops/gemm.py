@@ -298,6 +298,60 @@ def _lib_linear(x2, w, b):
         return torch.nn.functional.linear(x2, w, b)
 
 
+# The residual add in the LIBRARY product's epilogue (hs_lib_gemm_nt: hipBLASLt's D = A W^T + bias + C with C != D), for the fc2 shapes
+# the library runs (K >= 1024: stages 1-3).  The norm1 behind it is then a plain LayerNorm (reads 1, writes 1) instead of the fused
+# add + LayerNorm (reads 2, writes 2), as at stages 0-1 with hs_gemm_nt's EPI_RESID.  "0" / False: the add stays deferred into the norm.
+LIB_RESID = os.environ.get("HS_LIB_RESID", "1") != "0"
+LIB_GEMM_CALLS = [0]  # hs_lib_gemm_nt launches so far (tests count them; profiles use the `lib fwd+res` tag)
+
+
+def lib_resid_ok(n, k, dtype, stochastic=False, comp=False):
+    """Whether a residual add may ride on the library product [*, k] x [n, k]^T (`_lib_linear_resid`): bf16, hipBLASLt reachable,
+    nothing stochastic on the branch, no compensated residual stream -- the restrictions of the hs_gemm_nt form of the same add."""
+    return bool(LIB_RESID and dtype == torch.bfloat16 and not stochastic and not comp and n % 8 == 0 and n >= 16 and k % 8 == 0 and
+                lib.hs_lib_gemm_supported())
+
+
+def lib_gemm_nt(a2, w, bias, res2):
+    """a2 [m, k] @ w [n, k]^T + bias (+ res2 [m, n]) in one library launch (`hs_lib_gemm_nt`), bf16; None where the library has no
+    algorithm for the call (HS_ERR_UNSUPPORTED: e.g. a stream first met inside a capture and only workspace-hungry candidates)."""
+    a2, w, bias, res2 = _aligned(a2.contiguous()), _aligned(w.contiguous()), _aligned(bias), (None if res2 is None else _aligned(res2.contiguous()))
+    (m, k), n = a2.shape, w.shape[0]
+    assert a2.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and (res2 is None or (res2.dtype == torch.bfloat16 and res2.shape == (m, n)))
+    d = torch.empty((m, n), dtype=torch.bfloat16, device=a2.device)
+    bias_code = _lib.HS_BF16 if bias is None else _lib.dtype_code(bias.dtype)
+    with _timed(_lib_tag("fwd+res" if res2 is not None else "fwd", m, n, k), a2.device, 2 * (m * k + (2 if res2 is not None else 1) * m * n), 2 * m * k * n):
+        st = lib.hs_lib_gemm_nt(ptr(a2), ptr(w), ptr(bias), bias_code, ptr(res2), ptr(d), m, n, k, stream_ptr(a2.device))
+    if st == 2:
+        return None
+    check(st, "hs_lib_gemm_nt")
+    LIB_GEMM_CALLS[0] += 1
+    return d
+
+
+def lib_gemm_pick(m, n, k, has_c=True):
+    """(position, solution index, text) of the algorithm hs_lib_gemm_nt chose for this shape class on the current device; position -1: none yet."""
+    import ctypes
+    idx, sol, name = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.create_string_buffer(128)
+    check(lib.hs_lib_gemm_pick(int(m), int(n), int(k), int(bool(has_c)), ctypes.byref(idx), ctypes.byref(sol), name, 128), "hs_lib_gemm_pick")
+    return idx.value, sol.value, name.value.decode()
+
+
+def lib_gemm_set_pick(m, n, k, has_c, index):
+    """Pin candidate `index` for the shape class instead of a first-call trial (-1: forget the class).  Data-parallel ranks pass rank 0's
+    `lib_gemm_pick` position so that every rank runs the same algorithm."""
+    check(lib.hs_lib_gemm_set_pick(int(m), int(n), int(k), int(bool(has_c)), int(index)), "hs_lib_gemm_set_pick")
+
+
+def _lib_linear_resid(x2, w, b, res2):
+    """x2 W^T + b + res2 with the add in the library product's epilogue, one rounding (bf16 only; fp32 and bf16x3 keep `_lib_linear`).
+    Where the library refuses the call, hs_gemm_nt's residual epilogue runs instead."""
+    y = lib_gemm_nt(x2, w, b, res2)
+    if y is None:
+        y = gemm_nt(x2, w, b, _lib.HS_EPI_RESID, aux=res2)[0]
+    return y
+
+
 def _lib_matmul(dy2, w, res=None):
     m, n = dy2.shape
     if isinstance(dy2, _Split):

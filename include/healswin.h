@@ -704,6 +704,35 @@ int hs_gemm_nt_set_tile(int variant);
 int hs_gemm_nt_tile_variant(int64_t m, int n, int k, int k2, int epilogue);
 
 /* ------------------------------------------------------------------------------------------------
+ * The library GEMM (hipBLASLt) in its full product form, for the Linear products the library runs faster than hs_gemm_nt
+ * (long reductions: Mlp.fc2, models_torch/swin_hp_transformer.py:42, with the block's residual add :338 behind it):
+ *     d[m, n] = sum_k a[m, k] * w[n, k] + bias[n] + c[m, n]            fp32 accumulation, one rounding to bf16
+ *   a [dev] bf16 [m, k], w [dev] bf16 [n, k] (nn.Linear layout), c [dev] bf16 [m, n] or NULL (the plain product), d [dev] bf16 [m, n];
+ *   all row-major, contiguous and 16-byte aligned; n, k multiples of 8.  bias [dev] [n] of bias_dtype (HS_BF16 or HS_F32) or NULL.
+ *   d must not overlap a, w or c (HS_ERR_INVALID_ARG): c != d is the point -- the residual is read in the product's epilogue and
+ *   the sum is written once, where torch.addmm first copies c into d in a pass of its own.
+ * hipBLASLt is resolved at run time from the copy the process already holds (PyTorch's), else from the ROCm installation; there
+ * is no link dependency.  hs_lib_gemm_supported: 1 where that succeeded and a device is visible, else 0 -- hs_lib_gemm_nt then
+ * returns HS_ERR_UNSUPPORTED and the caller keeps the library product + separate add.  hs_lib_gemm_set_supported(0) turns the
+ * path off for the process (tests, A/B runs), (1) on again.
+ * State kept by the library: one hipBLASLt handle per device; one 32 MiB workspace per (device, stream), allocated by the first
+ * call on that stream outside a capture and kept; the descriptors of every shape met.  A call on a capturing stream allocates
+ * nothing and times nothing: it runs the remembered choice, and on a stream without a workspace a candidate that needs none.
+ * Algorithm choice: up to 8 candidates of hipblasLtMatmulAlgoGetHeuristic; the first call of a class (bit_length(m), n, k, c given)
+ * outside a capture runs each 1 + 3 times on the caller's stream and operands and remembers the fastest for the process and device.
+ * hs_lib_gemm_pick reports that choice for the current device: *index its position among the candidates (-1: none yet), *solution
+ * the library's solution index, name a text for records (any of the three may be NULL).  hs_lib_gemm_set_pick pins position
+ * `index` for the class instead of a trial (data-parallel ranks take rank 0's; a position past the candidates runs candidate 0);
+ * index -1 forgets the class.
+ * ---------------------------------------------------------------------------------------------- */
+int hs_lib_gemm_supported(void);
+int hs_lib_gemm_set_supported(int on);
+int hs_lib_gemm_nt(const void* a, const void* w, const void* bias, int bias_dtype, const void* c, void* d, int64_t m, int n, int k,
+                   void* stream);
+int hs_lib_gemm_pick(int64_t m, int n, int k, int has_c, int* index, int* solution, char* name, int name_len);
+int hs_lib_gemm_set_pick(int64_t m, int n, int k, int has_c, int index);
+
+/* ------------------------------------------------------------------------------------------------
  * Fisheye image -> HEALPix projection, the input pipeline in front of the model.  Replaces, per image, the
  * sampling of data/segmentation/project_on_s2.py:344-372; the coordinate table (u, v) of a calibration is built once on
  * the host (heal_swin_amd/projection.py, the reference's project_s2_points_to_img :141-183) and stays resident.
