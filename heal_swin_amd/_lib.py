@@ -126,6 +126,9 @@ _SIGNATURES = {
     "hs_hp_rotated_coords": [c_int, c_i64, c_i64, ctypes.POINTER(FisheyeCamera), c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     "hs_sample_bilinear_u8_per_sample": [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_sample_mask_u8_per_sample": [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr],
+    "hs_hp_rotated_interp": [c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
+    "hs_hp_rotated_interp_host": [c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
+    "hs_hp_rotate": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr],
     "hs_hp_interp_weights_nest": [c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_backproject_labels": [c_ptr, c_int, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr],
     "hs_backproject_image": [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],

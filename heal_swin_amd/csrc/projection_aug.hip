@@ -13,61 +13,16 @@
 // table (arccos / cos phi / sin phi of the angles) to rounding, not bit for bit: the exact path is the resident table.
 // One thread per (sample, pixel): bound by float64 transcendental throughput (sincos, hypot, atan2, two divisions), 16 B out.
 #include "hs_device.h"
+#include "hs_healpix_device.h"  // pixel_centre
 
 #pragma clang fp contract(off)
 
 namespace {
 
+using hs::healpix::pixel_centre;
+using hs::healpix::Vec3;
+
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ uint32_t compact_bits(uint64_t v) {  // keeps the even bits
-    v &= 0x5555555555555555ull;
-    v = (v | (v >> 1)) & 0x3333333333333333ull;
-    v = (v | (v >> 2)) & 0x0F0F0F0F0F0F0F0Full;
-    v = (v | (v >> 4)) & 0x00FF00FF00FF00FFull;
-    v = (v | (v >> 8)) & 0x0000FFFF0000FFFFull;
-    v = (v | (v >> 16)) & 0x00000000FFFFFFFFull;
-    return (uint32_t)v;
-}
-
-struct Vec3 {
-    double x, y, z;
-};
-
-// centre of nested pixel p: hs_pix2ang_nest's (face, ix, iy) -> ring jr -> zone, with the vector built from z and sin(theta)
-// directly (caps: sqrt(tmp (2 - tmp)), belt: sqrt((1 - z)(1 + z))) instead of through acos
-__device__ __forceinline__ Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p) {
-    const int face = (int)(p >> log2_npface);
-    const uint64_t in_face = (uint64_t)(p & (((int64_t)1 << log2_npface) - 1));
-    const int64_t ix = compact_bits(in_face), iy = compact_bits(in_face >> 1);
-    // ring index (units of nside) of the base pixel's northern corner, and its longitude offset (kJrll, kJpll of the host tables)
-    const int jrll = 2 + (face >> 2), jpll = (face >> 2) == 1 ? 2 * (face & 3) : 2 * (face & 3) + 1;
-    const int64_t jr = jrll * nside - ix - iy - 1;
-    const double fact2 = 4.0 / (double)(12 * nside * nside), fact1 = (double)(2 * nside) * fact2, halfpi = 0.5 * M_PI;
-    int64_t nr;
-    double z, sth;
-    if (jr < nside) {  // north polar cap
-        nr = jr;
-        const double tmp = (double)(nr * nr) * fact2;
-        z = 1.0 - tmp;
-        sth = sqrt(tmp * (2.0 - tmp));
-    } else if (jr > 3 * nside) {  // south polar cap
-        nr = 4 * nside - jr;
-        const double tmp = (double)(nr * nr) * fact2;
-        z = tmp - 1.0;
-        sth = sqrt(tmp * (2.0 - tmp));
-    } else {  // equatorial belt
-        nr = nside;
-        z = (double)(2 * nside - jr) * fact1;
-        sth = sqrt((1.0 - z) * (1.0 + z));
-    }
-    int64_t t = jpll * nr + ix - iy;
-    if (t < 0) t += 8 * nr;
-    const double phi = nr == nside ? 0.75 * halfpi * (double)t * fact1 : (0.5 * halfpi * (double)t) / (double)nr;
-    double s, c;
-    sincos(phi, &s, &c);
-    return {sth * c, sth * s, z};
-}
 
 // grid (pixel blocks, samples)
 __global__ void __launch_bounds__(kThreads) hp_rotated_coords_kernel(int64_t nside, int log2_npface, int64_t first_pix, int64_t count,

@@ -787,6 +787,54 @@ int hs_sample_mask_u8_per_sample(const void* mask, int batch, int height, int wi
                                  int background, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rotation of maps that already live on the sphere (heal_swin_amd/hp_rotate.py: rotated_interp, HPRotator): the augmentation
+ * of a dataset that was projected once, offline, as the reference's are (hp_img / hp_mask read from .npz files,
+ * data/segmentation/hp_datasets.py:92-98).  No frame is needed: output pixel p of sample b shows the SOURCE MAP at direction
+ * d = M_b g_p (the convention of hs_hp_rotated_coords), resampled with HEALPix's get_interpol evaluated per (sample, pixel).
+ *   hs_hp_rotated_interp  pix [dev] i32[batch, 4, count], wgt [dev] f64[batch, 4, count], nearest [dev] i32[batch, count] for the
+ *                       nested pixels first_pix .. first_pix + count - 1.  Per (sample b, pixel p), in float64 without FMA:
+ *                         g = centre of p as a unit vector (as in hs_hp_rotated_coords), d = M_b g, M_b = rot[9 b .. 9 b + 8]
+ *                         row-major ([dev]); any real matrix is accepted,
+ *                         theta = atan2(hypot(d.x, d.y), d.z) (0 for d = 0), phi = atan2(d.y, d.x) reduced to [0, 2 pi) with
+ *                         HEALPix's fmodulo,
+ *                         then the steps of hs_hp_interp_weights_nest (T_Healpix_Base::get_interpol, nested): ring_above, the
+ *                         two bracketing rings with weights linear in phi, then linear in theta; above the first and below the
+ *                         last ring the four polar pixels with a quarter of the missing ring's weight each; the same order of
+ *                         the four pixels,
+ *                         nearest = the pixel of largest weight, the first maximum in that order
+ *                         (data/segmentation/project_on_s2.py:83-105, evaluation.hp_nearest_pix_idcs).
+ *                       A non-finite component of d: pix -1, wgt 0, nearest -1.  Against hs_hp_interp_weights_nest at the same
+ *                       direction the pixels are equal and the weights agree to rounding, except where the direction lies
+ *                       within rounding of a ring or of a pixel boundary along a ring (there the other bracket is chosen; the
+ *                       interpolated value is continuous across it).
+ *   hs_hp_rotated_interp_host  the same inline function in a plain loop, every pointer [host]: the oracle of the two device
+ *                       entry points.
+ *   hs_hp_rotate        one launch, one thread per (sample, output pixel), the geometry evaluated once and applied to every plane
+ *                       given; no table is written.  npix = base_pix nside^2 pixels per map, base_pix in 1 .. 12; a source index
+ *                       idx is covered iff (uint64_t) idx < (uint64_t) npix, compared before every load.
+ *                         img [dev] u8[batch, channels, npix] -> img_out: v = ((w0 v0 + w1 v1) + w2 v2) + w3 v3 in float64 without
+ *                           FMA, an uncovered neighbour reads 0.0 (as hs_sample_bilinear_u8's neighbours outside the image);
+ *                           the byte is rint(v) (half to even) clamped to [0, 255] -- not the frame sampler's truncation, so that
+ *                           a direction on a pixel centre (top weight 1 - 1e-14) returns that pixel's byte,
+ *                         labels [dev] u8[batch, npix] -> labels_out: labels[b, nearest], `background` where uncovered (classes
+ *                           never mix),
+ *                         depth [dev] f32[batch, npix] -> depth_out: depth[b, nearest] copied bit for bit (inf and NaN included),
+ *                           depth_fill where uncovered.
+ *                       Each plane is given by both pointers or by neither (NULL).
+ * HS_ERR_INVALID_ARG before any launch: nside no power of two or above 8192 (the indices are int32; 2^29 is HEALPix's own
+ * limit), [first_pix, first_pix + count) outside [0, 12 nside^2), npix not in {1 .. 12} nside^2, batch outside 1 .. 65535,
+ * channels outside 1 .. 16 with img given, exactly one pointer of a pair, no plane, an output overlapping its input, background
+ * outside 0 .. 255, a null rot / pix / wgt / nearest.  count == 0 returns HS_OK.
+ * ---------------------------------------------------------------------------------------------- */
+int hs_hp_rotated_interp(int nside, int64_t first_pix, int64_t count, const double* rot, int batch, int32_t* pix, double* wgt,
+                         int32_t* nearest, void* stream);
+int hs_hp_rotated_interp_host(int nside, int64_t first_pix, int64_t count, const double* rot, int batch, int32_t* pix, double* wgt,
+                              int32_t* nearest);
+int hs_hp_rotate(int nside, int64_t npix, const double* rot, int batch, const uint8_t* img, int channels, uint8_t* img_out,
+                 const uint8_t* labels, uint8_t* labels_out, int background, const float* depth, float* depth_out, float depth_fill,
+                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation: HEALPix predictions scored and back-projected onto the fisheye image plane (heal_swin_amd/evaluation.py).
  * The tables of a calibration (nearest pixel, four interpolation pixels and weights per image-plane pixel) are built once on
  * the host; the per-batch work is the three gathers below.
