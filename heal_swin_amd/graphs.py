@@ -24,7 +24,7 @@ forward and backward of a step agree.  DropPath's per-sample factors come from t
 """
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 
 class GraphedTrainStep:
@@ -147,4 +147,8 @@ class GraphedTrainStep:
         invalidate = getattr(self.model, "invalidate_param_casts", None)
         if invalidate is not None:
             invalidate()
+        # ... and it ran no Python: neither note_forward nor FlatAdam.step() moved the weight epoch that the bf16x3 splits of fp32
+        # weights are keyed on (ops._weight_split).  Without this the SECOND evaluation after the capture is served the splits the
+        # first one made (tests/test_gpu_fp32_linear.py).  After the replay (both replays of the data-parallel form), host-only.
+        ops.note_weights_changed()
         return self.loss

@@ -25,7 +25,9 @@ class RuntimeState:
       last_cast_cache    that of the most recent forward: what a backward falls back to when its node kept none
       prefer_own_gemm    every legal bf16 Linear product on hs_gemm_nt (set while CUs are reserved for a communication library)
       zero_padded_grads  data_ptr -> zero-padded gradient buffer written by losses.seg_loss' backward (weak values, see PadSliceFn)
-      weight_epoch       generation counter of "the parameters may have changed" for caches that cannot rely on `_version`
+      weight_epoch       generation counter of "the parameters may have changed" for caches that cannot rely on `_version`; moved by
+                         note_forward, by optim.FlatAdam.step() and -- a replay runs no Python -- by graphs.GraphedTrainStep after
+                         every replay (note_weights_changed), so nothing derived from the weights before a replay is served after it
     One training setup per process is the supported configuration (as with DistributedDataParallel); `scoped` swaps fields for the
     duration of a block and restores them, which is how nested / temporary configurations should be expressed."""
 
@@ -60,6 +62,13 @@ def note_forward(grad_enabled):
     if grad_enabled or RT._epoch_dirty:
         RT.weight_epoch += 1
     RT._epoch_dirty = bool(grad_enabled)
+
+
+def note_weights_changed():
+    """The parameters have just been updated behind Python's back and no forward announced it (a HIP-graph replay of a training
+    step): open a new weight epoch now.  Nothing is pending afterwards, so the next no-grad forward opens no further one."""
+    RT.weight_epoch += 1
+    RT._epoch_dirty = False
 
 
 class _timed:
