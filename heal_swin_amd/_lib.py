@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_PKG, "lib", "libhealswin.so")
 HS_F32, HS_BF16 = 0, 1
 HS_F64 = 3
 HS_PRED_LABELS, HS_PRED_ROWS16 = 2, 4
+HS_ENSEMBLE_PROB, HS_ENSEMBLE_LOGIT = 0, 1
 HS_ATTN_COSINE = 1
 HS_ATTN_FORCE_VALU = 2
 HS_ATTN_RESIDUAL = 4
@@ -129,6 +130,12 @@ _SIGNATURES = {
     "hs_hp_rotated_interp": [c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
     "hs_hp_rotated_interp_host": [c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     "hs_hp_rotate": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr],
+    "hs_hp_ensemble_add_seg": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
+    "hs_hp_ensemble_add_seg_host": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int, c_int, c_ptr, c_ptr],
+    "hs_hp_ensemble_add_depth": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
+    "hs_hp_ensemble_add_depth_host": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr],
+    "hs_hp_ensemble_finish_seg": [c_i64, c_int, c_int, c_ptr, c_ptr, c_float, c_int, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr],
+    "hs_hp_ensemble_finish_depth": [c_i64, c_int, c_ptr, c_ptr, c_float, c_ptr, c_ptr],
     "hs_hp_interp_weights_nest": [c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],
     "hs_backproject_labels": [c_ptr, c_int, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr],
     "hs_backproject_image": [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr],

@@ -835,6 +835,52 @@ int hs_hp_rotate(int nside, int64_t npix, const double* rot, int batch, const ui
                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rotation ensembles at evaluation (heal_swin_amd/hp_ensemble.py: HPRotationEnsemble; csrc/hp_ensemble.hip): the way back of
+ * hs_hp_rotate.  A sample is predicted under several rotations; each prediction, made on a frame that hs_hp_rotate rotated by M
+ * (pixel q shows the scene at M g_q), is resampled onto the unrotated grid and accumulated there; the finish kernels average.
+ * The caller passes rot = M^T [dev] f64[batch, 9] (the inverse of an orthogonal M), so unrotated pixel p reads the prediction at
+ * direction M^T g_p through hs_hp_rotated_interp's function, unchanged; rot == NULL is the unrotated member (pixel p itself with
+ * weight 1).  npix = base_pix nside^2.  A neighbour j of the four is TAKEN when it is covered ((uint64_t) pix_j < npix), when
+ * valid[b, pix_j] != 0 if `valid` ([dev] u8[batch, npix], in the rotated frame, nullable) is given, and, for depth, when its value
+ * is finite.  Weights are rounded to fp32 once; sums run over j = 0 .. 3 in order in fp32 without FMA.
+ *   hs_hp_ensemble_add_seg    pred: logits HS_F32 / HS_BF16 (| HS_PRED_ROWS16), element (b, c, pixel) at b*stride_b + c*stride_k +
+ *                       pixel*stride_p as in hs_seg_confusion, n_classes <= 16.  value_j = softmax(row_j) in fp32
+ *                       (mode HS_ENSEMBLE_PROB) or row_j itself (HS_ENSEMBLE_LOGIT).  acc [dev] f32[batch, npix, KP], KP =
+ *                       4 ceil(n_classes / 4), 16-byte aligned: acc[b, p, c] += sum_j w_j value_j[c] (classes >= n_classes: += 0);
+ *                       wsum [dev] f32[batch, npix] += sum_j w_j.  accumulate == 0 stores instead of adding (the first member: no
+ *                       zero fill is needed); with accumulate != 0 a pixel that took no neighbour is not written.
+ *   hs_hp_ensemble_add_depth  pred: HS_F32 / HS_BF16, element (b, pixel) at b*stride_b + pixel*stride_p; acc, wsum [dev]
+ *                       f32[batch, npix]: acc += sum_j w_j d_j, wsum += sum_j w_j.
+ *   hs_hp_ensemble_finish_seg  preds [dev] u8[batch, npix] = argmax_c acc[b, p, c] (the first maximum, a NaN counts as the maximum,
+ *                       as torch.max) where wsum[b, p] > min_weight, `background` elsewhere; probs (nullable) [dev] f32, element
+ *                       (b, c, p) at b*stride_b + c*stride_k + p*stride_p = acc / wsum there, 0 elsewhere.
+ *   hs_hp_ensemble_finish_depth  out [dev] f32[batch, npix] = acc / wsum where wsum > min_weight, NaN elsewhere.
+ *   hs_hp_ensemble_add_seg_host, hs_hp_ensemble_add_depth_host  the same inline per-pixel functions in a plain loop, every
+ *                       pointer [host]: the oracle of the device entry points (the exponential is the one call that differs:
+ *                       v_exp_f32 of x log2(e) on the device, expf on the host; about 1e-7 on a probability).
+ * One thread per (sample, unrotated pixel), no LDS, no atomics: bit-reproducible.  HS_ERR_INVALID_ARG before any launch: nside no
+ * power of two or above 8192, npix not in {1 .. 12} nside^2, batch outside 1 .. 65535, n_classes outside 1 .. 16, another
+ * prediction kind or mode, a negative stride, HS_PRED_ROWS16 rows that are not contiguous / aligned / padded, a null pred / acc /
+ * wsum / preds / out, acc or wsum overlapping the predictions or each other, background outside 0 .. 255, a negative or NaN
+ * min_weight; HS_ERR_MISALIGNED: acc not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_ENSEMBLE_PROB 0
+#define HS_ENSEMBLE_LOGIT 1
+int hs_hp_ensemble_add_seg(int nside, int64_t npix, const double* rot, int batch, const void* pred, int pred_kind, int n_classes,
+                           int64_t stride_b, int64_t stride_k, int64_t stride_p, const uint8_t* valid, int mode, int accumulate, float* acc,
+                           float* wsum, void* stream);
+int hs_hp_ensemble_add_seg_host(int nside, int64_t npix, const double* rot, int batch, const void* pred, int pred_kind, int n_classes,
+                                int64_t stride_b, int64_t stride_k, int64_t stride_p, const uint8_t* valid, int mode, int accumulate,
+                                float* acc, float* wsum);
+int hs_hp_ensemble_add_depth(int nside, int64_t npix, const double* rot, int batch, const void* pred, int pred_kind, int64_t stride_b,
+                             int64_t stride_p, const uint8_t* valid, int accumulate, float* acc, float* wsum, void* stream);
+int hs_hp_ensemble_add_depth_host(int nside, int64_t npix, const double* rot, int batch, const void* pred, int pred_kind, int64_t stride_b,
+                                  int64_t stride_p, const uint8_t* valid, int accumulate, float* acc, float* wsum);
+int hs_hp_ensemble_finish_seg(int64_t npix, int batch, int n_classes, const float* acc, const float* wsum, float min_weight, int background,
+                              uint8_t* preds, float* probs, int64_t stride_b, int64_t stride_k, int64_t stride_p, void* stream);
+int hs_hp_ensemble_finish_depth(int64_t npix, int batch, const float* acc, const float* wsum, float min_weight, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation: HEALPix predictions scored and back-projected onto the fisheye image plane (heal_swin_amd/evaluation.py).
  * The tables of a calibration (nearest pixel, four interpolation pixels and weights per image-plane pixel) are built once on
  * the host; the per-batch work is the three gathers below.
