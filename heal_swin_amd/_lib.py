@@ -130,6 +130,10 @@ _SIGNATURES = {
     "hs_hp_rotated_interp": [c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr],
     "hs_hp_rotated_interp_host": [c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],
     "hs_hp_rotate": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr],
+    "hs_erp_to_hp": [c_int, c_i64, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_float,
+                     c_ptr],
+    "hs_erp_to_hp_host": [c_int, c_i64, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
+                          c_float],
     "hs_hp_ensemble_add_seg": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
     "hs_hp_ensemble_add_seg_host": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int, c_int, c_ptr, c_ptr],
     "hs_hp_ensemble_add_depth": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],

@@ -41,9 +41,15 @@ struct Vec3 {
     double x, y, z;
 };
 
+struct LibmSinCos {  // the math library's sincos: the device's on the device, the host's on the host
+    HS_HD void operator()(double a, double& s, double& c) const { sincos(a, &s, &c); }
+};
+
 // centre of nested pixel p: hs_pix2ang_nest's (face, ix, iy) -> ring jr -> zone, with the vector built from z and sin(theta)
-// directly (caps: sqrt(tmp (2 - tmp)), belt: sqrt((1 - z)(1 + z))) instead of through acos
-HS_HD Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p) {
+// directly (caps: sqrt(tmp (2 - tmp)), belt: sqrt((1 - z)(1 + z))) instead of through acos.  `sc(phi, s, c)` evaluates the sine and
+// cosine of the longitude: LibmSinCos unless the caller needs the same bits on the host and on the device (hs_erp_device.h).
+template <typename SinCos>
+HS_HD Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p, SinCos sc) {
     const int face = (int)(p >> log2_npface);
     const uint64_t in_face = (uint64_t)(p & (((int64_t)1 << log2_npface) - 1));
     const int64_t ix = compact_bits(in_face), iy = compact_bits(in_face >> 1);
@@ -72,9 +78,11 @@ HS_HD Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p) {
     if (t < 0) t += 8 * nr;
     const double phi = nr == nside ? 0.75 * halfpi * (double)t * fact1 : (0.5 * halfpi * (double)t) / (double)nr;
     double s, c;
-    sincos(phi, &s, &c);
+    sc(phi, s, c);
     return {sth * c, sth * s, z};
 }
+
+HS_HD Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p) { return pixel_centre(nside, log2_npface, p, LibmSinCos{}); }
 
 // T_Healpix_Base::get_ring_info2 without the first pixel: pixel count, centre colatitude and phase shift of ring 1 .. 4 nside - 1
 HS_HD void ring_info(int64_t ns, int64_t ring, int64_t& nr, double& th, bool& shifted) {

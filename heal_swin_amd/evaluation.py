@@ -12,6 +12,8 @@ pipeline's other end (`projection.HPProjector` is its input side).  Mirrors the 
       .depth(pred)                                    data/depth_estimation/project_depth_on_s2.py:370-386
                                                       (project_depth_hp_mask_back, NaN fill)  `hs_backproject_depth`
       .valid                                          evaluation/custom_metrics.py:48-53 (HPMaskedIoU.get_mask)
+      .from_angles(theta, phi, nside, ...)            the same tables for any image plane given by its pixels' directions
+                                                      (no counterpart; erp.ERPBackProjector's panorama)
   SegConfusion                                        the confusion matrix behind torchmetrics 0.3.2's IoU / Accuracy
                                                       (models_lightning/segmentation/model_lightning_swin_hp.py:47-55) and
                                                       the back-projected metrics (evaluation/hp_pred_writers.py:110-222,
@@ -186,12 +188,26 @@ class HPBackProjector:
     """
 
     def __init__(self, cal_info, nside, base_pix=8, output_resolution=1.0, rotate_pole=False, s2_bkgd_class=0, device="cuda"):
-        self.nside, self.base_pix, self.s2_bkgd_class = int(nside), int(base_pix), int(s2_bkgd_class)
-        if not 0 <= self.s2_bkgd_class <= 255:
-            raise ValueError("s2_bkgd_class must fit uint8")
         intr = cal_info["intrinsic"]
         u, v = get_uv_from_hw(intr["height"], intr["width"], output_resolution)
         theta, phi = project_img_points_to_s2(u, v, cal_info, rotate_pole)
+        self._set_tables(theta, phi, nside, base_pix, s2_bkgd_class, device)
+
+    @classmethod
+    def from_angles(cls, theta, phi, nside, base_pix=8, s2_bkgd_class=0, device="cuda"):
+        """The projector of any image plane given by the directions (theta, phi) [H', W'] of its pixels (erp.ERPBackProjector's
+        panorama): the same tables from the same `hp_nearest_pix_idcs`, every method unchanged."""
+        self = cls.__new__(cls)
+        self._set_tables(theta, phi, nside, base_pix, s2_bkgd_class, device)
+        return self
+
+    def _set_tables(self, theta, phi, nside, base_pix, s2_bkgd_class, device):
+        self.nside, self.base_pix, self.s2_bkgd_class = int(nside), int(base_pix), int(s2_bkgd_class)
+        if not 0 <= self.s2_bkgd_class <= 255:
+            raise ValueError("s2_bkgd_class must fit uint8")
+        theta, phi = np.asarray(theta, dtype=np.float64), np.asarray(phi, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape != phi.shape:
+            raise ValueError(f"theta and phi must share one [H', W'] shape, got {theta.shape} and {phi.shape}")
         nearest, pix, wgt = hp_nearest_pix_idcs(self.nside, theta, phi)
         self.device = _device(device)
         self.shape = tuple(nearest.shape)

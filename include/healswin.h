@@ -835,6 +835,45 @@ int hs_hp_rotate(int nside, int64_t npix, const double* rot, int batch, const ui
                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Equirectangular panoramas (ERP, the lat/long image) onto the sphere (heal_swin_amd/erp.py: ERPProjector; csrc/erp_project.hip,
+ * csrc/hs_erp_device.h): the full-sphere data entry point, no counterpart in the reference.  Output pixel p of sample b shows the
+ * panorama at direction d = M_b g_p (the convention of hs_hp_rotated_coords), M_b = rot[9 b .. 9 b + 8] row-major ([dev]; any
+ * real matrix is accepted).  Per (sample b, pixel p), in float64 without FMA:
+ *   g = centre of nested pixel p as a unit vector (as in hs_hp_rotated_coords), d = M_b g,
+ *   theta = atan2(hypot(d.x, d.y), d.z), phi = atan2(d.y, d.x) reduced to [0, 2 pi) with HEALPix's fmodulo,
+ *   x = phi width / (2 pi) - 0.5 (column), y = theta height / pi - 0.5 (row): column j is centred at longitude
+ *   2 pi (j + 0.5) / width, row i at colatitude pi (i + 0.5) / height.
+ *   frame [dev] u8 or f32 [batch, channels, height, width] (frame_kind HS_U8 / HS_F32) -> frame_out, the same type,
+ *     [batch, channels, npix]: j0 = floor x, fx = x - j0, i0 = floor y, fy = y - i0; columns WRAP (ja = j0 mod width,
+ *     jb = (j0 + 1) mod width, non-negative), rows CLAMP (ia, ib = i0, i0 + 1 clamped to [0, height - 1]);
+ *     v = (1-fy) ((1-fx) v[ia,ja] + fx v[ia,jb]) + fy ((1-fx) v[ib,ja] + fx v[ib,jb]), in that order.  These are the proper
+ *     bilinear weights, not hs_sample_bilinear_u8's (which mirror the reference's ceil - r / r - floor and give 0 at integer
+ *     coordinates).  With supersample = s in {0, 1, 2} the value is the mean of the un-rounded v at the centres of the 4^s nested
+ *     children p 4^s .. p 4^s + 4^s - 1 at nside 2^s, summed in ascending order and multiplied by the exact 2^(-2s).  u8: rint
+ *     (half to even) clamped to [0, 255]; f32: the value cast to float, NaN propagates.
+ *   labels [dev] u8[batch, height, width] -> labels_out [batch, npix]: the pixel at column floor(x + 0.5) mod width and row
+ *     floor(y + 0.5) clamped to [0, height - 1], at the pixel's own centre whatever supersample is; classes never mix.
+ *   depth [dev] f32[batch, height, width] -> depth_out [batch, npix]: that pixel's word copied (inf and NaN keep their bits).
+ *   A non-finite component of d (of any child, for the frame): 0 (u8) or NaN (f32), `background`, depth_fill; no load is issued.
+ * npix = base_pix nside^2, base_pix in 1 .. 12.  Each plane is given by both pointers or by neither (NULL).  One launch, one
+ * thread per (sample, output pixel), the geometry evaluated once and applied to every plane given; no table is written, no LDS,
+ * no atomics.  hs_erp_to_hp_host runs the same inline function in a plain loop, every pointer [host]: the kernel's oracle, equal
+ * bit for bit, because the sine and cosine of the pixel centre, hypot and atan2 are evaluated in +, -, *, / and sqrt alone
+ * (csrc/hs_erp_device.h; about 1 ulp from the math library's values, which differ between the device and the host in the last bit).
+ * For a matrix so large or so small that the squares of d's components leave float64's range, theta is pi / 2, 0 or pi.
+ * HS_ERR_INVALID_ARG before any launch: nside no power of two, supersample outside {0, 1, 2}, nside << supersample above 8192
+ * (the nested indices are int32), npix not in {1 .. 12} nside^2, batch outside 1 .. 65535, height or width below 1 or height
+ * width >= 2^31, exactly one pointer of a pair, no plane, with a frame another frame_kind or channels outside 1 .. 16, background
+ * outside 0 .. 255, a null rot, an output overlapping an input or the matrices.
+ * ---------------------------------------------------------------------------------------------- */
+int hs_erp_to_hp(int nside, int64_t npix, const double* rot, int batch, int height, int width, int supersample, const void* frame,
+                 int frame_kind, int channels, void* frame_out, const uint8_t* labels, uint8_t* labels_out, int background,
+                 const float* depth, float* depth_out, float depth_fill, void* stream);
+int hs_erp_to_hp_host(int nside, int64_t npix, const double* rot, int batch, int height, int width, int supersample, const void* frame,
+                      int frame_kind, int channels, void* frame_out, const uint8_t* labels, uint8_t* labels_out, int background,
+                      const float* depth, float* depth_out, float depth_fill);
+
+/* ------------------------------------------------------------------------------------------------
  * Rotation ensembles at evaluation (heal_swin_amd/hp_ensemble.py: HPRotationEnsemble; csrc/hp_ensemble.hip): the way back of
  * hs_hp_rotate.  A sample is predicted under several rotations; each prediction, made on a frame that hs_hp_rotate rotated by M
  * (pixel q shows the scene at M g_q), is resampled onto the unrotated grid and accumulated there; the finish kernels average.
