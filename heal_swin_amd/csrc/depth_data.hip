@@ -1,13 +1,7 @@
-// The depth data path (heal_swin_amd/depth_data.py): the per-frame part of the reference's depth projection, the target
-// transforms of its datasets and Lightning module, and the dataset statistics behind their normalization constants.
+// The depth data path (heal_swin_amd/depth_data.py) after the projection: the target transforms of the reference's datasets and
+// Lightning module, and the dataset statistics behind their normalization constants.  (The per-frame samplers of the depth
+// projection, hs_sample_bilinear_u8_f32 and hs_sample_nearest_f32, are projection.hip's.)
 //
-//   hs_sample_bilinear_u8_f32  sample_bilinear(img, v, u).astype(np.float32)
-//                              (data/depth_estimation/project_depth_on_s2.py:48-77, :411): projection.hip's float64 arithmetic
-//                              and operation order, rounded once to float32; non-finite coordinates give NaN as in the reference.
-//   hs_sample_nearest_f32      sample_mask(depth, v, u, s2_bkgd_class) (:80-84, :412): nearest pixel by round-half-to-even,
-//                              an exact float32 copy, the background value outside the image.
-//   hs_sample_*_per_sample     the two kernels above against one coordinate row per sample (rx, ry [batch, n]; the rotation
-//                              augmentation of projection_aug.hip), same arithmetic.
 //   hs_depth_target            one elementwise pass over [batch, n] rows read and written through their own strides:
 //                              the datasets' target preparation (hp_depth_datasets.py:90-107, flat_depth_datasets.py:122-148),
 //                              transform_and_normalize and unnormalize_and_retransform (utils/depth_utils.py:60-104, :140-170).
@@ -32,58 +26,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kStatsBlocksMax = 1024;
 constexpr int kHistBlocksMax = 512;  // every workgroup reads the edge table once
-
-struct Corner {
-    bool ok;
-    int64_t off;
-};
-__device__ __forceinline__ Corner corner(double fx, double fy, int h, int w) {
-    // numpy's bounds test on the integer casts; doubles compare the same way, NaN and +-inf fail it
-    const bool ok = fx >= 0.0 && fx < (double)h && fy >= 0.0 && fy < (double)w;
-    return {ok, ok ? (int64_t)fx * w + (int64_t)fy : 0};
-}
-
-// PER_SAMPLE (both sampling kernels): the grid's y index is the sample, which reads row y of rx, ry [batch, n] and owns its `planes`
-// (= channels, or 1 map) source planes; otherwise one (rx, ry) [n] serves all `planes`.  The arithmetic below is the same code.
-template <bool PER_SAMPLE>
-__global__ void __launch_bounds__(kThreads) sample_bilinear_u8_f32_kernel(const uint8_t* __restrict__ img, int planes, int h, int w,
-                                                                          const double* __restrict__ rx, const double* __restrict__ ry,
-                                                                          int64_t n, float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (PER_SAMPLE) {
-        const int64_t b = blockIdx.y;
-        rx += b * n, ry += b * n, img += b * planes * ((int64_t)h * w), out += b * planes * n;
-    }
-    const double x = rx[i], y = ry[i];
-    const double x0 = floor(x), x1 = ceil(x), y0 = floor(y), y1 = ceil(y);
-    const Corner c00 = corner(x0, y0, h, w), c10 = corner(x1, y0, h, w), c01 = corner(x0, y1, h, w), c11 = corner(x1, y1, h, w);
-    const double wx0 = x1 - x, wx1 = x - x0, wy0 = y1 - y, wy1 = y - y0;  // NaN for NaN / +-inf coordinates: the result is NaN
-    const int64_t plane = (int64_t)h * w;
-    for (int p = 0; p < planes; ++p) {
-        const uint8_t* s = img + p * plane;
-        const double s00 = c00.ok ? (double)s[c00.off] : 0.0, s10 = c10.ok ? (double)s[c10.off] : 0.0;
-        const double s01 = c01.ok ? (double)s[c01.off] : 0.0, s11 = c11.ok ? (double)s[c11.off] : 0.0;
-        const double fx1 = wx0 * s00 + wx1 * s10;
-        const double fx2 = wx0 * s01 + wx1 * s11;
-        out[p * n + i] = (float)(wy0 * fx1 + wy1 * fx2);
-    }
-}
-
-template <bool PER_SAMPLE>
-__global__ void __launch_bounds__(kThreads) sample_nearest_f32_kernel(const float* __restrict__ src, int planes, int h, int w,
-                                                                      const double* __restrict__ rx, const double* __restrict__ ry,
-                                                                      int64_t n, float background, float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (PER_SAMPLE) {
-        const int64_t b = blockIdx.y;
-        rx += b * n, ry += b * n, src += b * planes * ((int64_t)h * w), out += b * planes * n;
-    }
-    const Corner c = corner(rint(rx[i]), rint(ry[i]), h, w);  // np.around: round half to even
-    const int64_t plane = (int64_t)h * w;
-    for (int p = 0; p < planes; ++p) out[p * n + i] = c.ok ? src[p * plane + c.off] : background;
-}
 
 // ------------------------------------------------------------------ target transforms
 // the per-element rule: hs_depth_target.h (shared with the flat data path's resize kernel)
@@ -312,60 +254,9 @@ __global__ void __launch_bounds__(kThreads) depth_histogram_kernel(const float* 
         if (hist[j] != 0) atomicAdd(&counts[j], (unsigned long long)hist[j]);
 }
 
-// one argument check and one launch for the shared-table and the per-sample entry points
-template <bool PER_SAMPLE>
-int sample_bilinear_u8_f32(const void* img, int batch, int channels, int height, int width, const double* rx, const double* ry, int64_t n,
-                           float* out, void* stream) {
-    HS_CHECK_ARG(batch > 0 && channels > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
-    HS_CHECK_ARG((int64_t)batch * channels < (1 << 20), "too many image planes");
-    HS_CHECK_ARG(!PER_SAMPLE || batch <= 65535, "per-sample tables: batch <= 65535");
-    if (n == 0) return HS_OK;
-    HS_CHECK_ARG(img && rx && ry && out, "null pointer");
-    hipLaunchKernelGGL(sample_bilinear_u8_f32_kernel<PER_SAMPLE>,
-                       dim3((unsigned)((n + kThreads - 1) / kThreads), PER_SAMPLE ? (unsigned)batch : 1u), dim3(kThreads), 0,
-                       (hipStream_t)stream, (const uint8_t*)img, PER_SAMPLE ? channels : batch * channels, height, width, rx, ry, n, out);
-    HS_LAUNCH_CHECK("sample_bilinear_u8_f32");
-    return HS_OK;
-}
-
-template <bool PER_SAMPLE>
-int sample_nearest_f32(const float* src, int batch, int height, int width, const double* rx, const double* ry, int64_t n, float background,
-                       float* out, void* stream) {
-    HS_CHECK_ARG(batch > 0 && height > 0 && width > 0 && n >= 0, "bad shape");
-    HS_CHECK_ARG(batch < (1 << 20), "too many maps");
-    HS_CHECK_ARG(!PER_SAMPLE || batch <= 65535, "per-sample tables: batch <= 65535");
-    if (n == 0) return HS_OK;
-    HS_CHECK_ARG(src && rx && ry && out, "null pointer");
-    hipLaunchKernelGGL(sample_nearest_f32_kernel<PER_SAMPLE>,
-                       dim3((unsigned)((n + kThreads - 1) / kThreads), PER_SAMPLE ? (unsigned)batch : 1u), dim3(kThreads), 0,
-                       (hipStream_t)stream, src, PER_SAMPLE ? 1 : batch, height, width, rx, ry, n, background, out);
-    HS_LAUNCH_CHECK("sample_nearest_f32");
-    return HS_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-int hs_sample_bilinear_u8_f32(const void* img, int batch, int channels, int height, int width, const double* rx, const double* ry,
-                              int64_t n, float* out, void* stream) {
-    return sample_bilinear_u8_f32<false>(img, batch, channels, height, width, rx, ry, n, out, stream);
-}
-
-int hs_sample_bilinear_u8_f32_per_sample(const void* img, int batch, int channels, int height, int width, const double* rx,
-                                         const double* ry, int64_t n, float* out, void* stream) {
-    return sample_bilinear_u8_f32<true>(img, batch, channels, height, width, rx, ry, n, out, stream);
-}
-
-int hs_sample_nearest_f32(const float* src, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
-                          float background, float* out, void* stream) {
-    return sample_nearest_f32<false>(src, batch, height, width, rx, ry, n, background, out, stream);
-}
-
-int hs_sample_nearest_f32_per_sample(const float* src, int batch, int height, int width, const double* rx, const double* ry, int64_t n,
-                                     float background, float* out, void* stream) {
-    return sample_nearest_f32<true>(src, batch, height, width, rx, ry, n, background, out, stream);
-}
 
 int hs_depth_target(const float* in, int64_t in_stride_b, int64_t in_stride_p, float* out, int64_t out_stride_b, int64_t out_stride_p,
                     int64_t batch, int64_t n, int flags, int transform, float shift, float scale, void* stream) {

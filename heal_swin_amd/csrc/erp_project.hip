@@ -14,6 +14,7 @@
 // against 4 scattered loads per channel and centre.
 #include "hs_device.h"
 #include "hs_erp_device.h"
+#include "hs_sphere_args.h"
 
 #pragma clang fp contract(off)
 
@@ -21,8 +22,7 @@ namespace {
 
 using hs::erp::Args;
 using hs::erp::project_pixel;
-
-constexpr int kThreads = 256;
+using namespace hs::sphere;
 
 // grid (pixel blocks, samples)
 template <typename T, bool Super>
@@ -62,23 +62,14 @@ struct Loop {
     }
 };
 
-bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + (uintptr_t)b_bytes && y < x + (uintptr_t)a_bytes;
-}
-
 // every refusal of both entry points; on HS_OK `a` is filled in
 int check(const char* who, int nside, int64_t npix, const double* rot, int batch, int height, int width, int supersample,
           const void* frame, int frame_kind, int channels, void* frame_out, const uint8_t* labels, uint8_t* labels_out, int background,
           const float* depth, float* depth_out, float depth_fill, Args& a) {
-    HS_CHECK_ARG(nside >= 1 && hs::is_pow2(nside), "%s: nside must be a power of two, got %d", who, nside);
     HS_CHECK_ARG(supersample >= 0 && supersample <= 2, "%s: supersample must be 0, 1 or 2, got %d", who, supersample);
-    HS_CHECK_ARG(nside <= (8192 >> supersample), "%s: nside %d << supersample %d above 8192: the nested indices are int32", who, nside,
-                 supersample);
-    const int64_t npface = (int64_t)nside * nside;
-    HS_CHECK_ARG(npix >= npface && npix <= 12 * npface && npix % npface == 0,
-                 "%s: npix must be base_pix nside^2 with base_pix in [1, 12], got %lld for nside %d", who, (long long)npix, nside);
-    HS_CHECK_ARG(batch > 0 && batch <= 65535, "%s: batch must be in [1, 65535], got %d", who, batch);
+    if (int st = check_nside(who, nside, supersample)) return st;
+    if (int st = check_npix(who, nside, npix)) return st;
+    if (int st = check_batch(who, batch)) return st;
     HS_CHECK_ARG(height >= 1 && width >= 1 && (int64_t)height * width < (1ll << 31),
                  "%s: the panorama must be at least 1 x 1 with height width < 2^31, got %d x %d", who, height, width);
     HS_CHECK_ARG(!frame == !frame_out && !labels == !labels_out && !depth == !depth_out,
@@ -97,12 +88,10 @@ int check(const char* who, int nside, int64_t npix, const double* rot, int batch
     const int64_t out_bytes[3] = {dst * channels * elem, dst, dst * 4};
     for (int o = 0; o < 3; ++o)
         for (int i = 0; i < 4; ++i)
-            HS_CHECK_ARG(!overlap(out[o], out_bytes[o], in[i], in_bytes[i]), "%s: an output overlaps an input (a pixel reads others' source values)",
-                         who);
-    uint32_t fill;
-    __builtin_memcpy(&fill, &depth_fill, 4);
-    a = Args{nside,  npix,       rot,        height, width,       supersample,           frame,
-             frame_out, channels, labels, labels_out, background, (const uint32_t*)depth, (uint32_t*)depth_out, fill};
+            HS_CHECK_ARG(!ranges_overlap(out[o], out_bytes[o], in[i], in_bytes[i]),
+                         "%s: an output overlaps an input (a pixel reads others' source values)", who);
+    a = Args{nside,     npix,     rot,    height,     width,      supersample,            frame,
+             frame_out, channels, labels, labels_out, background, (const uint32_t*)depth, (uint32_t*)depth_out, float_word(depth_fill)};
     return HS_OK;
 }
 
@@ -117,7 +106,7 @@ int hs_erp_to_hp(int nside, int64_t npix, const double* rot, int batch, int heig
     if (int st = check("hs_erp_to_hp", nside, npix, rot, batch, height, width, supersample, frame, frame_kind, channels, frame_out, labels,
                        labels_out, background, depth, depth_out, depth_fill, a))
         return st;
-    dispatch(a, frame_kind, Launch{a, dim3((unsigned)((npix + kThreads - 1) / kThreads), (unsigned)batch), (hipStream_t)stream});
+    dispatch(a, frame_kind, Launch{a, pixel_grid(npix, batch), (hipStream_t)stream});
     HS_LAUNCH_CHECK("erp_to_hp");
     return HS_OK;
 }

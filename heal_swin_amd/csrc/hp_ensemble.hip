@@ -23,16 +23,18 @@
 
 #include "hs_device.h"
 #include "hs_healpix_device.h"
+#include "hs_sphere_args.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 using hs::bf16_t;
+using hs::healpix::covered;
 using hs::healpix::rotated_interp;
 using hs::healpix::RotatedInterp;
+using namespace hs::sphere;
 
-constexpr int kThreads = 256;
 constexpr int kMaxClasses = 16;
 
 struct SegArgs {
@@ -56,8 +58,6 @@ struct DepthArgs {
     float* wsum;
     int accumulate;
 };
-
-HS_HD bool covered(int32_t idx, int64_t npix) { return (uint64_t)(int64_t)idx < (uint64_t)npix; }
 
 HS_HD float bf16_bits_to_float(uint32_t b) {
     const uint32_t w = b << 16;
@@ -253,18 +253,9 @@ __global__ void __launch_bounds__(kThreads) ensemble_finish_depth_kernel(int64_t
 }
 
 int check_grid(const char* who, int nside, int64_t npix, int batch) {
-    HS_CHECK_ARG(nside >= 1 && hs::is_pow2(nside), "%s: nside must be a power of two, got %d", who, nside);
-    HS_CHECK_ARG(nside <= 8192, "%s: nside %d above 8192: the nested indices are int32", who, nside);
-    const int64_t npface = (int64_t)nside * nside;
-    HS_CHECK_ARG(npix >= npface && npix <= 12 * npface && npix % npface == 0,
-                 "%s: npix must be base_pix nside^2 with base_pix in [1, 12], got %lld for nside %d", who, (long long)npix, nside);
-    HS_CHECK_ARG(batch > 0 && batch <= 65535, "%s: batch must be in [1, 65535], got %d", who, batch);
-    return HS_OK;
-}
-
-bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)b_bytes && y < x + (uintptr_t)a_bytes;
+    if (int st = check_nside(who, nside)) return st;
+    if (int st = check_npix(who, nside, npix)) return st;
+    return check_batch(who, batch);
 }
 
 int elem_size(int kind) { return (kind & ~HS_PRED_ROWS16) == HS_F32 ? 4 : 2; }
@@ -290,8 +281,8 @@ int check_seg(const char* who, int nside, int64_t npix, int batch, const void* p
     const int64_t last = (kind & HS_PRED_ROWS16) ? width : (K - 1) * sk + 1;
     const int64_t pred_bytes = ((batch - 1) * sb + (npix - 1) * sp + last) * elem_size(kind);
     const int64_t acc_bytes = (int64_t)batch * npix * KP * 4, wsum_bytes = (int64_t)batch * npix * 4;
-    HS_CHECK_ARG(!overlap(acc, acc_bytes, pred, pred_bytes) && !overlap(wsum, wsum_bytes, pred, pred_bytes) &&
-                     !overlap(acc, acc_bytes, wsum, wsum_bytes),
+    HS_CHECK_ARG(!ranges_overlap(acc, acc_bytes, pred, pred_bytes) && !ranges_overlap(wsum, wsum_bytes, pred, pred_bytes) &&
+                     !ranges_overlap(acc, acc_bytes, wsum, wsum_bytes),
                  "%s: acc / wsum overlap the predictions or each other (a pixel reads others' rows)", who);
     return HS_OK;
 }
@@ -303,7 +294,8 @@ int check_depth(const char* who, int nside, int64_t npix, int batch, const void*
     HS_CHECK_ARG(sb >= 0 && sp >= 0, "%s: negative stride", who);
     HS_CHECK_ARG(pred && acc && wsum, "%s: null pointer", who);
     const int64_t pred_bytes = ((batch - 1) * sb + (npix - 1) * sp + 1) * elem_size(kind), bytes = (int64_t)batch * npix * 4;
-    HS_CHECK_ARG(!overlap(acc, bytes, pred, pred_bytes) && !overlap(wsum, bytes, pred, pred_bytes) && !overlap(acc, bytes, wsum, bytes),
+    HS_CHECK_ARG(!ranges_overlap(acc, bytes, pred, pred_bytes) && !ranges_overlap(wsum, bytes, pred, pred_bytes) &&
+                     !ranges_overlap(acc, bytes, wsum, bytes),
                  "%s: acc / wsum overlap the predictions or each other (a pixel reads others' values)", who);
     return HS_OK;
 }
@@ -347,8 +339,6 @@ struct LoopSeg {
             for (int64_t p = 0; p < a.npix; ++p) add_seg_pixel<T, R, KP>(a, b, p);
     }
 };
-
-dim3 pixel_grid(int64_t npix, int batch) { return dim3((unsigned)((npix + kThreads - 1) / kThreads), (unsigned)batch); }
 
 }  // namespace
 
@@ -409,7 +399,7 @@ int hs_hp_ensemble_finish_seg(int64_t npix, int batch, int n_classes, const floa
                               uint8_t* preds, float* probs, int64_t stride_b, int64_t stride_k, int64_t stride_p, void* stream) {
     const char* who = "hs_hp_ensemble_finish_seg";
     HS_CHECK_ARG(npix > 0 && npix < (1ll << 31), "%s: npix must be in [1, 2^31), got %lld", who, (long long)npix);
-    HS_CHECK_ARG(batch > 0 && batch <= 65535, "%s: batch must be in [1, 65535], got %d", who, batch);
+    if (int st = check_batch(who, batch)) return st;
     HS_CHECK_ARG(n_classes >= 1 && n_classes <= kMaxClasses, "%s: n_classes must be in [1, %d], got %d", who, kMaxClasses, n_classes);
     HS_CHECK_ARG(background >= 0 && background <= 255, "%s: background must be in [0, 255], got %d", who, background);
     HS_CHECK_ARG(min_weight >= 0.f, "%s: min_weight must be >= 0", who);  // a NaN fails
@@ -435,7 +425,7 @@ int hs_hp_ensemble_finish_seg(int64_t npix, int batch, int n_classes, const floa
 int hs_hp_ensemble_finish_depth(int64_t npix, int batch, const float* acc, const float* wsum, float min_weight, float* out, void* stream) {
     const char* who = "hs_hp_ensemble_finish_depth";
     HS_CHECK_ARG(npix > 0 && npix < (1ll << 31), "%s: npix must be in [1, 2^31), got %lld", who, (long long)npix);
-    HS_CHECK_ARG(batch > 0 && batch <= 65535, "%s: batch must be in [1, 65535], got %d", who, batch);
+    if (int st = check_batch(who, batch)) return st;
     HS_CHECK_ARG(min_weight >= 0.f, "%s: min_weight must be >= 0", who);
     HS_CHECK_ARG(acc && wsum && out, "%s: null pointer", who);
     hipLaunchKernelGGL(ensemble_finish_depth_kernel, pixel_grid(npix, batch), dim3(kThreads), 0, (hipStream_t)stream, npix, acc, wsum,

@@ -7,24 +7,26 @@
 //     frame   rint(((w0 v0 + w1 v1) + w2 v2) + w3 v3) clamped to [0, 255], float64 without FMA, an uncovered neighbour reads 0.0
 //     labels  labels[b, nearest], `background` where uncovered: classes never mix
 //     depth   depth[b, nearest] copied bit for bit, `depth_fill` where uncovered
-// A source index is covered iff (uint64_t) idx < (uint64_t) npix, compared before every load: the base pixels the map does not
-// hold, and the -1 of a non-finite matrix, are uncovered.  Convention of hs_hp_rotated_coords: output pixel p shows the source
-// map at direction M_b g_p.
+// A source index is covered iff (uint64_t) idx < (uint64_t) npix (hs::healpix::covered), compared before every load: the base
+// pixels the map does not hold, and the -1 of a non-finite matrix, are uncovered.  Convention of hs_hp_rotated_coords: output
+// pixel p shows the source map at direction M_b g_p.
 //
 // One thread per (sample, output pixel), the geometry evaluated once and applied to every plane given; no table is written, no
 // LDS, no atomics.  Bound by float64 transcendental throughput like hp_rotated_coords_kernel (sincos, hypot, two atan2, cos,
 // fmod and, per bracketing ring, acos or atan2), against 4 scattered byte loads per channel.
 #include "hs_device.h"
 #include "hs_healpix_device.h"
+#include "hs_sphere_args.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+using hs::healpix::covered;
 using hs::healpix::rotated_interp;
 using hs::healpix::RotatedInterp;
-
-constexpr int kThreads = 256;
+using hs::healpix::store_interp;
+using namespace hs::sphere;
 
 // grid (pixel blocks, samples)
 __global__ void __launch_bounds__(kThreads) hp_rotated_interp_kernel(int64_t nside, int64_t first_pix, int64_t count,
@@ -33,16 +35,9 @@ __global__ void __launch_bounds__(kThreads) hp_rotated_interp_kernel(int64_t nsi
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
     const int64_t b = blockIdx.y;
-    const RotatedInterp r = rotated_interp(nside, rot + 9 * b, first_pix + i);  // the matrix is uniform over the workgroup
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        pix[(b * 4 + k) * count + i] = r.pix[k];
-        wgt[(b * 4 + k) * count + i] = r.wgt[k];
-    }
-    nearest[b * count + i] = r.nearest;
+    // the matrix is uniform over the workgroup
+    store_interp(rotated_interp(nside, rot + 9 * b, first_pix + i), b, i, count, pix, wgt, nearest);
 }
-
-__device__ __forceinline__ bool covered(int32_t idx, int64_t npix) { return (uint64_t)(int64_t)idx < (uint64_t)npix; }
 
 __global__ void __launch_bounds__(kThreads) hp_rotate_kernel(int64_t nside, int64_t npix, const double* __restrict__ rot,
                                                              const uint8_t* __restrict__ img, int channels, uint8_t* __restrict__ img_out,
@@ -69,26 +64,11 @@ __global__ void __launch_bounds__(kThreads) hp_rotate_kernel(int64_t nside, int6
     if (depth) depth_out[b * npix + i] = cn ? depth[b * npix + r.nearest] : depth_fill;  // the word, not the value: NaNs keep their bits
 }
 
-// nside a power of two whose 12 nside^2 nested indices fit the int32 outputs
-int check_nside(const char* who, int nside) {
-    HS_CHECK_ARG(nside >= 1 && hs::is_pow2(nside), "%s: nside must be a power of two, got %d", who, nside);
-    HS_CHECK_ARG(nside <= (1 << 29), "%s: nside %d above HEALPix's limit 2^29", who, nside);
-    HS_CHECK_ARG(nside <= 8192, "%s: nside %d above 8192: the nested indices are int32", who, nside);
-    return HS_OK;
-}
-
+// the grid, the pixel sub-range and the batch of the two hs_hp_rotated_interp entry points
 int check_range(const char* who, int nside, int64_t first_pix, int64_t count, int batch) {
     if (int st = check_nside(who, nside)) return st;
-    const int64_t npix = 12 * (int64_t)nside * nside;
-    HS_CHECK_ARG(first_pix >= 0 && count >= 0 && first_pix <= npix && count <= npix - first_pix, "%s: pixel range outside [0, 12 nside^2)",
-                 who);
-    HS_CHECK_ARG(batch > 0 && batch <= 65535, "%s: batch must be in [1, 65535], got %d", who, batch);
-    return HS_OK;
-}
-
-bool overlap(const void* a, const void* b, int64_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
+    if (int st = check_pixel_range(who, nside, first_pix, count)) return st;
+    return check_batch(who, batch);
 }
 
 }  // namespace
@@ -100,8 +80,8 @@ int hs_hp_rotated_interp(int nside, int64_t first_pix, int64_t count, const doub
     if (int st = check_range("hs_hp_rotated_interp", nside, first_pix, count, batch)) return st;
     if (count == 0) return HS_OK;
     HS_CHECK_ARG(rot && pix && wgt && nearest, "hs_hp_rotated_interp: null pointer");
-    hipLaunchKernelGGL(hp_rotated_interp_kernel, dim3((unsigned)((count + kThreads - 1) / kThreads), (unsigned)batch), dim3(kThreads), 0,
-                       (hipStream_t)stream, (int64_t)nside, first_pix, count, rot, pix, wgt, nearest);
+    hipLaunchKernelGGL(hp_rotated_interp_kernel, pixel_grid(count, batch), dim3(kThreads), 0, (hipStream_t)stream, (int64_t)nside,
+                       first_pix, count, rot, pix, wgt, nearest);
     HS_LAUNCH_CHECK("hp_rotated_interp");
     return HS_OK;
 }
@@ -112,14 +92,8 @@ int hs_hp_rotated_interp_host(int nside, int64_t first_pix, int64_t count, const
     if (count == 0) return HS_OK;
     HS_CHECK_ARG(rot && pix && wgt && nearest, "hs_hp_rotated_interp_host: null pointer");
     for (int64_t b = 0; b < batch; ++b)
-        for (int64_t i = 0; i < count; ++i) {
-            const RotatedInterp r = rotated_interp(nside, rot + 9 * b, first_pix + i);
-            for (int k = 0; k < 4; ++k) {
-                pix[(b * 4 + k) * count + i] = r.pix[k];
-                wgt[(b * 4 + k) * count + i] = r.wgt[k];
-            }
-            nearest[b * count + i] = r.nearest;
-        }
+        for (int64_t i = 0; i < count; ++i)
+            store_interp(rotated_interp(nside, rot + 9 * b, first_pix + i), b, i, count, pix, wgt, nearest);
     return HS_OK;
 }
 
@@ -128,25 +102,21 @@ int hs_hp_rotate(int nside, int64_t npix, const double* rot, int batch, const ui
                  void* stream) {
     const char* who = "hs_hp_rotate";
     if (int st = check_nside(who, nside)) return st;
-    const int64_t npface = (int64_t)nside * nside;
-    HS_CHECK_ARG(npix >= npface && npix <= 12 * npface && npix % npface == 0,
-                 "%s: npix must be base_pix nside^2 with base_pix in [1, 12], got %lld for nside %d", who, (long long)npix, nside);
-    HS_CHECK_ARG(batch > 0 && batch <= 65535, "%s: batch must be in [1, 65535], got %d", who, batch);
+    if (int st = check_npix(who, nside, npix)) return st;
+    if (int st = check_batch(who, batch)) return st;
     HS_CHECK_ARG(!img == !img_out && !labels == !labels_out && !depth == !depth_out,
                  "%s: each plane needs both its input and its output pointer, or neither", who);
     HS_CHECK_ARG(img || labels || depth, "%s: no plane given", who);
     if (img) HS_CHECK_ARG(channels >= 1 && channels <= 16, "%s: channels must be in [1, 16], got %d", who, channels);
     HS_CHECK_ARG(background >= 0 && background <= 255, "%s: background must be in [0, 255], got %d", who, background);
     const int64_t plane = (int64_t)batch * npix;
-    HS_CHECK_ARG(!(img && overlap(img, img_out, plane * channels)) && !(labels && overlap(labels, labels_out, plane)) &&
-                     !(depth && overlap(depth, depth_out, plane * 4)),
+    HS_CHECK_ARG(!ranges_overlap(img, plane * channels, img_out, plane * channels) && !ranges_overlap(labels, plane, labels_out, plane) &&
+                     !ranges_overlap(depth, plane * 4, depth_out, plane * 4),
                  "%s: an output overlaps its input (a pixel reads others' source values)", who);
     HS_CHECK_ARG(rot, "%s: null pointer", who);
-    uint32_t fill;
-    __builtin_memcpy(&fill, &depth_fill, 4);
-    hipLaunchKernelGGL(hp_rotate_kernel, dim3((unsigned)((npix + kThreads - 1) / kThreads), (unsigned)batch), dim3(kThreads), 0,
-                       (hipStream_t)stream, (int64_t)nside, npix, rot, img, channels, img_out, labels, labels_out, background,
-                       (const uint32_t*)depth, (uint32_t*)depth_out, fill);
+    hipLaunchKernelGGL(hp_rotate_kernel, pixel_grid(npix, batch), dim3(kThreads), 0, (hipStream_t)stream, (int64_t)nside, npix, rot, img,
+                       channels, img_out, labels, labels_out, background, (const uint32_t*)depth, (uint32_t*)depth_out,
+                       float_word(depth_fill));
     HS_LAUNCH_CHECK("hp_rotate");
     return HS_OK;
 }

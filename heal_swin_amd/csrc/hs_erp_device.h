@@ -115,23 +115,13 @@ HS_HD double atan2_finite(double y, double x) {  // finite arguments; atan2(+-0,
 
 HS_HD Tap tap(int64_t nside, const double* m, int64_t p, int height, int width) {
     const int log2_ns = __builtin_ctzll((unsigned long long)nside);
-    const healpix::Vec3 g = healpix::pixel_centre(nside, 2 * log2_ns, p, SinCos{});
-    const double dx = m[0] * g.x + m[1] * g.y + m[2] * g.z;
-    const double dy = m[3] * g.x + m[4] * g.y + m[5] * g.z;
-    const double dz = m[6] * g.x + m[7] * g.y + m[8] * g.z;
+    const healpix::Vec3 d = healpix::rotated(m, healpix::pixel_centre(nside, 2 * log2_ns, p, SinCos{}));
     Tap t;
-    const double dmax = 1.7976931348623157e308;  // a NaN fails every comparison
-    t.ok = fabs(dx) <= dmax && fabs(dy) <= dmax && fabs(dz) <= dmax;
+    t.ok = healpix::all_finite(d);
     if (!t.ok) return t;
     const double twopi = 2.0 * M_PI;
-    const double th = atan2_finite(sqrt(dx * dx + dy * dy), dz);  // hypot, for components far from over- and underflow
-    double ph = atan2_finite(dy, dx);
-    if (ph >= 0.0) {  // HEALPix fmodulo(phi, 2 pi)
-        if (ph >= twopi) ph = fmod(ph, twopi);
-    } else {
-        ph = fmod(ph, twopi) + twopi;
-        if (ph == twopi) ph = 0.0;
-    }
+    const double th = atan2_finite(sqrt(d.x * d.x + d.y * d.y), d.z);  // hypot, for components far from over- and underflow
+    const double ph = healpix::fmodulo_twopi(atan2_finite(d.y, d.x));
     const double x = ph * (double)width / twopi - 0.5, y = th * (double)height / M_PI - 0.5;
     // x in [-0.5, W - 0.5] and y in [-0.5, H - 0.5] (the upper ends by rounding only), so the floors fit int32; every column goes
     // through the non-negative modulo and every row through the clamp, so the offsets lie in [0, H W) whatever the floors are

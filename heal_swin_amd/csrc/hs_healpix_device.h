@@ -1,7 +1,9 @@
 // HEALPix geometry evaluated per pixel, one copy for the device kernels and the host loops that restate them
-// (projection_aug.hip, hp_rotate.hip): the centre of a nested pixel as a unit vector, and HEALPix's get_interpol of a rotated
-// pixel centre in nested order.  Every function is __host__ __device__ (the macros are empty in a plain C++ translation unit),
-// float64, without FMA contraction, so that the host entry point runs the statements of the kernel.
+// (projection_aug.hip, hp_rotate.hip, hp_ensemble.hip, hs_erp_device.h): the centre of a nested pixel as a unit vector, its
+// rotation d = M g with the finiteness test and the longitude reduction every resampler applies to d, HEALPix's get_interpol of
+// a rotated pixel centre in nested order, and the coverage test of a source index.  Every function is __host__ __device__ (the
+// macros are empty in a plain C++ translation unit), float64, without FMA contraction, so that the host entry point runs the
+// statements of the kernel.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -84,6 +86,32 @@ HS_HD Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p, SinCos sc) {
 
 HS_HD Vec3 pixel_centre(int64_t nside, int log2_npface, int64_t p) { return pixel_centre(nside, log2_npface, p, LibmSinCos{}); }
 
+// d = M g, M nine row-major doubles
+HS_HD Vec3 rotated(const double* m, const Vec3& g) {
+    return {m[0] * g.x + m[1] * g.y + m[2] * g.z, m[3] * g.x + m[4] * g.y + m[5] * g.z, m[6] * g.x + m[7] * g.y + m[8] * g.z};
+}
+
+HS_HD bool all_finite(const Vec3& d) {
+    const double dmax = 1.7976931348623157e308;  // a NaN fails every comparison
+    return fabs(d.x) <= dmax && fabs(d.y) <= dmax && fabs(d.z) <= dmax;
+}
+
+// HEALPix fmodulo(phi, 2 pi): a longitude in [0, 2 pi)
+HS_HD double fmodulo_twopi(double ph) {
+    const double twopi = 2.0 * M_PI;
+    if (ph >= 0.0) {
+        if (ph >= twopi) ph = fmod(ph, twopi);
+    } else {
+        ph = fmod(ph, twopi) + twopi;
+        if (ph == twopi) ph = 0.0;
+    }
+    return ph;
+}
+
+// a source index is covered iff it names one of the npix pixels the map holds: the base pixels it lacks, and the -1 of a
+// non-finite matrix, are not
+HS_HD bool covered(int32_t idx, int64_t npix) { return (uint64_t)(int64_t)idx < (uint64_t)npix; }
+
 // T_Healpix_Base::get_ring_info2 without the first pixel: pixel count, centre colatitude and phase shift of ring 1 .. 4 nside - 1
 HS_HD void ring_info(int64_t ns, int64_t ring, int64_t& nr, double& th, bool& shifted) {
     const double fact2 = 4.0 / (double)(12 * ns * ns), fact1 = (double)(ns << 1) * fact2;
@@ -163,27 +191,16 @@ struct RotatedInterp {
 HS_HD RotatedInterp rotated_interp(int64_t nside, const double* m, int64_t p) {
     const int log2_ns = __builtin_ctzll((unsigned long long)nside);
     const int64_t ns = nside, nl4 = 4 * ns;
-    const Vec3 g = pixel_centre(ns, 2 * log2_ns, p);
-    const double dx = m[0] * g.x + m[1] * g.y + m[2] * g.z;
-    const double dy = m[3] * g.x + m[4] * g.y + m[5] * g.z;
-    const double dz = m[6] * g.x + m[7] * g.y + m[8] * g.z;
+    const Vec3 d = rotated(m, pixel_centre(ns, 2 * log2_ns, p));
     RotatedInterp out;
-    const double dmax = 1.7976931348623157e308;  // a NaN fails every comparison
-    if (!(fabs(dx) <= dmax && fabs(dy) <= dmax && fabs(dz) <= dmax)) {
+    if (!all_finite(d)) {
         for (int k = 0; k < 4; ++k) out.pix[k] = -1, out.wgt[k] = 0.0;
         out.nearest = -1;
         return out;
     }
-    const double twopi = 2.0 * M_PI;
-    const double r = hypot(dx, dy);
-    const double t = (r == 0.0 && dz == 0.0) ? 0.0 : atan2(r, dz);
-    double ph = atan2(dy, dx);
-    if (ph >= 0.0) {  // HEALPix fmodulo(phi, 2 pi)
-        if (ph >= twopi) ph = fmod(ph, twopi);
-    } else {
-        ph = fmod(ph, twopi) + twopi;
-        if (ph == twopi) ph = 0.0;
-    }
+    const double r = hypot(d.x, d.y);
+    const double t = (r == 0.0 && d.z == 0.0) ? 0.0 : atan2(r, d.z);
+    const double ph = fmodulo_twopi(atan2(d.y, d.x));
     const double z = cos(t), az = fabs(z);
     int64_t ir1;  // T_Healpix_Base::ring_above
     if (az <= 2.0 / 3.0) {
@@ -239,6 +256,16 @@ HS_HD RotatedInterp rotated_interp(int64_t nside, const double* m, int64_t p) {
     if (w3 > wbest) best = out.pix[3], wbest = w3;
     out.nearest = best;
     return out;
+}
+
+// r as entry (b, i) of pix, wgt [batch, 4, count] and nearest [batch, count]
+HS_HD void store_interp(const RotatedInterp& r, int64_t b, int64_t i, int64_t count, int32_t* pix, double* wgt, int32_t* nearest) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pix[(b * 4 + k) * count + i] = r.pix[k];
+        wgt[(b * 4 + k) * count + i] = r.wgt[k];
+    }
+    nearest[b * count + i] = r.nearest;
 }
 
 }  // namespace healpix

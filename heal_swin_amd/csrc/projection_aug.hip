@@ -13,16 +13,17 @@
 // table (arccos / cos phi / sin phi of the angles) to rounding, not bit for bit: the exact path is the resident table.
 // One thread per (sample, pixel): bound by float64 transcendental throughput (sincos, hypot, atan2, two divisions), 16 B out.
 #include "hs_device.h"
-#include "hs_healpix_device.h"  // pixel_centre
+#include "hs_healpix_device.h"  // pixel_centre, rotated
+#include "hs_sphere_args.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 using hs::healpix::pixel_centre;
+using hs::healpix::rotated;
 using hs::healpix::Vec3;
-
-constexpr int kThreads = 256;
+using namespace hs::sphere;
 
 // grid (pixel blocks, samples)
 __global__ void __launch_bounds__(kThreads) hp_rotated_coords_kernel(int64_t nside, int log2_npface, int64_t first_pix, int64_t count,
@@ -31,14 +32,10 @@ __global__ void __launch_bounds__(kThreads) hp_rotated_coords_kernel(int64_t nsi
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
     const int64_t b = blockIdx.y;
-    const double* m = rot + 9 * b;  // uniform over the workgroup
-    const Vec3 g = pixel_centre(nside, log2_npface, first_pix + i);
-    const double dx = m[0] * g.x + m[1] * g.y + m[2] * g.z;
-    const double dy = m[3] * g.x + m[4] * g.y + m[5] * g.z;
-    const double dz = m[6] * g.x + m[7] * g.y + m[8] * g.z;
-    const double r = hypot(dx, dy);
-    const double theta = atan2(r, dz);
-    const double cphi = r == 0.0 ? 1.0 : dx / r, sphi = r == 0.0 ? 0.0 : dy / r;
+    const Vec3 d = rotated(rot + 9 * b, pixel_centre(nside, log2_npface, first_pix + i));  // the matrix is uniform over the workgroup
+    const double r = hypot(d.x, d.y);
+    const double theta = atan2(r, d.z);
+    const double cphi = r == 0.0 ? 1.0 : d.x / r, sphi = r == 0.0 ? 0.0 : d.y / r;
     double rho = 0.0, tp = 1.0;
 #pragma unroll
     for (int o = 0; o < 8; ++o) {
@@ -55,12 +52,12 @@ extern "C" {
 
 int hs_hp_rotated_coords(int nside, int64_t first_pix, int64_t count, const hs_fisheye_camera* cam, const double* rot, int batch,
                          double* u, double* v, void* stream) {
-    HS_CHECK_ARG(nside >= 1 && hs::is_pow2(nside), "nside must be a power of two, got %d", nside);
+    const char* who = "hs_hp_rotated_coords";
+    if (int st = check_nside(who, nside, 0, /*int32_indices=*/false)) return st;  // u, v are tables of doubles
     HS_CHECK_ARG(nside <= (1 << 29), "nside %d above HEALPix's limit 2^29", nside);
-    const int64_t npix = 12 * (int64_t)nside * nside;
-    HS_CHECK_ARG(first_pix >= 0 && count >= 0 && first_pix <= npix && count <= npix - first_pix, "pixel range outside [0, 12 nside^2)");
+    if (int st = check_pixel_range(who, nside, first_pix, count)) return st;
     HS_CHECK_ARG(count <= (int64_t)INT32_MAX * kThreads, "too many pixels for one launch");
-    HS_CHECK_ARG(batch > 0 && batch <= 65535, "batch must be in [1, 65535], got %d", batch);
+    if (int st = check_batch(who, batch)) return st;
     HS_CHECK_ARG(cam, "null pointer");
     HS_CHECK_ARG(cam->poly_order >= 1 && cam->poly_order <= 8, "poly_order must be in [1, 8], got %d", cam->poly_order);
     HS_CHECK_ARG(cam->width > 0 && cam->height > 0, "image size must be positive");
@@ -68,8 +65,8 @@ int hs_hp_rotated_coords(int nside, int64_t first_pix, int64_t count, const hs_f
     HS_CHECK_ARG(rot && u && v, "null pointer");
     int log2_npface = 0;
     while (((int64_t)1 << log2_npface) < (int64_t)nside * nside) ++log2_npface;
-    hipLaunchKernelGGL(hp_rotated_coords_kernel, dim3((unsigned)((count + kThreads - 1) / kThreads), (unsigned)batch), dim3(kThreads), 0,
-                       (hipStream_t)stream, (int64_t)nside, log2_npface, first_pix, count, *cam, rot, u, v);
+    hipLaunchKernelGGL(hp_rotated_coords_kernel, pixel_grid(count, batch), dim3(kThreads), 0, (hipStream_t)stream, (int64_t)nside,
+                       log2_npface, first_pix, count, *cam, rot, u, v);
     HS_LAUNCH_CHECK("hp_rotated_coords");
     return HS_OK;
 }

@@ -31,9 +31,8 @@ import torch
 
 from ._lib import (HS_DEPTH_STATS_WORDS, HS_DT_1000_BKG, HS_DT_AFFINE, HS_DT_INV, HS_DT_INVERSE, HS_DT_LOG, HS_DT_NONE,
                    HS_DT_ZERO_BKG, HS_HISTOGRAM_MAX_BINS, check, lib, ptr, stream_ptr)
-from .evaluation import _device
-from .projection import (_coords, _device_u8, _per_sample_count, _pole_rotation, _rotated_coords, camera_record, hp_grid,
-                         project_s2_points_to_img)
+from ._sphere_args import _resolved
+from .projection import _FisheyeProjector, _sample, _with_used_size, project_s2_points_to_img
 
 IMG_KEY, MASK_KEY = "hp_img", "hp_mask"
 TRANSFORMS = {None: HS_DT_NONE, "None": HS_DT_NONE, "log": HS_DT_LOG, "inv": HS_DT_INV}
@@ -44,23 +43,7 @@ NORMALIZATIONS = (None, "None", "standardize", "min-max")
 def project_depth_s2_points_to_img(theta, phi, cal_info, rotate_pole=False, used_size=None):
     """Float pixel coordinates (u along the width, v along the height) of spherical points; used_size = (height, width) of
     the image actually sampled replaces the calibration's size."""
-    if used_size is not None:
-        intr = dict(cal_info["intrinsic"], height=int(used_size[0]), width=int(used_size[1]))
-        cal_info = dict(cal_info, intrinsic=intr)
-    return project_s2_points_to_img(theta, phi, cal_info, rotate_pole)
-
-
-def _device_f32(t, ndim, what):
-    if not torch.is_tensor(t):
-        t = torch.from_numpy(np.ascontiguousarray(t))
-    if t.dtype != torch.float32:
-        raise TypeError(f"{what} must be float32, got {t.dtype}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} must be a GPU tensor: the sampling runs in the HIP kernels only (no CPU path)")
-    lead = ndim - t.dim()
-    if lead not in (0, 1):
-        raise ValueError(f"{what}: expected {ndim - 1} or {ndim} dimensions, got {t.dim()}")
-    return (t[None] if lead else t).contiguous(), bool(lead)
+    return project_s2_points_to_img(theta, phi, _with_used_size(cal_info, used_size), rotate_pole)
 
 
 def sample_bilinear_f32(img, rx, ry, per_sample=False):
@@ -68,38 +51,18 @@ def sample_bilinear_f32(img, rx, ry, per_sample=False):
     W -> float32 [(B,) C, n]; NaN where a coordinate is not finite, 0 at integer coordinates (the reference's floor / ceil).
     per_sample=False: one coordinate table for the whole batch (rx, ry of any shape are flattened).  per_sample=True: rx, ry
     are [B, n] and sample b reads row b (`hs_sample_bilinear_u8_f32_per_sample`, the same kernel and arithmetic)."""
-    n = _per_sample_count(img, 4, rx, ry) if per_sample else None
-    img, squeeze = _device_u8(img, 4, "img")
-    rx, ry = _coords(rx, img.device), _coords(ry, img.device)
-    if rx.shape != ry.shape:
-        raise ValueError("rx and ry must have the same shape")
-    n = rx.numel() if n is None else n
-    b, c, h, w = img.shape
-    out = torch.empty((b, c, n), dtype=torch.float32, device=img.device)
-    fn = lib.hs_sample_bilinear_u8_f32_per_sample if per_sample else lib.hs_sample_bilinear_u8_f32
-    check(fn(ptr(img), b, c, h, w, ptr(rx), ptr(ry), n, ptr(out), stream_ptr(img.device)), "hs_sample_bilinear_u8_f32")
-    return out[0] if squeeze else out
+    return _sample("sample_bilinear_u8_f32", img, 4, torch.uint8, "img", rx, ry, per_sample, torch.float32)
 
 
 def sample_depth(depth, rx, ry, background=0.0, per_sample=False):
     """`sample_mask(depth, rx, ry, background)`: depth float32 [H, W] or [B, H, W] on the GPU -> float32 [(B,) n], the nearest
     pixel's value (round half to even), `background` outside the image.  per_sample as in sample_bilinear_f32
     (`hs_sample_nearest_f32_per_sample`)."""
-    n = _per_sample_count(depth, 3, rx, ry) if per_sample else None
-    depth, squeeze = _device_f32(depth, 3, "depth")
-    rx, ry = _coords(rx, depth.device), _coords(ry, depth.device)
-    if rx.shape != ry.shape:
-        raise ValueError("rx and ry must have the same shape")
-    n = rx.numel() if n is None else n
-    b, h, w = depth.shape
-    out = torch.empty((b, n), dtype=torch.float32, device=depth.device)
-    fn = lib.hs_sample_nearest_f32_per_sample if per_sample else lib.hs_sample_nearest_f32
-    check(fn(ptr(depth), b, h, w, ptr(rx), ptr(ry), n, float(np.float32(background)), ptr(out), stream_ptr(depth.device)),
-          "hs_sample_nearest_f32")
-    return out[0] if squeeze else out
+    return _sample("sample_nearest_f32", depth, 3, torch.float32, "depth", rx, ry, per_sample, torch.float32,
+                   (float(np.float32(background)),))
 
 
-class HPDepthProjector:
+class HPDepthProjector(_FisheyeProjector):
     """project_depth_dataset_hp for the frames of one camera: `proj(imgs, depths)` -> (hp_img float32 [B, 3, Npix], hp_mask
     float32 [B, Npix]) on the GPU.  The coordinate table is built once on the host and stays on the device.
 
@@ -109,30 +72,13 @@ class HPDepthProjector:
     resident table, the reference's bytes.  Identity rotations go through the device arithmetic and agree with it to coordinate
     rounding only (about 1e-12 px), not bit for bit."""
 
-    def __init__(self, cal_info, nside, base_pix=8, rotate_pole=False, s2_bkgd_class=0, used_size=None, device="cuda"):
-        self.nside, self.base_pix = int(nside), int(base_pix)
-        self.s2_bkgd_class = float(s2_bkgd_class)
-        theta, phi = hp_grid(self.nside, self.base_pix)
-        u, v = project_depth_s2_points_to_img(theta, phi, cal_info, rotate_pole, used_size)
-        self.device = torch.device(device)
-        self.u, self.v = _coords(u, self.device), _coords(v, self.device)
-        self._cam = camera_record(cal_info, used_size)
-        self._pole = torch.from_numpy(_pole_rotation(cal_info)).to(self.device) if rotate_pole else None
+    _sample_frame, _sample_nearest = staticmethod(sample_bilinear_f32), staticmethod(sample_depth)
 
-    @property
-    def npix(self):
-        return self.u.numel()
+    def __init__(self, cal_info, nside, base_pix=8, rotate_pole=False, s2_bkgd_class=0, used_size=None, device="cuda"):
+        super().__init__(cal_info, nside, base_pix, rotate_pole, float(s2_bkgd_class), used_size, device)
 
     def proj(self, imgs, depths=None, rotations=None):
-        if rotations is None:
-            u, v, per_sample = self.u, self.v, False
-        else:
-            u, v = _rotated_coords(self.nside, self.base_pix, self._cam, rotations, self._pole, self.device)
-            per_sample = True
-        hp_img = sample_bilinear_f32(imgs, v, u, per_sample)
-        if depths is None:
-            return hp_img
-        return hp_img, sample_depth(depths, v, u, self.s2_bkgd_class, per_sample)
+        return self._proj(imgs, depths, rotations)
 
     __call__ = proj
 
@@ -306,7 +252,7 @@ class DepthStatsAccumulator:
         self.use_masking = bool(use_masking)
         if torch.device(device).type != "cuda":
             raise RuntimeError("DepthStatsAccumulator runs on the GPU only (HIP kernels, no CPU path)")
-        self.device = _device(device)
+        self.device = _resolved(device)
         self.state = torch.from_numpy(_initial_state()).to(self.device)
 
     def reset(self):
@@ -380,7 +326,7 @@ class DepthHistogram:
         self.bin_edges = np.histogram_bin_edges(np.empty(0, np.float64), self.bins, (lo, hi)).astype(np.float64, copy=False)
         if torch.device(device).type != "cuda":
             raise RuntimeError("DepthHistogram runs on the GPU only (HIP kernel, no CPU path)")
-        self.device = _device(device)
+        self.device = _resolved(device)
         self._edges = torch.from_numpy(self.bin_edges).to(self.device)
         self.counts = torch.zeros(self.bins, dtype=torch.int64, device=self.device)
 

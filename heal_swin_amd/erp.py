@@ -28,11 +28,11 @@ import numpy as np
 import torch
 
 from ._lib import HS_F32, HS_U8, check, lib, np_ptr, ptr, stream_ptr
+from ._sphere_args import (MAX_CHANNELS, MAX_NSIDE, _any_given, _check_base_pix, _check_batch, _check_nside, _device_planes,  # noqa: F401
+                           _dtype_name, _fills, _gather_planes, _matmul3, _results, _rotation_batch, _same_batch)
 from .evaluation import HPBackProjector
-from .projection import _rotation_batch
 
-MAX_NSIDE = 8192  # nside << supersample: 12 nside^2 nested indices as int32
-MAX_CHANNELS = 16
+_NAMES = ("imgs", "masks", "depth")
 
 
 def erp_grid(height, width):
@@ -67,19 +67,10 @@ def _layout(layout):
 
 
 def _check_grid(nside, base_pix, supersample):
-    nside, base_pix, supersample = int(nside), int(base_pix), int(supersample)
+    supersample = int(supersample)
     if supersample not in (0, 1, 2):
         raise ValueError(f"supersample must be 0, 1 or 2, got {supersample}")
-    if nside < 1 or nside & (nside - 1) or nside << supersample > MAX_NSIDE:
-        raise ValueError(f"nside must be a power of two with nside << supersample <= {MAX_NSIDE}, got {nside} << {supersample}")
-    if not 1 <= base_pix <= 12:
-        raise ValueError(f"base_pix must be in [1, 12], got {base_pix}")
-    return nside, base_pix, supersample
-
-
-def _dtype_name(dtype):
-    """'uint8', 'float32', ... of a torch or numpy dtype"""
-    return str(dtype).replace("torch.", "")
+    return _check_nside(nside, supersample), _check_base_pix(base_pix), supersample
 
 
 def _frame_kind(dtype):
@@ -89,21 +80,10 @@ def _frame_kind(dtype):
     return kind
 
 
-def _panorama(t, ndim, what):
-    """A plane with its batch dimension, plus whether that was added (rank checked without touching the device)."""
-    if not torch.is_tensor(t):
-        t = torch.from_numpy(np.ascontiguousarray(t))
-    lead = ndim - t.dim()
-    if lead not in (0, 1):
-        raise ValueError(f"{what}: expected {ndim - 1} or {ndim} dimensions, got {t.dim()}")
-    return (t[None] if lead else t), bool(lead)
-
-
 def _check_planes(planes, batch):
-    """planes = [imgs, masks, depth] with batch dimensions (None where not given): dtypes, one panorama size, one batch."""
+    """planes = [imgs, masks, depth] with batch dimensions (None where not given, not all of them): dtypes, one panorama size, the
+    batch."""
     img, mask, depth = planes
-    if img is None and mask is None and depth is None:
-        raise ValueError("give at least one of imgs, masks, depth")
     if img is not None:
         _frame_kind(img.dtype)
         if not 1 <= img.shape[1] <= MAX_CHANNELS:
@@ -118,16 +98,8 @@ def _check_planes(planes, batch):
     height, width = sizes.pop()
     if height < 1 or width < 1 or height * width >= 1 << 31:
         raise ValueError(f"the panorama must be at least 1 x 1 with height * width < 2^31, got {height} x {width}")
-    for t, what in zip(planes, ("imgs", "masks", "depth")):
-        if t is not None and t.shape[0] != batch:
-            raise ValueError(f"{what} holds {t.shape[0]} samples, expected {batch}")
-    if not 1 <= batch <= 65535:
-        raise ValueError(f"batch must be in [1, 65535], got {batch}")
+    _check_batch(batch)
     return height, width
-
-
-def _resolved(device):
-    return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device
 
 
 class ERPProjector:
@@ -150,10 +122,7 @@ class ERPProjector:
 
     def __init__(self, nside, base_pix=12, layout=None, s2_bkgd_class=0, supersample=0, device="cuda", depth_fill=None):
         self.nside, self.base_pix, self.supersample = _check_grid(nside, base_pix, supersample)
-        self.s2_bkgd_class = int(s2_bkgd_class)
-        if not 0 <= self.s2_bkgd_class <= 255:
-            raise ValueError(f"s2_bkgd_class must be in [0, 255] (uint8 labels), got {s2_bkgd_class}")
-        self.depth_fill = float(s2_bkgd_class) if depth_fill is None else float(depth_fill)
+        self.s2_bkgd_class, self.depth_fill = _fills(s2_bkgd_class, depth_fill)
         self.device = torch.device(device)  # "cpu" serves `matrices` alone: `proj` takes GPU tensors only
         layout = _layout(layout)
         self._layout = None if layout is None else torch.from_numpy(layout).to(self.device)
@@ -169,39 +138,22 @@ class ERPProjector:
         else:
             m = _rotation_batch(rotations, self.device)
         if self._layout is not None:
-            m = (self._layout[None, :, :, None] * m[:, None, :, :]).sum(2)  # L A_b, elementwise: the same rounding on every device
+            m = _matmul3(self._layout, m)  # L A_b
         return m.contiguous()
 
     def proj(self, imgs=None, masks=None, depth=None, rotations=None):
-        planes, squeezes = [], set()
-        for t, ndim, what in ((imgs, 4, "imgs"), (masks, 3, "masks"), (depth, 3, "depth")):
-            if t is None:
-                planes.append(None)
-                continue
-            t, squeeze = _panorama(t, ndim, what)
-            planes.append(t)
-            squeezes.add(squeeze)
-        if len(squeezes) > 1:
-            raise ValueError("either every input has a batch dimension or none has")
-        batch = next((t.shape[0] for t in planes if t is not None), 0)
+        planes, squeeze, batch = _gather_planes(((imgs, 4, None, _NAMES[0]), (masks, 3, None, _NAMES[1]), (depth, 3, None, _NAMES[2])))
         height, width = _check_planes(planes, batch)
         if rotations is not None and _rotation_batch(rotations).shape[0] != batch:
             raise ValueError(f"rotations holds {_rotation_batch(rotations).shape[0]} samples, the inputs {batch}")
-        for t, what in zip(planes, ("imgs", "masks", "depth")):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError(f"{what} must be a GPU tensor: the projection runs in the HIP kernel only (the host loop is erp_to_hp_host)")
-            if t is not None and t.device != _resolved(self.device):
-                raise RuntimeError(f"{what} is on {t.device}, the projector on {self.device}")
-        img, mask, dep = planes = [None if t is None else t.contiguous() for t in planes]
+        (img, mask, dep), outs = _device_planes(planes, _NAMES, self.device, "the projector", self.npix, 2,
+                                                "the host loop is erp_to_hp_host")
         m = self.matrices(rotations, batch)
         channels = 0 if img is None else img.shape[1]
-        outs = [None if t is None else torch.empty(t.shape[:-2] + (self.npix,), dtype=t.dtype, device=t.device) for t in planes]
         check(lib.hs_erp_to_hp(self.nside, self.npix, ptr(m), batch, height, width, self.supersample, ptr(img),
                                HS_U8 if img is None else _frame_kind(img.dtype), channels, ptr(outs[0]), ptr(mask), ptr(outs[1]),
                                self.s2_bkgd_class, ptr(dep), ptr(outs[2]), self.depth_fill, stream_ptr(self.device)), "hs_erp_to_hp")
-        squeeze = squeezes.pop()
-        res = tuple(o[0] if squeeze else o for o in outs if o is not None)
-        return res[0] if len(res) == 1 else res
+        return _results(outs, squeeze)
 
     __call__ = proj
 
@@ -213,9 +165,11 @@ def erp_to_hp_host(nside, rotations, imgs=None, masks=None, depth=None, base_pix
     nside, base_pix, supersample = _check_grid(nside, base_pix, supersample)
     m = np.ascontiguousarray(_rotation_batch(rotations).detach().cpu().numpy(), dtype=np.float64)
     planes = [None if t is None else np.ascontiguousarray(t) for t in (imgs, masks, depth)]
-    for t, ndim, what in zip(planes, (4, 3, 3), ("imgs", "masks", "depth")):
+    _any_given(planes, _NAMES)
+    for t, ndim, what in zip(planes, (4, 3, 3), _NAMES):
         if t is not None and t.ndim != ndim:
             raise ValueError(f"{what}: expected {ndim} dimensions, got {t.ndim}")
+    _same_batch(planes, _NAMES, m.shape[0])
     height, width = _check_planes(planes, m.shape[0])
     img, mask, dep = planes
     npix = base_pix * nside * nside
@@ -224,8 +178,7 @@ def erp_to_hp_host(nside, rotations, imgs=None, masks=None, depth=None, base_pix
                                 HS_U8 if img is None else _frame_kind(img.dtype), 0 if img is None else img.shape[1], np_ptr(outs[0]),
                                 np_ptr(mask), np_ptr(outs[1]), int(s2_bkgd_class), np_ptr(dep), np_ptr(outs[2]), float(depth_fill)),
           "hs_erp_to_hp_host")
-    res = tuple(o for o in outs if o is not None)
-    return res[0] if len(res) == 1 else res
+    return _results(outs, False)
 
 
 class ERPBackProjector(HPBackProjector):

@@ -36,6 +36,7 @@ import numpy as np
 import torch
 
 from ._lib import HS_BF16, HS_F32, HS_PRED_LABELS, HS_PRED_ROWS16, check, lib, np_ptr, ptr, stream_ptr
+from ._sphere_args import _resolved as _device  # noqa: F401  (the evaluation modules import it from here)
 from .projection import rot_grid
 
 MAX_CLASSES = 64
@@ -130,11 +131,6 @@ def hp_nearest_pix_idcs(nside, theta, phi):
 
 
 # ------------------------------------------------------------------ device side
-def _device(device):
-    d = torch.device(device)
-    return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
-
-
 def _pred_args(pred, npix, device):
     """(pred_kind, n_classes, batch, (stride_b, stride_k, stride_p), tensor) of logits [B, K, Npix] or labels [B, Npix]."""
     if not torch.is_tensor(pred) or pred.device != device:

@@ -19,9 +19,10 @@ import numpy as np
 import torch
 
 from ._lib import HS_BF16, HS_ENSEMBLE_LOGIT, HS_ENSEMBLE_PROB, HS_F32, HS_PRED_ROWS16, check, lib, np_ptr, ptr, stream_ptr
+from ._sphere_args import _check_batch, _check_nside, _fills, _resolved, _rotation_batch
 from .evaluation import _pred_args
-from .hp_rotate import HPRotator, _check_grid, _resolved
-from .projection import _pole_rotation, _rotation_batch
+from .hp_rotate import HPRotator
+from .projection import _pole_rotation
 
 MAX_CLASSES = 16
 MODES = {"prob": HS_ENSEMBLE_PROB, "logit": HS_ENSEMBLE_LOGIT}
@@ -54,7 +55,7 @@ def add_seg_host(nside, base_pix, pred, rot=None, valid=None, mode="prob", acc=N
     rows16=True promises HS_PRED_ROWS16 rows.  rot = M^T [B, 3, 3] or None (the unrotated member), valid uint8 [B, Npix] or None.
     acc / wsum None: a first member (new arrays); else they are added to in place (stored into with accumulate=False).  Returns
     (acc float32 [B, Npix, KP], wsum float32 [B, Npix])."""
-    nside, _, _ = _check_grid(nside, 0, 0, 1)
+    nside = _check_nside(nside)
     npix = int(base_pix) * nside * nside
     kind, (sb, sk, sp) = _host_pred(pred, 3, npix)
     b, k, _ = pred.shape
@@ -72,7 +73,7 @@ def add_seg_host(nside, base_pix, pred, rot=None, valid=None, mode="prob", acc=N
 
 def add_depth_host(nside, base_pix, pred, rot=None, valid=None, acc=None, wsum=None, accumulate=None):
     """`hs_hp_ensemble_add_depth_host`: pred numpy [B, Npix]; otherwise as add_seg_host.  Returns (acc, wsum) float32 [B, Npix]."""
-    nside, _, _ = _check_grid(nside, 0, 0, 1)
+    nside = _check_nside(nside)
     npix = int(base_pix) * nside * nside
     kind, (sb, sp) = _host_pred(pred, 2, npix)
     b = pred.shape[0]
@@ -114,9 +115,7 @@ class HPRotationEnsemble:
     def __init__(self, nside, base_pix=8, cal_info=None, rotate_pole=False, s2_bkgd_class=0, mode="prob", min_weight=1e-3, device="cuda"):
         self._rotator = HPRotator(nside, base_pix, cal_info=cal_info, rotate_pole=rotate_pole, s2_bkgd_class=0, device=device)
         self.nside, self.base_pix, self.device = self._rotator.nside, self._rotator.base_pix, self._rotator.device
-        self.s2_bkgd_class = int(s2_bkgd_class)
-        if not 0 <= self.s2_bkgd_class <= 255:
-            raise ValueError(f"s2_bkgd_class must be in [0, 255] (uint8 class ids), got {s2_bkgd_class}")
+        self.s2_bkgd_class, _ = _fills(s2_bkgd_class, None)
         if mode not in MODES:
             raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
         self.mode, self.min_weight = mode, float(min_weight)
@@ -165,8 +164,7 @@ class HPRotationEnsemble:
                 raise ValueError(f"channel {channel} outside the {pred.shape[1]} channels of pred")
             pred = pred[:, int(channel)]
         batch = pred.shape[0]
-        if not 1 <= batch <= 65535:
-            raise ValueError(f"batch must be in [1, 65535], got {batch}")
+        _check_batch(batch)
         k = pred.shape[1] if task == "seg" else 0
         if task == "seg" and not 1 <= k <= MAX_CLASSES:
             raise ValueError(f"the ensemble kernels support 1 .. {MAX_CLASSES} classes, got {k}")

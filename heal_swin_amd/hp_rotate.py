@@ -22,22 +22,18 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, np_ptr, ptr, stream_ptr
-from .projection import _pole_rotation, _rotation_batch
+from ._sphere_args import (MAX_CHANNELS, MAX_NSIDE, _check_base_pix, _check_batch, _check_nside, _device_planes, _fills,  # noqa: F401
+                           _gather_planes, _matmul3, _results, _rotation_batch)
+from .projection import _pole_rotation
 
-MAX_NSIDE = 8192  # 12 nside^2 nested indices as int32
-MAX_CHANNELS = 16
 
-
-def _check_grid(nside, first_pix, count, batch):
-    nside, first_pix = int(nside), int(first_pix)
-    if nside < 1 or nside & (nside - 1) or nside > MAX_NSIDE:
-        raise ValueError(f"nside must be a power of two in [1, {MAX_NSIDE}], got {nside}")
+def _check_range(nside, first_pix, count, batch):
+    nside, first_pix = _check_nside(nside), int(first_pix)
     npix = 12 * nside * nside
     count = npix - first_pix if count is None else int(count)
     if first_pix < 0 or count < 0 or first_pix + count > npix:
         raise ValueError(f"pixels [{first_pix}, {first_pix + count}) outside [0, {npix}) for nside {nside}")
-    if batch > 65535:
-        raise ValueError(f"batch must be in [1, 65535], got {batch}")
+    _check_batch(batch)
     return nside, first_pix, count
 
 
@@ -48,7 +44,7 @@ def rotated_interp(nside, rotations, first_pix=0, count=None, device="cuda"):
     device tensor or a host array; any real matrix is accepted, a non-finite one gives -1 / 0 / -1 for its sample.  One launch,
     nothing synchronises with the host."""
     batch = _rotation_batch(rotations).shape[0]
-    nside, first_pix, count = _check_grid(nside, first_pix, count, batch)
+    nside, first_pix, count = _check_range(nside, first_pix, count, batch)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"rotated_interp runs in the HIP kernel only, got device {device} (the host loop is rotated_interp_host)")
@@ -66,28 +62,13 @@ def rotated_interp_host(nside, rotations, first_pix=0, count=None):
     m = _rotation_batch(rotations)
     m = np.ascontiguousarray(m.detach().cpu().numpy(), dtype=np.float64)
     batch = m.shape[0]
-    nside, first_pix, count = _check_grid(nside, first_pix, count, batch)
+    nside, first_pix, count = _check_range(nside, first_pix, count, batch)
     pix = np.empty((batch, 4, count), dtype=np.int32)
     wgt = np.empty((batch, 4, count), dtype=np.float64)
     nearest = np.empty((batch, count), dtype=np.int32)
     check(lib.hs_hp_rotated_interp_host(nside, first_pix, count, np_ptr(m), batch, np_ptr(pix), np_ptr(wgt), np_ptr(nearest)),
           "hs_hp_rotated_interp_host")
     return pix, wgt, nearest
-
-
-def _plane(t, dtype, ndim, npix, what):
-    """A map with its batch dimension, plus whether that was added: dtype, rank and pixel count, checked without touching the
-    device."""
-    if not torch.is_tensor(t):
-        t = torch.from_numpy(np.ascontiguousarray(t))
-    if t.dtype != dtype:
-        raise TypeError(f"{what} must be {dtype}, got {t.dtype}")
-    lead = ndim - t.dim()
-    if lead not in (0, 1):
-        raise ValueError(f"{what}: expected {ndim - 1} or {ndim} dimensions, got {t.dim()}")
-    if t.shape[-1] != npix:
-        raise ValueError(f"{what} covers {t.shape[-1]} HEALPix pixels, expected {npix}")
-    return (t[None] if lead else t), bool(lead)
 
 
 class HPRotator:
@@ -106,15 +87,10 @@ class HPRotator:
     nothing is read on the host and only the outputs (and the [B, 3, 3] matrix temporaries) are allocated: capturable."""
 
     def __init__(self, nside, base_pix=8, cal_info=None, rotate_pole=False, s2_bkgd_class=0, depth_fill=None, device="cuda"):
-        self.nside, _, _ = _check_grid(nside, 0, 0, 1)
-        self.base_pix, self.s2_bkgd_class = int(base_pix), int(s2_bkgd_class)
-        if not 1 <= self.base_pix <= 12:
-            raise ValueError(f"base_pix must be in [1, 12], got {base_pix}")
-        if not 0 <= self.s2_bkgd_class <= 255:
-            raise ValueError(f"s2_bkgd_class must be in [0, 255] (uint8 labels), got {s2_bkgd_class}")
+        self.nside, self.base_pix = _check_nside(nside), _check_base_pix(base_pix)
+        self.s2_bkgd_class, self.depth_fill = _fills(s2_bkgd_class, depth_fill)
         if rotate_pole and cal_info is None:
             raise ValueError("rotate_pole=True needs the cal_info the dataset was projected with")
-        self.depth_fill = float(s2_bkgd_class) if depth_fill is None else float(depth_fill)
         self.device = torch.device(device)  # "cpu" serves `matrices` alone: `rot` takes GPU tensors only
         self._pole = torch.from_numpy(_pole_rotation(cal_info)).to(self.device) if rotate_pole else None
 
@@ -126,50 +102,27 @@ class HPRotator:
         """M_b = R^T A_b R, float64 [B, 3, 3] on the device (A itself without rotate_pole)."""
         m = _rotation_batch(rotations, self.device)
         if self._pole is not None:
-            m = (m[:, :, :, None] * self._pole[None, None, :, :]).sum(2)  # A_b R, elementwise: the same rounding on every device
-            m = (self._pole.t()[None, :, :, None] * m[:, None, :, :]).sum(2)  # R^T (A_b R)
+            m = _matmul3(self._pole.t(), _matmul3(m, self._pole))  # R^T (A_b R)
         return m.contiguous()
 
     def rot(self, hp_img=None, hp_mask=None, hp_depth=None, rotations=None):
         if rotations is None:
             raise ValueError("rotations=A [batch, 3, 3] is required (projection.random_rotations)")
-        batch = _rotation_batch(rotations).shape[0]
-        if hp_img is None and hp_mask is None and hp_depth is None:
-            raise ValueError("give at least one of hp_img, hp_mask, hp_depth")
-        planes, squeezes = [], set()
-        for t, dtype, ndim, what in ((hp_img, torch.uint8, 3, "hp_img"), (hp_mask, torch.uint8, 2, "hp_mask"),
-                                     (hp_depth, torch.float32, 2, "hp_depth")):
-            if t is None:
-                planes.append(None)
-                continue
-            t, squeeze = _plane(t, dtype, ndim, self.npix, what)
-            if t.shape[0] != batch:
-                raise ValueError(f"{what} holds {t.shape[0]} samples, rotations {batch}")
-            planes.append(t)
-            squeezes.add(squeeze)
-        if len(squeezes) != 1:
-            raise ValueError("either every map has a batch dimension or none has")
-        if batch > 65535:
-            raise ValueError(f"batch must be in [1, 65535], got {batch}")
+        names = ("hp_img", "hp_mask", "hp_depth")
+        planes, squeeze, batch = _gather_planes(((hp_img, 3, torch.uint8, names[0]), (hp_mask, 2, torch.uint8, names[1]),
+                                                 (hp_depth, 2, torch.float32, names[2])), _rotation_batch(rotations).shape[0])
+        for t, what in zip(planes, names):
+            if t is not None and t.shape[-1] != self.npix:
+                raise ValueError(f"{what} covers {t.shape[-1]} HEALPix pixels, expected {self.npix}")
+        _check_batch(batch)
         channels = 0 if planes[0] is None else planes[0].shape[1]
         if planes[0] is not None and not 1 <= channels <= MAX_CHANNELS:
             raise ValueError(f"hp_img must have 1 .. {MAX_CHANNELS} channels, got {channels}")
-        for t, what in zip(planes, ("hp_img", "hp_mask", "hp_depth")):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError(f"{what} must be a GPU tensor: the rotation runs in the HIP kernel only (no CPU path)")
-            if t is not None and t.device != _resolved(self.device):
-                raise RuntimeError(f"{what} is on {t.device}, the rotator on {self.device}")
-        img, mask, depth = planes = [None if t is None else t.contiguous() for t in planes]
+        (img, mask, depth), outs = _device_planes(planes, names, self.device, "the rotator", self.npix, 1)
         m = self.matrices(rotations)
-        outs = [None if t is None else torch.empty_like(t) for t in planes]
         check(lib.hs_hp_rotate(self.nside, self.npix, ptr(m), batch, ptr(img), channels, ptr(outs[0]), ptr(mask), ptr(outs[1]),
                                self.s2_bkgd_class, ptr(depth), ptr(outs[2]), self.depth_fill, stream_ptr(self.device)), "hs_hp_rotate")
-        squeeze = squeezes.pop()
-        res = tuple(o[0] if squeeze else o for o in outs if o is not None)
-        return res[0] if len(res) == 1 else res
+        return _results(outs, squeeze)
 
     __call__ = rot
 
-
-def _resolved(device):
-    return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device

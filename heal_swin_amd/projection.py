@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from ._lib import FisheyeCamera, check, lib, np_ptr, ptr, stream_ptr
+from ._sphere_args import _batched, _matmul3, _rotation_batch
 
 _EXT_REF = {"FV": (1.0, 0.0, 0.0), "RV": (-1.0, 0.0, 0.0), "MVL": (0.0, 1.0, 0.0), "MVR": (0.0, -1.0, 0.0)}
 
@@ -80,19 +81,6 @@ def project_s2_points_to_img(theta, phi, cal_info, rotate_pole=False):
     return u, v
 
 
-def _device_u8(t, ndim, what):
-    if not torch.is_tensor(t):
-        t = torch.from_numpy(np.ascontiguousarray(t))
-    if t.dtype != torch.uint8:
-        raise TypeError(f"{what} must be uint8 (the reference samples tv.io.read_image frames and class-id masks), got {t.dtype}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} must be a GPU tensor: the sampling runs in the HIP kernels only (no CPU path)")
-    lead = ndim - t.dim()
-    if lead not in (0, 1):
-        raise ValueError(f"{what}: expected {ndim - 1} or {ndim} dimensions, got {t.dim()}")
-    return (t[None] if lead else t).contiguous(), bool(lead)
-
-
 def _coords(r, device):
     if torch.is_tensor(r):
         return r.to(device=device, dtype=torch.float64).contiguous().reshape(-1)
@@ -109,36 +97,36 @@ def _per_sample_count(src, ndim, rx, ry):
     return sx[1]
 
 
+def _sample(name, src, ndim, dtype, what, rx, ry, per_sample, out_dtype, background=()):
+    """The four public samplers (two here, two in depth_data): src [(B,) ..., H, W] of `ndim` dimensions with its batch one, checked,
+    then `hs_<name>` or `hs_<name>_per_sample` with `background` between n and the output -> out_dtype [(B,) ..., n]."""
+    n = _per_sample_count(src, ndim, rx, ry) if per_sample else None
+    src, squeeze = _batched(src, ndim, what, dtype)
+    if n is None and int(np.prod(np.shape(rx))) != int(np.prod(np.shape(ry))):
+        raise ValueError("rx and ry must have the same shape")
+    if not src.is_cuda:
+        raise RuntimeError(f"{what} must be a GPU tensor: the sampling runs in the HIP kernels only (no CPU path)")
+    src = src.contiguous()
+    rx, ry = _coords(rx, src.device), _coords(ry, src.device)
+    n = rx.numel() if n is None else n
+    out = torch.empty(src.shape[:-2] + (n,), dtype=out_dtype, device=src.device)
+    fn = getattr(lib, f"hs_{name}_per_sample" if per_sample else f"hs_{name}")
+    check(fn(ptr(src), *src.shape, ptr(rx), ptr(ry), n, *background, ptr(out), stream_ptr(src.device)), f"hs_{name}")
+    return out[0] if squeeze else out
+
+
 def sample_bilinear_u8(img, rx, ry, per_sample=False):
     """`sample_bilinear(img, rx, ry).astype(np.uint8)`: img uint8 [C, H, W] or [B, C, H, W] on the GPU, rx along H, ry along
     W (float64 arrays or tensors) -> uint8 [(B,) C, n].  per_sample=False: one coordinate table for the whole batch (rx, ry of
     any shape are flattened).  per_sample=True: rx, ry are [B, n] and sample b reads row b (`hs_sample_bilinear_u8_per_sample`,
     the same kernel and arithmetic)."""
-    n = _per_sample_count(img, 4, rx, ry) if per_sample else None
-    img, squeeze = _device_u8(img, 4, "img")
-    rx, ry = _coords(rx, img.device), _coords(ry, img.device)
-    assert rx.shape == ry.shape, "rx and ry must have the same shape"
-    n = rx.numel() if n is None else n
-    b, c, h, w = img.shape
-    out = torch.empty((b, c, n), dtype=torch.uint8, device=img.device)
-    fn = lib.hs_sample_bilinear_u8_per_sample if per_sample else lib.hs_sample_bilinear_u8
-    check(fn(ptr(img), b, c, h, w, ptr(rx), ptr(ry), n, ptr(out), stream_ptr(img.device)), "hs_sample_bilinear_u8")
-    return out[0] if squeeze else out
+    return _sample("sample_bilinear_u8", img, 4, torch.uint8, "img", rx, ry, per_sample, torch.uint8)
 
 
 def sample_mask(mask, rx, ry, s2_bkgd_class=0, per_sample=False):
     """Nearest-pixel (round half to even) class ids: mask uint8 [H, W] or [B, H, W] on the GPU -> uint8 [(B,) n].  Classes
     never mix.  per_sample as in sample_bilinear_u8 (`hs_sample_mask_u8_per_sample`)."""
-    n = _per_sample_count(mask, 3, rx, ry) if per_sample else None
-    mask, squeeze = _device_u8(mask, 3, "mask")
-    rx, ry = _coords(rx, mask.device), _coords(ry, mask.device)
-    assert rx.shape == ry.shape, "rx and ry must have the same shape"
-    n = rx.numel() if n is None else n
-    b, h, w = mask.shape
-    out = torch.empty((b, n), dtype=torch.uint8, device=mask.device)
-    fn = lib.hs_sample_mask_u8_per_sample if per_sample else lib.hs_sample_mask_u8
-    check(fn(ptr(mask), b, h, w, ptr(rx), ptr(ry), n, int(s2_bkgd_class), ptr(out), stream_ptr(mask.device)), "hs_sample_mask_u8")
-    return out[0] if squeeze else out
+    return _sample("sample_mask_u8", mask, 3, torch.uint8, "mask", rx, ry, per_sample, torch.uint8, (int(s2_bkgd_class),))
 
 
 # ------------------------------------------------------------------ per-sample rotation augmentation
@@ -184,24 +172,13 @@ def camera_record(cal_info, used_size=None):
     return cam
 
 
-def _rotation_batch(rotations, device=None):
-    """rotations [B, 3, 3] (device tensor or host array) as a float64 tensor, on `device` if given; the shape is checked before
-    anything touches the device."""
-    shape = tuple(np.shape(rotations))
-    if len(shape) != 3 or shape[1:] != (3, 3) or shape[0] < 1:
-        raise ValueError(f"rotations must be [batch, 3, 3] with batch >= 1, got {shape}")
-    if not torch.is_tensor(rotations):
-        rotations = torch.from_numpy(np.ascontiguousarray(rotations, dtype=np.float64))
-    return rotations if device is None else rotations.to(device=device, dtype=torch.float64)
-
-
 def _rotated_coords(nside, base_pix, cam, rotations, pole, device):
     """rotated_coords on prepared arguments: cam a FisheyeCamera, pole None or rot_grid's matrix as a float64 [3, 3] tensor on
     `device`.  No host synchronisation and, with `rotations` on the device, no copy: capturable."""
     device = torch.device(device)
     m = _rotation_batch(rotations, device)
     if pole is not None:
-        m = (m[:, :, :, None] * pole[None, None, :, :]).sum(2)  # A_b R, elementwise: the same rounding on every device
+        m = _matmul3(m, pole)  # A_b R
     m = m.contiguous()
     batch, n = m.shape[0], int(nside) * int(nside) * int(base_pix)
     u = torch.empty((batch, n), dtype=torch.float64, device=device)
@@ -227,7 +204,46 @@ def rotated_coords(nside, base_pix, cal_info, rotations, rotate_pole=False, used
     return _rotated_coords(nside, base_pix, camera_record(cal_info, used_size), rotations, pole, device)
 
 
-class HPProjector:
+def _with_used_size(cal_info, used_size):
+    """cal_info with used_size = (height, width) of the image actually sampled in place of the calibration's size"""
+    if used_size is None:
+        return cal_info
+    return dict(cal_info, intrinsic=dict(cal_info["intrinsic"], height=int(used_size[0]), width=int(used_size[1])))
+
+
+class _FisheyeProjector:
+    """What HPProjector and depth_data.HPDepthProjector share: the resident coordinate table of one calibration, the per-sample
+    coordinates under `rotations`, and the two sampling launches.  A subclass names its frame and nearest samplers, the type of its
+    background value and the keyword of its second plane."""
+
+    _sample_frame = _sample_nearest = None
+
+    def __init__(self, cal_info, nside, base_pix, rotate_pole, s2_bkgd_class, used_size, device):
+        self.nside, self.base_pix, self.s2_bkgd_class = int(nside), int(base_pix), s2_bkgd_class
+        theta, phi = hp_grid(self.nside, self.base_pix)
+        u, v = project_s2_points_to_img(theta, phi, _with_used_size(cal_info, used_size), rotate_pole)
+        self.device = torch.device(device)
+        self.u, self.v = _coords(u, self.device), _coords(v, self.device)  # resident coordinate table: 16 B per pixel
+        self._cam = camera_record(cal_info, used_size)
+        self._pole = torch.from_numpy(_pole_rotation(cal_info)).to(self.device) if rotate_pole else None
+
+    @property
+    def npix(self):
+        return self.u.numel()
+
+    def _proj(self, imgs, nearest, rotations):
+        if rotations is None:
+            u, v, per_sample = self.u, self.v, False
+        else:
+            u, v = _rotated_coords(self.nside, self.base_pix, self._cam, rotations, self._pole, self.device)
+            per_sample = True
+        hp_img = self._sample_frame(imgs, v, u, per_sample)
+        if nearest is None:
+            return hp_img
+        return hp_img, self._sample_nearest(nearest, v, u, self.s2_bkgd_class, per_sample)
+
+
+class HPProjector(_FisheyeProjector):
     """project_dataset_hp for the frames of one camera: `proj(imgs, masks)` -> (hp_img uint8 [B, C, Npix], hp_mask uint8
     [B, Npix]) on the GPU, ready for `SwinHPTransformerSys.forward` and `seg_loss` (or `data.write_sample`).
 
@@ -237,26 +253,12 @@ class HPProjector:
     path: the resident table, the reference's bytes.  Identity rotations go through the device arithmetic and agree with it to
     coordinate rounding only (about 1e-12 px), not bit for bit."""
 
+    _sample_frame, _sample_nearest = staticmethod(sample_bilinear_u8), staticmethod(sample_mask)
+
     def __init__(self, cal_info, nside, base_pix=8, rotate_pole=False, s2_bkgd_class=0, device="cuda"):
-        self.nside, self.base_pix, self.s2_bkgd_class = int(nside), int(base_pix), int(s2_bkgd_class)
-        theta, phi = hp_grid(nside, base_pix)
-        u, v = project_s2_points_to_img(theta, phi, cal_info, rotate_pole)
-        self.device = torch.device(device)
-        self.u, self.v = _coords(u, self.device), _coords(v, self.device)  # resident coordinate table: 16 B per pixel
-        self._cam = camera_record(cal_info)
-        self._pole = torch.from_numpy(_pole_rotation(cal_info)).to(self.device) if rotate_pole else None
+        super().__init__(cal_info, nside, base_pix, rotate_pole, int(s2_bkgd_class), None, device)
 
-    @property
-    def npix(self):
-        return self.u.numel()
+    def proj(self, imgs, masks=None, rotations=None):
+        return self._proj(imgs, masks, rotations)
 
-    def __call__(self, imgs, masks=None, rotations=None):
-        if rotations is None:
-            u, v, per_sample = self.u, self.v, False
-        else:
-            u, v = _rotated_coords(self.nside, self.base_pix, self._cam, rotations, self._pole, self.device)
-            per_sample = True
-        hp_img = sample_bilinear_u8(imgs, v, u, per_sample)
-        if masks is None:
-            return hp_img
-        return hp_img, sample_mask(masks, v, u, self.s2_bkgd_class, per_sample)
+    __call__ = proj

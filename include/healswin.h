@@ -1047,8 +1047,9 @@ int hs_depth_metrics_gather(const void* pred, int pred_kind, int64_t batch, int6
 
 /* ------------------------------------------------------------------------------------------------
  * The depth data path (heal_swin_amd/depth_data.py): the per-frame sampling of data/depth_estimation/project_depth_on_s2.py
- * (project_depth_dataset_hp :389-440, against hs_sample_*_u8's coordinate tables), the target transforms of the depth datasets
- * and Lightning module, and compute_depth_stats.py's statistics.
+ * (project_depth_dataset_hp :389-440, against hs_sample_*_u8's coordinate tables; the same kernels as hs_sample_*_u8,
+ * csrc/projection.hip), the target transforms of the depth datasets and Lightning module, and compute_depth_stats.py's statistics
+ * (csrc/depth_data.hip).
  *   hs_sample_bilinear_u8_f32  sample_bilinear(img, rx, ry).astype(np.float32) (:48-77): hs_sample_bilinear_u8's float64
  *                       arithmetic rounded once to float32, NaN where a coordinate is not finite.  out [dev] f32[batch, channels, n].
  *   hs_sample_nearest_f32  sample_mask(depth, rx, ry, background) (:80-84): src [dev] f32[batch, height, width] -> out [dev]

@@ -1,5 +1,5 @@
-"""heal_swin_amd.depth_data on the GPU (csrc/depth_data.hip): the depth sampling bit-equal to the reference's, the target
-transforms of all 18 (transform, normalization, mask_background) combinations forward, inverse and as dataset preparation, the
+"""heal_swin_amd.depth_data on the GPU (csrc/projection.hip, csrc/depth_data.hip): the depth sampling bit-equal to the
+reference's, the target transforms of all 18 (transform, normalization, mask_background) combinations forward, inverse and as dataset preparation, the
 streaming dataset statistics against a numpy restatement of compute_depth_stats.py, and the whole depth data path feeding
 forward_depth_loss and DepthMetrics."""
 import math

@@ -48,6 +48,19 @@ def test_sampling_edge_cases():
     assert (P.sample_mask(dev(g["edge/mask"]), np.ones(5), bad, 9).cpu().numpy() == 9).all()
 
 
+def test_every_sampler_refuses_coordinates_of_unequal_length():
+    """rx of length 3 with ry of length 4: a ValueError from each of the four public samplers."""
+    from heal_swin_amd import depth_data as DD
+    from heal_swin_amd import projection as P
+
+    img, mask = torch.zeros((3, 5, 7), dtype=torch.uint8).cuda(), torch.zeros((5, 7), dtype=torch.uint8).cuda()
+    rx, ry = np.zeros(3), np.zeros(4)
+    for call in (lambda: P.sample_bilinear_u8(img, rx, ry), lambda: P.sample_mask(mask, rx, ry),
+                 lambda: DD.sample_bilinear_f32(img, rx, ry), lambda: DD.sample_depth(mask.float(), rx, ry)):
+        with pytest.raises(ValueError):
+            call()
+
+
 def test_batched_full_size_projection_matches_the_oracle():
     """WoodScape frame size (966 x 1280), nside 256, 8 base pixels (524 288 pixels), a batch of 3 frames against one table."""
     from heal_swin_amd import projection as P
