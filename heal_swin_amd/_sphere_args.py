@@ -1,9 +1,11 @@
-"""Argument handling shared by the sphere data path (projection, depth_data, hp_rotate, erp, hp_ensemble; evaluation takes
-`_resolved`): plain functions, one copy of each.  Everything here refuses by shape, dtype and value first and touches the device
-last, so a malformed call fails the same way with and without a GPU.
+"""Argument handling shared by the sphere data path (projection, depth_data, hp_rotate, erp, hp_ensemble) and the evaluation
+path (evaluation, depth_evaluation, flat_evaluation): plain functions, one copy of each.  Everything here refuses by shape,
+dtype and value first and touches the device last, so a malformed call fails the same way with and without a GPU.
 """
 import numpy as np
 import torch
+
+from ._lib import HS_F64, dtype_code
 
 MAX_NSIDE = 8192  # 12 nside^2 nested indices as int32
 MAX_CHANNELS = 16
@@ -70,12 +72,34 @@ def _check_batch(batch):
         raise ValueError(f"batch must be in [1, {MAX_BATCH}], got {batch}")
 
 
+def _label_class(s2_bkgd_class):
+    """s2_bkgd_class as a uint8 label"""
+    if not 0 <= int(s2_bkgd_class) <= 255:
+        raise ValueError(f"s2_bkgd_class must be in [0, 255] (uint8 labels), got {s2_bkgd_class}")
+    return int(s2_bkgd_class)
+
+
 def _fills(s2_bkgd_class, depth_fill):
     """(s2_bkgd_class as a uint8 label, depth_fill with its default float(s2_bkgd_class): what HPDepthProjector writes outside the
     image)"""
-    if not 0 <= int(s2_bkgd_class) <= 255:
-        raise ValueError(f"s2_bkgd_class must be in [0, 255] (uint8 labels), got {s2_bkgd_class}")
-    return int(s2_bkgd_class), float(s2_bkgd_class) if depth_fill is None else float(depth_fill)
+    return _label_class(s2_bkgd_class), float(s2_bkgd_class) if depth_fill is None else float(depth_fill)
+
+
+# ------------------------------------------------------------------ the tensors of the evaluation path
+def _kind_of(t, allow_f64=False):
+    """HS_F32 / HS_BF16 (HS_F64 where the entry point takes it) of a tensor's dtype; TypeError for any other"""
+    return HS_F64 if allow_f64 and t.dtype == torch.float64 else dtype_code(t.dtype)
+
+
+def _device_tensor(t, what, device, dtypes=None, error=TypeError):
+    """Refuse what the evaluation kernels cannot read in place: anything but a GPU tensor on `device` (raised as `error`, the type
+    callers of each public method catch), a dtype outside `dtypes` (TypeError), a negative stride (ValueError)."""
+    if not torch.is_tensor(t) or t.device != device or not t.is_cuda:
+        raise error(f"{what} must be a tensor on {device} (the evaluation kernels have no CPU path)")
+    if dtypes is not None and t.dtype not in dtypes:
+        raise TypeError(f"{what} must be {' / '.join(_dtype_name(d) for d in dtypes)}, got {t.dtype}")
+    if t.dim() and min(t.stride()) < 0:
+        raise ValueError(f"{what}: negative strides are not supported")
 
 
 # ------------------------------------------------------------------ the planes of HPRotator.rot and ERPProjector.proj

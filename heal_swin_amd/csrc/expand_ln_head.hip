@@ -20,6 +20,7 @@
 // logits of the row land in registers 0..7 of the same lane pair.  32 C / 16 + 4 C / 16 MFMAs per 32 pixel rows.
 #include "ln_head_device.h"
 #include "hs_depth_loss.h"
+#include "hs_histogram.h"
 
 // the target transform and the metric rules of TailDepthStep form their values unfused (their headers say why); everything else in
 // this file keeps the default contraction
@@ -36,16 +37,6 @@ constexpr int kRowB = 256;  // bytes per weight row in LDS (C <= 128 bf16; rows 
 constexpr int kPatchRow = 128;
 
 constexpr int kHistBins = kKP * kKP;  // per-wave LDS histogram of TailCeStep: 16 x 16 uint32 bins = 1 KB
-
-// torch.max(logits, 1)'s index over a row split between two lanes: (best, arg) is each lane's own result over its classes in
-// ascending order (argmax_step), `ob`, `oa` the partner's.  The first NaN wins, else the larger value, and on equal values the
-// lower class id: the lanes of a pair hold interleaved ids, so the merge has to compare the indices too.
-__device__ __forceinline__ int argmax_merge(float best, int arg, float ob, int oa) {
-    const bool n0 = best != best, n1 = ob != ob;
-    const int lower = arg < oa ? arg : oa;
-    if (n0 || n1) return n0 && n1 ? lower : (n0 ? arg : oa);
-    return best > ob ? arg : (ob > best ? oa : lower);
-}
 
 // ---- The loss epilogues.  The kernel is a template over one of the four structs below and calls its row() once per pixel
 // row, with the row's 16 head outputs in registers 0..7 of the lane pair (class_natural) and TailLane for what the lane carries
@@ -107,8 +98,8 @@ struct TailCe {
 
 // ... or the segmentation caller's whole `shared_step` (model_lightning_swin_hp.py:104-111: argmax, weighted cross-entropy, IoU /
 // Accuracy on (preds, masks)): TailCe's loss, plus the row's class id (torch.max(logits, 1): the first maximal class, a NaN
-// counts as the maximum -- argmax_step of evaluation.hip) and the confusion matrix behind the metrics (hs_seg_confusion's
-// counting: labels >= n_classes stay out of the matrix and are counted in bad[0]).  labels is never null here.
+// counts as the maximum -- argmax_step and argmax_merge of hs_device.h) and the confusion matrix behind the metrics
+// (hs_seg_confusion's counting: labels >= n_classes stay out of the matrix and are counted in bad[0]).  labels is never null here.
 struct TailCeStep : TailCe {
     uint8_t* preds;            // [rows] class ids, or null; 4-byte aligned (the 4 children of a token leave as one dword)
     unsigned long long* conf;  // [n_classes][n_classes] (target, prediction) counts, added to; or null
@@ -125,10 +116,7 @@ struct TailCeStep : TailCe {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {  // r ascending = class id ascending
             const int cls = class_natural(r, half);
-            if (cls < n_classes && !(best != best) && (v[r] > best || v[r] != v[r])) {
-                best = v[r];
-                arg = cls;
-            }
+            if (cls < n_classes) argmax_step(v[r], cls, best, arg);
         }
         const int pred = argmax_merge(best, arg, __shfl_xor(best, 32, 64), __shfl_xor(arg, 32, 64));
         st.pred4 |= (uint32_t)pred << (8 * p);
@@ -136,14 +124,7 @@ struct TailCeStep : TailCe {
             const bool mine = live && half == 0;
             const int bin = mine && yl < n_classes ? yl * n_classes + pred : -1;
             st.bad_rows += (uint32_t)__popcll(__ballot(mine && yl >= n_classes));
-            // the lanes that share the first lane's bin (most of them in the uniform regions of a mask) add with one atomic
-            const int lead = __builtin_amdgcn_readfirstlane(bin);
-            const unsigned long long same = __ballot(bin == lead);
-            if (bin == lead) {
-                if (lead >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(&st.hist[lead], (uint32_t)__popcll(same));
-            } else if (bin >= 0) {
-                atomicAdd(&st.hist[bin], 1u);
-            }
+            wave_count_lead(st.hist, bin, lane);
         }
     }
 };
@@ -524,12 +505,9 @@ int hs_expand_ln_head_depth_step_fwd(const void* xn, const void* xn_lo, const vo
     HS_CHECK_ALIGNED(who, 4, target, loss_partials);
     if (int e = launch_expand_ln_head(xn, xn_lo, wexp, wfold, bvec, y, logits, mean, rstd, tokens, width, children, dtype, stream, st, who))
         return e;
-    if (metric_state) {  // the ordered merge of hs_depth_metrics: state[k] += sum over workgroups of partial[blk][k]
-        hipLaunchKernelGGL(hs::depth_metrics::reduce_kernel, dim3(1), dim3(hs::depth_metrics::kThreads), 0, (hipStream_t)stream,
-                           metric_partials, (int)hs_expand_ln_head_blocks(tokens), metric_state);
-        HS_LAUNCH_CHECK("expand_ln_head_depth_step_reduce");
-    }
-    return HS_OK;
+    if (!metric_state) return HS_OK;
+    // the ordered merge of hs_depth_metrics: state[k] += sum over workgroups of partial[blk][k]
+    return hs::depth_metrics::launch_reduce(metric_partials, (int)hs_expand_ln_head_blocks(tokens), metric_state, (hipStream_t)stream);
 }
 
 int hs_expand_ln_head_depth_fwd(const void* xn, const void* xn_lo, const void* wexp, const void* wfold, const float* bvec, const float* target,

@@ -12,7 +12,7 @@
 // pixel and sample; neighbouring HEALPix pixels land on neighbouring image pixels, so the reads of a wave share cache lines.
 #include <algorithm>
 
-#include "hs_device.h"
+#include "hs_sphere_args.h"
 
 #pragma clang fp contract(off)
 
@@ -34,16 +34,12 @@ struct FlatPred {
     int64_t n;               // HEALPix pixels
 };
 
-__device__ __forceinline__ float load_pred(const FlatPred& a, int64_t off) {
-    return a.kind == HS_F32 ? ((const float*)a.p)[off] : bf16_to_float(((const uint16_t*)a.p)[off]);
-}
-
 // the prediction of HEALPix pixel i of sample b, channel offset `ch` (0 or sc); NaN where uncovered
 __device__ __forceinline__ float gather_pred(const FlatPred& a, int64_t b, int64_t i, int64_t ch) {
     const int64_t base = b * a.sb + ch;
     if (a.nearest) {
         const int64_t q = a.nearest[i];
-        return q >= 0 && q < a.n_src ? load_pred(a, base + q * a.sp) : NAN;  // copied, not computed: the bits survive
+        return q >= 0 && q < a.n_src ? load_val<float>(a.p, a.kind, base + q * a.sp) : NAN;  // copied, not computed: the bits survive
     }
     int64_t q[4];
     bool in = true;
@@ -54,8 +50,8 @@ __device__ __forceinline__ float gather_pred(const FlatPred& a, int64_t b, int64
     }
     if (!in) return NAN;
     const float h0 = a.wgt[i], h1 = a.wgt[a.n + i], w0 = a.wgt[2 * a.n + i], w1 = a.wgt[3 * a.n + i];
-    const float p00 = load_pred(a, base + q[0] * a.sp), p01 = load_pred(a, base + q[1] * a.sp);
-    const float p10 = load_pred(a, base + q[2] * a.sp), p11 = load_pred(a, base + q[3] * a.sp);
+    const float p00 = load_val<float>(a.p, a.kind, base + q[0] * a.sp), p01 = load_val<float>(a.p, a.kind, base + q[1] * a.sp);
+    const float p10 = load_val<float>(a.p, a.kind, base + q[2] * a.sp), p11 = load_val<float>(a.p, a.kind, base + q[3] * a.sp);
     // torch's upsample_bilinear2d on the CPU: h0 * (w0 p00 + w1 p01) + h1 * (w0 p10 + w1 p11), fp32, no fused multiply-add
     return h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11);
 }
@@ -76,29 +72,22 @@ struct GatherTarget {
 
 __global__ void __launch_bounds__(kThreads) depth_metrics_gather_kernel(FlatPred a, GatherTarget t, int64_t batch, depth_metrics::Rule rule,
                                                                         double* __restrict__ partial) {
-    __shared__ double lds[kThreads];
-    double acc[depth_metrics::kNSums];
-#pragma unroll
-    for (int k = 0; k < depth_metrics::kNSums; ++k) acc[k] = 0.0;
-    const int64_t total = a.n * batch;
-    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
-        const int64_t b = e / a.n, i = e - b * a.n;
-        const float p = gather_pred(a, b, i, 0);
-        const float tv = depth_metrics::load_val<float>(t.p, t.kind, b * t.sb + i * t.sp);
-        depth_metrics::accumulate(acc, rule, p, tv, [&] { return gather_pred(a, b, i, a.sc); });
-    }
-    depth_metrics::store_partials(acc, lds, partial);
+    depth_metrics::metric_pass(rule, a.n, batch, partial, [&a, &t](int64_t b, int64_t i) {
+        return std::make_tuple(gather_pred(a, b, i, 0), load_val<float>(t.p, t.kind, b * t.sb + i * t.sp),
+                               [&a, b, i] { return gather_pred(a, b, i, a.sc); });
+    });
 }
 
-int make_pred(FlatPred& a, const void* pred, int kind, int64_t batch, int64_t n_src, int64_t stride_b, int64_t stride_c, int64_t stride_p,
-              const int32_t* nearest, const int32_t* idx, const float* wgt, int64_t n) {
-    HS_CHECK_ARG(kind == HS_F32 || kind == HS_BF16, "prediction kind %d: expected HS_F32 or HS_BF16", kind);
-    HS_CHECK_ARG(batch > 0 && n_src > 0 && n_src < (1ll << 31) && n > 0 && n < (1ll << 31), "bad shape (batch %lld, n_src %lld, n %lld)",
-                 (long long)batch, (long long)n_src, (long long)n);
-    HS_CHECK_ARG(stride_b >= 0 && stride_c >= 0 && stride_p >= 0, "negative strides");
-    HS_CHECK_ARG((nearest != nullptr) != (idx != nullptr), "give the nearest table or the bilinear taps, not both");
-    HS_CHECK_ARG(nearest || wgt, "bilinear taps need their weights");
-    HS_CHECK_ARG(pred, "null pointer");
+int make_pred(const char* who, FlatPred& a, const void* pred, int kind, int64_t batch, int64_t n_src, int64_t stride_b, int64_t stride_c,
+              int64_t stride_p, const int32_t* nearest, const int32_t* idx, const float* wgt, int64_t n) {
+    if (int st = sphere::check_float_kind(who, "prediction", kind)) return st;
+    HS_CHECK_ARG(batch > 0, "%s: batch must be positive, got %lld", who, (long long)batch);
+    if (int st = sphere::check_pixel_count(who, "n_src", n_src)) return st;
+    if (int st = sphere::check_pixel_count(who, "n", n)) return st;
+    HS_CHECK_ARG(stride_b >= 0 && stride_c >= 0 && stride_p >= 0, "%s: negative strides", who);
+    HS_CHECK_ARG((nearest != nullptr) != (idx != nullptr), "%s: give the nearest table or the bilinear taps, not both", who);
+    HS_CHECK_ARG(nearest || wgt, "%s: bilinear taps need their weights", who);
+    HS_CHECK_ARG(pred, "%s: null pointer", who);
     a = FlatPred{pred, kind, stride_b, stride_c, stride_p, n_src, nearest, idx, wgt, n};
     return HS_OK;
 }
@@ -113,7 +102,7 @@ extern "C" {
 int hs_flat_depth_to_hp(const void* pred, int kind, int64_t batch, int64_t n_src, int64_t stride_b, int64_t stride_p, const int32_t* nearest,
                         const int32_t* idx, const float* wgt, int64_t n, float* out, void* stream) {
     FlatPred a;
-    if (int st = make_pred(a, pred, kind, batch, n_src, stride_b, 0, stride_p, nearest, idx, wgt, n)) return st;
+    if (int st = make_pred("hs_flat_depth_to_hp", a, pred, kind, batch, n_src, stride_b, 0, stride_p, nearest, idx, wgt, n)) return st;
     HS_CHECK_ARG(out, "null pointer");
     const int64_t blocks = std::min<int64_t>((n * batch + kThreads - 1) / kThreads, 4096);
     hipLaunchKernelGGL(flat_depth_to_hp_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, a, batch, out);
@@ -125,21 +114,19 @@ int hs_depth_metrics_gather(const void* pred, int pred_kind, int64_t batch, int6
                             const int32_t* nearest, const int32_t* idx, const float* wgt, int64_t n, const void* target, int target_kind,
                             int64_t t_stride_b, int64_t t_stride_p, int use_logvar, double total_mean, const float* ranges, int n_ranges,
                             double* partial, double* state, void* stream) {
+    const char* who = "hs_depth_metrics_gather";
     FlatPred a;
-    if (int st = make_pred(a, pred, pred_kind, batch, n_src, stride_b, stride_c, stride_p, nearest, idx, wgt, n)) return st;
-    HS_CHECK_ARG(target_kind == HS_F32 || target_kind == HS_BF16, "target kind %d: expected HS_F32 or HS_BF16", target_kind);
-    HS_CHECK_ARG(t_stride_b >= 0 && t_stride_p >= 0, "negative strides");
+    if (int st = make_pred(who, a, pred, pred_kind, batch, n_src, stride_b, stride_c, stride_p, nearest, idx, wgt, n)) return st;
+    if (int st = sphere::check_float_kind(who, "target", target_kind)) return st;
+    HS_CHECK_ARG(t_stride_b >= 0 && t_stride_p >= 0, "%s: negative strides", who);
     depth_metrics::Rule rule;
     if (int st = depth_metrics::fill_rule(rule, use_logvar, total_mean, ranges, n_ranges)) return st;
-    HS_CHECK_ARG(target && partial && state, "null pointer");
+    HS_CHECK_ARG(target && partial && state, "%s: null pointer", who);
     const GatherTarget t{target, target_kind, t_stride_b, t_stride_p};
-    const int blocks = (int)depth_metrics::blocks_for(n * batch);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(depth_metrics_gather_kernel, dim3(blocks), dim3(kThreads), 0, s, a, t, batch, rule, partial);
-    HS_LAUNCH_CHECK("depth_metrics_gather");
-    hipLaunchKernelGGL(depth_metrics::reduce_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, state);
-    HS_LAUNCH_CHECK("depth_metrics_reduce");
-    return HS_OK;
+    return depth_metrics::run_pass(n * batch, partial, state, s, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(depth_metrics_gather_kernel, grid, block, 0, s, a, t, batch, rule, partial);
+    });
 }
 
 }  // extern "C"

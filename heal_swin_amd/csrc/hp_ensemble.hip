@@ -29,6 +29,7 @@
 
 namespace {
 
+using hs::argmax_step;
 using hs::bf16_t;
 using hs::healpix::covered;
 using hs::healpix::rotated_interp;
@@ -211,7 +212,7 @@ __global__ void __launch_bounds__(kThreads) ensemble_add_depth_kernel(DepthArgs 
     add_depth_pixel<T>(a, blockIdx.y, i);
 }
 
-// torch.max(acc, 1)'s index: the first maximal class; a NaN counts as the maximum (the first NaN wins)
+// preds: torch.max(acc, 1)'s index (argmax_step)
 template <int KP>
 __global__ void __launch_bounds__(kThreads) ensemble_finish_seg_kernel(int64_t npix, int K, const float* __restrict__ acc,
                                                                        const float* __restrict__ wsum, float min_weight, int background,
@@ -233,7 +234,7 @@ __global__ void __launch_bounds__(kThreads) ensemble_finish_seg_kernel(int64_t n
     int arg = 0;
 #pragma unroll
     for (int c = 0; c < KP; ++c)
-        if (c < K && !(best != best) && (v[c] > best || v[c] != v[c])) best = v[c], arg = c;
+        if (c < K) argmax_step(v[c], c, best, arg);
     preds[b * npix + i] = live ? (uint8_t)arg : (uint8_t)background;
     if (probs) {
 #pragma unroll
@@ -290,7 +291,7 @@ int check_seg(const char* who, int nside, int64_t npix, int batch, const void* p
 int check_depth(const char* who, int nside, int64_t npix, int batch, const void* pred, int kind, int64_t sb, int64_t sp, const float* acc,
                 const float* wsum) {
     if (int st = check_grid(who, nside, npix, batch)) return st;
-    HS_CHECK_ARG(kind == HS_F32 || kind == HS_BF16, "%s: prediction kind %d: expected HS_F32 or HS_BF16", who, kind);
+    if (int st = check_float_kind(who, "prediction", kind)) return st;
     HS_CHECK_ARG(sb >= 0 && sp >= 0, "%s: negative stride", who);
     HS_CHECK_ARG(pred && acc && wsum, "%s: null pointer", who);
     const int64_t pred_bytes = ((batch - 1) * sb + (npix - 1) * sp + 1) * elem_size(kind), bytes = (int64_t)batch * npix * 4;
@@ -398,7 +399,7 @@ int hs_hp_ensemble_add_depth_host(int nside, int64_t npix, const double* rot, in
 int hs_hp_ensemble_finish_seg(int64_t npix, int batch, int n_classes, const float* acc, const float* wsum, float min_weight, int background,
                               uint8_t* preds, float* probs, int64_t stride_b, int64_t stride_k, int64_t stride_p, void* stream) {
     const char* who = "hs_hp_ensemble_finish_seg";
-    HS_CHECK_ARG(npix > 0 && npix < (1ll << 31), "%s: npix must be in [1, 2^31), got %lld", who, (long long)npix);
+    if (int st = check_pixel_count(who, "npix", npix)) return st;
     if (int st = check_batch(who, batch)) return st;
     HS_CHECK_ARG(n_classes >= 1 && n_classes <= kMaxClasses, "%s: n_classes must be in [1, %d], got %d", who, kMaxClasses, n_classes);
     HS_CHECK_ARG(background >= 0 && background <= 255, "%s: background must be in [0, 255], got %d", who, background);
@@ -424,7 +425,7 @@ int hs_hp_ensemble_finish_seg(int64_t npix, int batch, int n_classes, const floa
 
 int hs_hp_ensemble_finish_depth(int64_t npix, int batch, const float* acc, const float* wsum, float min_weight, float* out, void* stream) {
     const char* who = "hs_hp_ensemble_finish_depth";
-    HS_CHECK_ARG(npix > 0 && npix < (1ll << 31), "%s: npix must be in [1, 2^31), got %lld", who, (long long)npix);
+    if (int st = check_pixel_count(who, "npix", npix)) return st;
     if (int st = check_batch(who, batch)) return st;
     HS_CHECK_ARG(min_weight >= 0.f, "%s: min_weight must be >= 0", who);
     HS_CHECK_ARG(acc && wsum && out, "%s: null pointer", who);

@@ -28,6 +28,10 @@ inline bool aligned_to(uintptr_t bytes, P... p) {
 
 inline bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
+// the classes of a segmentation that the loss (seg_loss.hip) and the evaluation kernels (evaluation.hip) take: a workgroup's
+// confusion matrix of 64 x 64 32-bit bins is 16 KB of LDS
+constexpr int kMaxSegClasses = 64;
+
 // Compute units the persistent / one-resident-round launches may plan for: 256 minus hs_set_reserved_cus(), spread evenly over
 // the 8 XCDs.  The kernels whose grids are sized to exactly the resident capacity of the chip (hs_linear_wgrad, hs_gemm_nt,
 // the attention kernels, the module kernel) leave the reserved CUs free for kernels of OTHER streams that must make progress

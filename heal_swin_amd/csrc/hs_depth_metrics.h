@@ -1,9 +1,12 @@
 // Per-element rules and the reduction of the depth error metrics (evaluation/custom_metrics.py:62-468), shared by
 // hs_depth_metrics (csrc/depth_eval.hip: both operands through strides) and hs_depth_metrics_gather (csrc/flat_eval.hip: the
 // prediction through a table), so that both form the same HS_DEPTH_NSUMS sums from the same values in the same order:
-// float64 per-lane sums, a tree over the workgroup, one partial record per workgroup, one ordered merge into the state.
+// float64 per-lane sums, a tree over the workgroup, one partial record per workgroup, one ordered merge into the state
+// (metric_pass and run_pass; the decoder tail, csrc/expand_ln_head.hip, accumulates in its own kernel and shares launch_reduce).
 // Include after `#pragma clang fp contract(off)`.
 #pragma once
+
+#include <tuple>
 
 #include "hs_device.h"
 
@@ -25,13 +28,6 @@ struct Rule {
 inline int64_t blocks_for(int64_t total) {
     const int64_t blocks = (total + kThreads * 8 - 1) / (kThreads * 8);
     return blocks < 1 ? 1 : (blocks > kBlocksMax ? kBlocksMax : blocks);
-}
-
-template <typename C>
-__device__ __forceinline__ C load_val(const void* p, int kind, int64_t off) {
-    if (kind == HS_F64) return (C)((const double*)p)[off];
-    if (kind == HS_BF16) return (C)bf16_to_float(((const uint16_t*)p)[off]);
-    return (C)((const float*)p)[off];
 }
 
 __device__ __forceinline__ float log_c(float x) { return logf(x); }
@@ -107,6 +103,24 @@ __device__ __forceinline__ void store_partials(const double (&acc)[kNSums], doub
     }
 }
 
+// A workgroup's share of a metric pass over `batch` samples of `n` elements (grid of blocks_for(n * batch) workgroups of kThreads,
+// element e = b n + i on lane e mod the grid's lanes): pair(b, i) returns std::make_tuple(prediction, target, log_var), log_var a
+// callable as accumulate() takes it; the sums leave as the workgroup's partial record.
+template <typename Pair>
+__device__ __forceinline__ void metric_pass(const Rule& rule, int64_t n, int64_t batch, double* __restrict__ partial, Pair&& pair) {
+    __shared__ double lds[kThreads];
+    double acc[kNSums];
+#pragma unroll
+    for (int k = 0; k < kNSums; ++k) acc[k] = 0.0;
+    const int64_t total = n * batch;
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
+        const int64_t b = e / n, i = e - b * n;
+        const auto [p, t, log_var] = pair(b, i);
+        accumulate(acc, rule, p, t, log_var);
+    }
+    store_partials(acc, lds, partial);
+}
+
 // one workgroup: state[k] += sum over blocks of partial[blk][k], in a fixed order
 static __global__ void __launch_bounds__(kThreads) reduce_kernel(const double* __restrict__ partial, int blocks, double* __restrict__ state) {
     __shared__ double lds[kThreads];
@@ -128,6 +142,22 @@ inline int fill_rule(Rule& a, int use_logvar, double total_mean, const float* ra
         a.hi[r] = r < n_ranges ? ranges[2 * r + 1] : 0.f;
     }
     return HS_OK;
+}
+
+// host: the ordered merge of `blocks` partial records into the state
+inline int launch_reduce(const double* partial, int blocks, double* state, hipStream_t s) {
+    hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, state);
+    HS_LAUNCH_CHECK("depth_metrics_reduce");
+    return HS_OK;
+}
+
+// host: a metric pass over `total` elements: launch(grid, block) starts the caller's metric_pass kernel, then the merge
+template <typename Launch>
+inline int run_pass(int64_t total, const double* partial, double* state, hipStream_t s, Launch&& launch) {
+    const int blocks = (int)blocks_for(total);
+    launch(dim3(blocks), dim3(kThreads));
+    HS_LAUNCH_CHECK("depth_metrics pass");
+    return launch_reduce(partial, blocks, state, s);
 }
 
 }  // namespace depth_metrics

@@ -76,6 +76,33 @@ struct io<bf16_t> {
     static __device__ __forceinline__ void store(void* p, int64_t i, float v) { ((uint16_t*)p)[i] = float_to_bf16(v); }
 };
 
+// element `off` of an array whose element kind is known at run time only, in the compute type C: HS_F32 or HS_BF16, and HS_F64
+// where the entry point admits it (AllowF64; the others have refused it, and their kernels hold no float64 path)
+template <typename C, bool AllowF64 = false>
+__device__ __forceinline__ C load_val(const void* p, int kind, int64_t off) {
+    if constexpr (AllowF64)
+        if (kind == HS_F64) return (C)((const double*)p)[off];
+    return kind == HS_F32 ? (C)((const float*)p)[off] : (C)bf16_to_float(((const uint16_t*)p)[off]);
+}
+
+// torch.max(logits, 1)'s index, one class at a time in ascending order from (best, arg) = (-inf, first class): the first maximal
+// class; a NaN counts as the maximum (the first NaN wins); the first class wins over -inf by index
+__device__ __forceinline__ void argmax_step(float v, int c, float& best, int& arg) {
+    if (!(best != best) && (v > best || v != v)) {
+        best = v;
+        arg = c;
+    }
+}
+// ... over a row split between two lanes: (best, arg) is each lane's own result over its classes in ascending order, `ob`, `oa`
+// the partner's.  The first NaN wins, else the larger value, and on equal values the lower class id: the lanes of a pair may hold
+// interleaved ids, so the merge has to compare the indices too.
+__device__ __forceinline__ int argmax_merge(float best, int arg, float ob, int oa) {
+    const bool n0 = best != best, n1 = ob != ob;
+    const int lower = arg < oa ? arg : oa;
+    if (n0 || n1) return n0 && n1 ? lower : (n0 ? arg : oa);
+    return best > ob ? arg : (ob > best ? oa : lower);
+}
+
 // Counter-based dropout mask shared by the elementwise kernels: the keep decision of element i is a pure function of
 // (seed, i), so a backward pass regenerates the forward's mask instead of reading a mask tensor.
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {  // "lowbias32" integer finaliser

@@ -1,5 +1,5 @@
-// The piece the histogram kernels share (select.hip, depth_data.hip): one count per lane into a workgroup's LDS counters,
-// aggregated per wave first.
+// The pieces the histogram kernels share (select.hip, depth_data.hip: wave_count; evaluation.hip, expand_ln_head.hip:
+// wave_count_lead): one count per lane into LDS counters, aggregated per wave first.
 #pragma once
 #include "hs_device.h"
 
@@ -24,6 +24,21 @@ __device__ __forceinline__ void wave_count(uint32_t* hist, bool active, uint32_t
         left &= ~same;
     }
     if (active) atomicAdd(&hist[bin], 1u);
+}
+
+// The confusion matrices' add (hs_seg_confusion, the decoder tail's seg step): one count into hist[bin] per lane with bin >= 0.
+// The lanes that share the FIRST lane's bin -- most of a wave in the uniform regions of a segmentation -- add with one atomic of
+// their population count, every other lane on its own: one round, where wave_count peels kPeel.  Contract: called by EVERY lane
+// of the wave (the loop around it has a wave-uniform trip count); a lane with nothing to count comes with bin < 0, which counts
+// nothing, also when it is the first lane's.  `lane` is the caller's index in its wave.
+__device__ __forceinline__ void wave_count_lead(uint32_t* hist, int bin, int lane) {
+    const int lead = __builtin_amdgcn_readfirstlane(bin);
+    const unsigned long long same = __ballot(bin == lead);
+    if (bin == lead) {
+        if (lead >= 0 && lane == __ffsll((long long)same) - 1) atomicAdd(&hist[lead], (uint32_t)__popcll(same));
+    } else if (bin >= 0) {
+        atomicAdd(&hist[bin], 1u);
+    }
 }
 
 }  // namespace hs

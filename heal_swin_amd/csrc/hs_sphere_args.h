@@ -1,6 +1,7 @@
 // Host-side argument checks and launch shapes shared by the entry points of the sphere data path (projection_aug.hip,
-// hp_rotate.hip, hp_ensemble.hip, erp_project.hip): the HEALPix grid a call names, its batch, and the memory ranges it may not
-// mix.  Host only: nothing here is called from a kernel.  `who` prefixes the message.
+// hp_rotate.hip, hp_ensemble.hip, erp_project.hip) and of the evaluation path (evaluation.hip, depth_eval.hip, flat_eval.hip): the
+// HEALPix grid a call names, its batch, pixel counts and element kinds, and the memory ranges it may not mix.  Host only: nothing
+// here is called from a kernel.  `who` prefixes the message.
 #pragma once
 #include "hs_device.h"
 
@@ -20,6 +21,18 @@ inline int check_nside(const char* who, int nside, int supersample = 0, bool int
                      nside, supersample, kMaxNside);
     else if (int32_indices)
         HS_CHECK_ARG(nside <= kMaxNside, "%s: nside %d above %d: the nested indices are int32", who, nside, kMaxNside);
+    return HS_OK;
+}
+
+// a count of pixels (`what` names the argument) that the kernels and their tables index with int32
+inline int check_pixel_count(const char* who, const char* what, int64_t n) {
+    HS_CHECK_ARG(n > 0 && n < (1ll << 31), "%s: %s must be in [1, 2^31), got %lld", who, what, (long long)n);
+    return HS_OK;
+}
+
+// the element kind of fp32 / bf16 values (`what` names them)
+inline int check_float_kind(const char* who, const char* what, int kind) {
+    HS_CHECK_ARG(kind == HS_F32 || kind == HS_BF16, "%s: %s kind %d: expected HS_F32 or HS_BF16", who, what, kind);
     return HS_OK;
 }
 

@@ -14,7 +14,6 @@
 namespace hs {
 namespace {
 
-constexpr int kMaxClasses = 64;
 constexpr int kCeBlocks = 2048;
 
 struct CeArgs {
@@ -213,7 +212,7 @@ bool row16_layout(const void* ptr, int64_t sb, int64_t sk, int64_t sp, int K, in
 int check_args(const CeArgs& a, int dtype) {
     HS_CHECK_ARG(a.logits && a.labels, "null pointer");
     HS_CHECK_ARG(a.batch > 0 && a.npix > 0, "bad shape");
-    HS_CHECK_ARG(a.K >= 1 && a.K <= kMaxClasses, "n_classes must be in [1, 64]");
+    HS_CHECK_ARG(a.K >= 1 && a.K <= kMaxSegClasses, "n_classes must be in [1, %d]", kMaxSegClasses);
     HS_CHECK_ARG(a.label_bytes == 1 || a.label_bytes == 4 || a.label_bytes == 8, "labels must be uint8, int32 or int64");
     HS_CHECK_ARG(dtype == HS_F32 || dtype == HS_BF16, "dtype must be HS_F32 or HS_BF16");
     return HS_OK;

@@ -41,7 +41,8 @@ import math
 import numpy as np
 import torch
 
-from ._lib import HS_BF16, HS_F32, HS_F64, check, lib, np_ptr, ptr, stream_ptr
+from ._lib import check, lib, np_ptr, ptr, stream_ptr
+from ._sphere_args import _device_tensor, _kind_of
 from .evaluation import _device, get_uv_from_hw, project_img_points_to_s2
 from .order_stats import row_median
 from .projection import _camera_rotation, hp_grid
@@ -77,14 +78,6 @@ def directions(theta, phi, rotation):
     return np.asarray(rotation, np.float64) @ u
 
 
-def _dtype_kind(t):
-    if t.dtype == torch.float32:
-        return HS_F32
-    if t.dtype == torch.bfloat16:
-        return HS_BF16
-    raise TypeError(f"depth must be float32 or bfloat16, got {t.dtype}")
-
-
 def _background_values(background):
     """The finite background depths of a get_foreground_mask background tuple (NaN and +-inf are always dropped)."""
     vals = [float(b) for b in (background if isinstance(background, (tuple, list)) else (background,))]
@@ -112,15 +105,11 @@ class _DepthGeometry:
         are rows offsets[b] .. offsets[b + 1]; rows past offsets[B] are unused.  A pixel is kept when its depth is finite,
         is not one of the finite `background` values (the writers' mask_background uses (nan, inf, 1000)) and, if
         `foreground` (bool / uint8 [B, *shape] or [*shape]) is given, it is true there."""
-        if not torch.is_tensor(depth) or depth.device != self.device:
-            raise TypeError(f"depth must be a tensor on {self.device}")
-        kind = _dtype_kind(depth)
+        _device_tensor(depth, "depth", self.device, (torch.float32, torch.bfloat16))
         if tuple(depth.shape) == self.shape:
             depth = depth[None]
         if tuple(depth.shape[1:]) != self.shape:
             raise ValueError(f"depth must be [B, {', '.join(map(str, self.shape))}], got {tuple(depth.shape)}")
-        if min(depth.stride()) < 0:
-            raise ValueError("depth with negative strides is not supported")
         b = depth.shape[0]
         if len(self.shape) == 1:
             width, sh, sw = self.n, 0, depth.stride(1)
@@ -142,7 +131,7 @@ class _DepthGeometry:
         ws = torch.empty(int(lib.hs_depth_points_workspace(b, self.n)), dtype=torch.uint8, device=self.device)
         pts = torch.empty((b * self.n, 3), dtype=torch.float32, device=self.device)
         offsets = torch.empty(b + 1, dtype=torch.int64, device=self.device)
-        check(lib.hs_depth_points(ptr(depth), kind, b, self.n, width, depth.stride(0), sh, sw, ptr(fg), fg_sb,
+        check(lib.hs_depth_points(ptr(depth), _kind_of(depth), b, self.n, width, depth.stride(0), sh, sw, ptr(fg), fg_sb,
                                   np_ptr(bg) if bg.size else None, int(bg.size),
                                   ptr(self.dir), ptr(ws), ptr(pts), ptr(offsets), stream_ptr(self.device)), "hs_depth_points")
         return pts, offsets
@@ -309,9 +298,13 @@ class DepthMetrics:
         self.state.zero_()
         self.median.zero_()
 
-    @staticmethod
-    def _kind(t):
-        return HS_F64 if t.dtype == torch.float64 else _dtype_kind(t)
+    def _rule_args(self, total):
+        """What the two metric launches end with: the rule (use_logvar, total_mean, the ranges), a partial record per workgroup of
+        a pass over `total` elements, the state and the stream."""
+        partial = torch.empty(int(lib.hs_depth_metrics_partials(total)) * NSUMS, dtype=torch.float64, device=self.device)
+        rng = self._ranges
+        return (int(self.use_logvar), 0.0 if self.total_mean is None else self.total_mean, np_ptr(rng) if rng.size else None,
+                len(self.distance_ranges), ptr(partial), ptr(self.state), stream_ptr(self.device))
 
     @staticmethod
     def _strides(t, spatial):
@@ -324,21 +317,14 @@ class DepthMetrics:
         """update() of a FLAT prediction sampled onto the sphere through a flat_evaluation.FlatToHPProjector
         (`hs_depth_metrics_gather`): target [B, Npix] fp32 / bf16, pred in the projector's layout, read in place; the
         projected map is not written.  The state is the one update(projector.depth(pred), target) gives, bit for bit."""
-        if not torch.is_tensor(target) or target.device != self.device:
-            raise TypeError(f"target must be a tensor on {self.device}")
+        _device_tensor(target, "target", self.device)
         pred, sb, sc, sp = projector._depth_args(pred, 2 if self.use_logvar else 1)
         if target.dim() != 2 or tuple(target.shape) != (pred.shape[0], projector.n_out):
             raise ValueError(f"target must be [{pred.shape[0]}, {projector.n_out}], got {tuple(target.shape)}")
-        if min(target.stride()) < 0:
-            raise ValueError("negative strides are not supported")
         b, n = target.shape
-        partial = torch.empty(int(lib.hs_depth_metrics_partials(b * n)) * NSUMS, dtype=torch.float64, device=self.device)
-        rng = self._ranges
         near, idx, wgt = projector._tables()
-        check(lib.hs_depth_metrics_gather(ptr(pred), _dtype_kind(pred), b, projector.npix, sb, sc, sp, near, idx, wgt, n, ptr(target),
-                                          _dtype_kind(target), target.stride(0), target.stride(1), int(self.use_logvar),
-                                          0.0 if self.total_mean is None else self.total_mean, np_ptr(rng) if rng.size else None,
-                                          len(self.distance_ranges), ptr(partial), ptr(self.state), stream_ptr(self.device)),
+        check(lib.hs_depth_metrics_gather(ptr(pred), _kind_of(pred), b, projector.npix, sb, sc, sp, near, idx, wgt, n, ptr(target),
+                                          _kind_of(target), target.stride(0), target.stride(1), *self._rule_args(b * n)),
               "hs_depth_metrics_gather")
         if self.use_logvar:  # MeanSTDMedian needs the projected log variance itself
             self._add_stds(torch.sqrt(torch.exp(projector.depth(pred, channel=1))))
@@ -346,9 +332,8 @@ class DepthMetrics:
     def update(self, pred, target, projector=None):
         if projector is not None:
             return self._update_projected(pred, target, projector)
-        for t, name in ((pred, "pred"), (target, "target")):
-            if not torch.is_tensor(t) or t.device != self.device:
-                raise TypeError(f"{name} must be a tensor on {self.device}")
+        _device_tensor(pred, "pred", self.device)
+        _device_tensor(target, "target", self.device)
         spatial = target.dim() - 1
         if spatial not in (1, 2):
             raise ValueError(f"target must be [B, Npix] or [B, H, W], got {tuple(target.shape)}")
@@ -364,20 +349,12 @@ class DepthMetrics:
             raise ValueError(f"pred {tuple(pred.shape)} does not match target {tuple(target.shape)}")
         if pred.shape[0] != target.shape[0] or pred.shape[-spatial:] != target.shape[-spatial:]:
             raise ValueError(f"pred {tuple(pred.shape)} does not match target {tuple(target.shape)}")
-        if min(pred.stride()) < 0 or min(target.stride()) < 0:
-            raise ValueError("negative strides are not supported")
         b = target.shape[0]
         n = int(np.prod(target.shape[1:]))
         width, psh, psw = self._strides(pred, spatial)
         _, tsh, tsw = self._strides(target, spatial)
-        partial = torch.empty(int(lib.hs_depth_metrics_partials(b * n)) * NSUMS, dtype=torch.float64, device=self.device)
-        rng = self._ranges
-        check(lib.hs_depth_metrics(ptr(pred), self._kind(pred), b, n, width, pred.stride(0), sc, psh, psw, ptr(target),
-                                   self._kind(target), target.stride(0), tsh, tsw, int(self.use_logvar),
-                                   0.0 if self.total_mean is None else self.total_mean,
-                                   np_ptr(rng) if rng.size else None,
-                                   len(self.distance_ranges), ptr(partial), ptr(self.state), stream_ptr(self.device)),
-              "hs_depth_metrics")
+        check(lib.hs_depth_metrics(ptr(pred), _kind_of(pred, True), b, n, width, pred.stride(0), sc, psh, psw, ptr(target),
+                                   _kind_of(target, True), target.stride(0), tsh, tsw, *self._rule_args(b * n)), "hs_depth_metrics")
         if self.use_logvar:  # MeanSTDMedian: the lower median per sample, on the device
             lv = pred[:, 1]
             self._add_stds(torch.sqrt(torch.exp(lv if lv.dtype == torch.float64 else lv.float())).reshape(b, -1))

@@ -35,8 +35,8 @@ Differences from the reference, by construction:
 import numpy as np
 import torch
 
-from ._lib import HS_BF16, HS_F32, HS_PRED_LABELS, HS_PRED_ROWS16, check, lib, np_ptr, ptr, stream_ptr
-from ._sphere_args import _resolved as _device  # noqa: F401  (the evaluation modules import it from here)
+from ._lib import HS_PRED_LABELS, HS_PRED_ROWS16, check, lib, np_ptr, ptr, stream_ptr
+from ._sphere_args import _device_tensor, _kind_of, _label_class, _resolved as _device  # noqa: F401  (imported from here)
 from .projection import rot_grid
 
 MAX_CLASSES = 64
@@ -133,31 +133,36 @@ def hp_nearest_pix_idcs(nside, theta, phi):
 # ------------------------------------------------------------------ device side
 def _pred_args(pred, npix, device):
     """(pred_kind, n_classes, batch, (stride_b, stride_k, stride_p), tensor) of logits [B, K, Npix] or labels [B, Npix]."""
-    if not torch.is_tensor(pred) or pred.device != device:
-        raise RuntimeError(f"predictions must be a tensor on {device} (the evaluation kernels have no CPU path)")
+    _device_tensor(pred, "predictions", device, (torch.float32, torch.bfloat16, torch.uint8), RuntimeError)
     if pred.dtype == torch.uint8:
         if pred.dim() == 1:
             pred = pred[None]
         if pred.dim() != 2:
             raise ValueError(f"label predictions must be [B, Npix] uint8, got shape {tuple(pred.shape)}")
         kind, k, sb, sk, sp = HS_PRED_LABELS, None, pred.stride(0), 0, pred.stride(1)
-    elif pred.dtype in (torch.float32, torch.bfloat16):
+    else:
         if pred.dim() == 2:
             pred = pred[None]
         if pred.dim() != 3:
             raise ValueError(f"logits must be [B, K, Npix], got shape {tuple(pred.shape)}")
-        kind, k, sb, sk, sp = HS_F32 if pred.dtype == torch.float32 else HS_BF16, pred.shape[1], *pred.stride()
+        kind, k, sb, sk, sp = _kind_of(pred), pred.shape[1], *pred.stride()
         if not 1 <= k <= MAX_CLASSES:
             raise ValueError(f"the evaluation kernels support 1 .. {MAX_CLASSES} classes, got {k}")
-    else:
-        raise TypeError(f"predictions must be float32 / bfloat16 logits or uint8 class ids, got {pred.dtype}")
     if pred.shape[-1] != npix:
         raise ValueError(f"predictions cover {pred.shape[-1]} HEALPix pixels, expected {npix}")
-    if min(pred.stride()) < 0:
-        raise ValueError("predictions with negative strides are not supported")
     if kind != HS_PRED_LABELS and _rows16(pred, k):
         kind |= HS_PRED_ROWS16
     return kind, k, pred.shape[0], (sb, sk, sp), pred
+
+
+def _backproject_labels(pred, nearest, n_out, npix, background, out_shape, device):
+    """`hs_backproject_labels`: class ids uint8 [B, *out_shape] of logits [B, K, npix] (argmax as torch.max(logits, 1)) or uint8
+    labels [B, npix] read through nearest [n_out]; `background` where the table points outside [0, npix)."""
+    kind, k, b, (sb, sk, sp), pred = _pred_args(pred, npix, device)
+    out = torch.empty((b,) + tuple(out_shape), dtype=torch.uint8, device=device)
+    check(lib.hs_backproject_labels(ptr(pred), kind, b, npix, k or 1, sb, sk, sp, ptr(nearest), n_out, background, ptr(out),
+                                    stream_ptr(device)), "hs_backproject_labels")
+    return out
 
 
 def _rows16(logits, k):
@@ -198,9 +203,7 @@ class HPBackProjector:
         return self
 
     def _set_tables(self, theta, phi, nside, base_pix, s2_bkgd_class, device):
-        self.nside, self.base_pix, self.s2_bkgd_class = int(nside), int(base_pix), int(s2_bkgd_class)
-        if not 0 <= self.s2_bkgd_class <= 255:
-            raise ValueError("s2_bkgd_class must fit uint8")
+        self.nside, self.base_pix, self.s2_bkgd_class = int(nside), int(base_pix), _label_class(s2_bkgd_class)
         theta, phi = np.asarray(theta, dtype=np.float64), np.asarray(phi, dtype=np.float64)
         if theta.ndim != 2 or theta.shape != phi.shape:
             raise ValueError(f"theta and phi must share one [H', W'] shape, got {theta.shape} and {phi.shape}")
@@ -224,17 +227,12 @@ class HPBackProjector:
     def masks(self, pred):
         """Back-projected class ids uint8 [B, H', W'] from logits [B, K, Npix] (argmax as torch.max(logits, 1)) or uint8
         labels [B, Npix]; pixels outside the model's base pixels get s2_bkgd_class."""
-        kind, k, b, (sb, sk, sp), pred = _pred_args(pred, self.npix, self.device)
-        out = torch.empty((b,) + self.shape, dtype=torch.uint8, device=self.device)
-        check(lib.hs_backproject_labels(ptr(pred), kind, b, self.npix, k or 1, sb, sk, sp, ptr(self.nearest), self.n_out,
-                                        self.s2_bkgd_class, ptr(out), stream_ptr(self.device)), "hs_backproject_labels")
-        return out
+        return _backproject_labels(pred, self.nearest, self.n_out, self.npix, self.s2_bkgd_class, self.shape, self.device)
 
     def images(self, hp_img):
         """Bilinear back-projection of HEALPix images: uint8 [B, C, Npix] or [C, Npix] -> float64 [(B,) C, H', W'];
         pixels that interpolate from outside the model's base pixels read 255 there, as in the reference."""
-        if not torch.is_tensor(hp_img) or hp_img.dtype != torch.uint8 or hp_img.device != self.device:
-            raise TypeError(f"hp_img must be a uint8 tensor on {self.device}")
+        _device_tensor(hp_img, "hp_img", self.device, (torch.uint8,))
         if hp_img.dim() not in (2, 3) or hp_img.shape[-1] != self.npix:
             raise ValueError(f"hp_img must be [B, C, {self.npix}] or [C, {self.npix}], got {tuple(hp_img.shape)}")
         lead = hp_img.shape[:-1]
@@ -249,18 +247,15 @@ class HPBackProjector:
         (data/depth_estimation/project_depth_on_s2.py:370-386).  pred: fp32 / bf16 [B, C, Npix] (channel `channel` is read
         in place, any strides) or [B, Npix] -> float64 [B, H', W'].  The map is completed with NaN outside the model's base
         pixels and NaN propagates from any of the four pixels, a weight-0 one included (0 * NaN in the reference's sum)."""
-        if not torch.is_tensor(pred) or pred.device != self.device or pred.dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError(f"pred must be a float32 / bfloat16 tensor on {self.device}")
+        _device_tensor(pred, "pred", self.device, (torch.float32, torch.bfloat16))
         if pred.dim() == 3:
             pred = pred[:, channel]
         if pred.dim() != 2 or pred.shape[-1] != self.npix:
             raise ValueError(f"pred must be [B, C, {self.npix}] or [B, {self.npix}], got {tuple(pred.shape)}")
-        if min(pred.stride()) < 0:
-            raise ValueError("predictions with negative strides are not supported")
         out = torch.empty((pred.shape[0],) + self.shape, dtype=torch.float64, device=self.device)
-        check(lib.hs_backproject_depth(ptr(pred), HS_F32 if pred.dtype == torch.float32 else HS_BF16, pred.shape[0], self.npix,
-                                       pred.stride(0), pred.stride(1), ptr(self.idx), ptr(self.wgt), self.n_out, ptr(out),
-                                       stream_ptr(self.device)), "hs_backproject_depth")
+        check(lib.hs_backproject_depth(ptr(pred), _kind_of(pred), pred.shape[0], self.npix, pred.stride(0), pred.stride(1),
+                                       ptr(self.idx), ptr(self.wgt), self.n_out, ptr(out), stream_ptr(self.device)),
+              "hs_backproject_depth")
         return out
 
 
@@ -308,8 +303,7 @@ class SegConfusion:
                                    uncovered, ptr(self.confmat), ptr(self._bad), stream_ptr(self.device)), "hs_seg_confusion")
 
     def update(self, pred, target, projector=None, masked=False, camera=None, check=True):
-        if not torch.is_tensor(target) or target.dtype != torch.uint8 or target.device != self.device:
-            raise TypeError(f"target must be a uint8 tensor of class ids on {self.device}")
+        _device_tensor(target, "target (class ids)", self.device, (torch.uint8,))
         if torch.is_tensor(pred) and pred.dim() == (1 if pred.dtype == torch.uint8 else 2):
             pred = pred[None]
         if projector is None:

@@ -39,11 +39,10 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ._lib import HS_BF16, HS_F32, check, flat_zorder, lib, ptr, stream_ptr
-from .evaluation import HPBackProjector, _device, _pred_args
+from ._lib import check, flat_zorder, lib, ptr, stream_ptr
+from ._sphere_args import _device_tensor, _kind_of, _label_class
+from .evaluation import HPBackProjector, _backproject_labels, _device
 from .projection import hp_grid, project_s2_points_to_img
-
-_NO_CPU = "(the evaluation kernels have no CPU path)"
 
 
 # ------------------------------------------------------------------ host tables (once per calibration)
@@ -116,19 +115,11 @@ class _FlatSource:
         """Index into one prediction of model-plane pixel indices h * W + w."""
         return pixel if self._rows is None else self._rows[pixel]
 
-    def _check(self, pred, dtypes, what):
-        if not torch.is_tensor(pred) or pred.device != self.device or not pred.is_cuda:
-            raise RuntimeError(f"{what} must be a tensor on a GPU, the projector's device {self.device} {_NO_CPU}")
-        if pred.dtype not in dtypes:
-            raise TypeError(f"{what} must be {' / '.join(str(d).replace('torch.', '') for d in dtypes)}, got {pred.dtype}")
-        if min(pred.stride()) < 0:
-            raise ValueError("predictions with negative strides are not supported")
-
     def logits(self, pred):
         """The prediction as SegConfusion and the label kernels read it: logits [B, K, n_src] (a view: NCHW logits flattened,
         or the head rows [B, n_src, K] permuted, whose 16-byte rows then take the fast loads) or class ids uint8 [B, n_src]."""
         h, w = self.model_size
-        self._check(pred, (torch.float32, torch.bfloat16, torch.uint8), "predictions")
+        _device_tensor(pred, "predictions", self.device, (torch.float32, torch.bfloat16, torch.uint8), RuntimeError)
         ids = pred.dtype == torch.uint8
         if self.layout == "image":
             want = "[B, H, W]" if ids else "[B, K, H, W]"
@@ -143,7 +134,7 @@ class _FlatSource:
         """(pred, stride_b, stride_c, stride_p) of a depth prediction with at least `channels` channels (a channel-less one
         has one)."""
         h, w = self.model_size
-        self._check(pred, (torch.float32, torch.bfloat16), "pred")
+        _device_tensor(pred, "pred", self.device, (torch.float32, torch.bfloat16), RuntimeError)
         if self.layout == "image":
             if pred.dim() not in (3, 4) or tuple(pred.shape[-2:]) != (h, w):
                 raise ValueError(f"layout='image' predictions must be [B, C, H, W] or [B, H, W] with H x W = {h} x {w}, got "
@@ -177,9 +168,7 @@ class FlatToHPProjector(_FlatSource):
     def __init__(self, cal_info, nside, base_pix=8, rotate_pole=False, model_size=None, orig_size=None, padding=(0, 0, 0, 0),
                  layout="image", patch_size=None, tile=None, s2_bkgd_class=0, interpolation="nearest", device="cuda"):
         self.nside, self.base_pix, self.rotate_pole = int(nside), int(base_pix), bool(rotate_pole)
-        self.s2_bkgd_class = int(s2_bkgd_class)
-        if not 0 <= self.s2_bkgd_class <= 255:
-            raise ValueError("s2_bkgd_class must fit uint8")
+        self.s2_bkgd_class = _label_class(s2_bkgd_class)
         if interpolation not in ("nearest", "bilinear"):
             raise ValueError(f"interpolation must be 'nearest' or 'bilinear', got {interpolation!r}")
         self.interpolation = interpolation
@@ -261,12 +250,8 @@ class FlatToHPProjector(_FlatSource):
         """The projected class ids uint8 [B, Npix]: sample_mask(argmax, v, u, s2_bkgd_class) of the un-padded, resized
         prediction.  pred: logits (argmax as torch.max(logits, 1), taken at the sampled pixel only) or uint8 class ids, in the
         projector's layout."""
-        nearest = self.nearest
-        kind, k, b, (sb, sk, sp), pred = _pred_args(self.logits(pred), self.npix, self.device)
-        out = torch.empty((b, self.n_out), dtype=torch.uint8, device=self.device)
-        check(lib.hs_backproject_labels(ptr(pred), kind, b, self.npix, k or 1, sb, sk, sp, ptr(nearest), self.n_out,
-                                        self.s2_bkgd_class, ptr(out), stream_ptr(self.device)), "hs_backproject_labels")
-        return out
+        nearest = self.nearest  # (refuses a bilinear projector before anything looks at pred)
+        return _backproject_labels(self.logits(pred), nearest, self.n_out, self.npix, self.s2_bkgd_class, self.shape, self.device)
 
     def _tables(self):
         """(nearest, idx, wgt) pointers for the depth kernels: one of the two tables."""
@@ -280,8 +265,8 @@ class FlatToHPProjector(_FlatSource):
             pred = pred.select(1 if self.layout == "image" else 2, int(channel))
         out = torch.empty((pred.shape[0], self.n_out), dtype=torch.float32, device=self.device)
         near, idx, wgt = self._tables()
-        check(lib.hs_flat_depth_to_hp(ptr(pred), HS_F32 if pred.dtype == torch.float32 else HS_BF16, pred.shape[0], self.npix, sb, sp,
-                                      near, idx, wgt, self.n_out, ptr(out), stream_ptr(self.device)), "hs_flat_depth_to_hp")
+        check(lib.hs_flat_depth_to_hp(ptr(pred), _kind_of(pred), pred.shape[0], self.npix, sb, sp, near, idx, wgt, self.n_out, ptr(out),
+                                      stream_ptr(self.device)), "hs_flat_depth_to_hp")
         return out
 
 

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ._lib import HS_BF16, HS_ENSEMBLE_LOGIT, HS_ENSEMBLE_PROB, HS_F32, HS_PRED_ROWS16, check, lib, np_ptr, ptr, stream_ptr
-from ._sphere_args import _check_batch, _check_nside, _fills, _resolved, _rotation_batch
+from ._sphere_args import _check_batch, _check_nside, _kind_of, _label_class, _resolved, _rotation_batch
 from .evaluation import _pred_args
 from .hp_rotate import HPRotator
 from .projection import _pole_rotation
@@ -115,7 +115,7 @@ class HPRotationEnsemble:
     def __init__(self, nside, base_pix=8, cal_info=None, rotate_pole=False, s2_bkgd_class=0, mode="prob", min_weight=1e-3, device="cuda"):
         self._rotator = HPRotator(nside, base_pix, cal_info=cal_info, rotate_pole=rotate_pole, s2_bkgd_class=0, device=device)
         self.nside, self.base_pix, self.device = self._rotator.nside, self._rotator.base_pix, self._rotator.device
-        self.s2_bkgd_class, _ = _fills(s2_bkgd_class, None)
+        self.s2_bkgd_class = _label_class(s2_bkgd_class)
         if mode not in MODES:
             raise ValueError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
         self.mode, self.min_weight = mode, float(min_weight)
@@ -199,8 +199,7 @@ class HPRotationEnsemble:
                   "hs_hp_ensemble_add_seg")
         else:
             check(lib.hs_hp_ensemble_add_depth(self.nside, self.npix, ptr(mt), batch, ptr(pred),
-                                               HS_F32 if pred.dtype == torch.float32 else HS_BF16, pred.stride(0), pred.stride(1),
-                                               ptr(valid), accumulate, ptr(self._acc), ptr(self._wsum), stream_ptr(dev)),
+                                               _kind_of(pred), pred.stride(0), pred.stride(1), ptr(valid), accumulate, ptr(self._acc), ptr(self._wsum), stream_ptr(dev)),
                   "hs_hp_ensemble_add_depth")
         self._task, self._shape, self._members = task, (batch, k if task == "seg" else 0), self._members + 1
 

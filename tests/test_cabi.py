@@ -41,6 +41,18 @@ def test_every_declared_symbol_is_exported(L):
     assert sorted(L.EXPORTED_SYMBOLS) == declared
 
 
+def test_depth_sum_indices_match_the_header(L):
+    """depth_evaluation's NSUMS and S_* (read at every compute()) restate HS_DEPTH_NSUMS and HS_DS_* of the header."""
+    from heal_swin_amd import depth_evaluation as D
+
+    src = open(os.path.join(ROOT, "include", "healswin.h")).read()
+    defines = {name: int(value) for name, value in re.findall(r"^#define (HS_DS_[A-Z0-9_]+|HS_DEPTH_NSUMS) (\d+)\b", src, flags=re.M)}
+    mine = {name: getattr(D, name) for name in dir(D) if re.fullmatch(r"S_[A-Z0-9_]+", name)}
+    assert len(defines) == 15 and {"HS_DS_" + name[2:]: value for name, value in mine.items()} == {
+        k: v for k, v in defines.items() if k != "HS_DEPTH_NSUMS"}
+    assert D.NSUMS == defines["HS_DEPTH_NSUMS"] == D.S_RANGE + 2 * D.MAX_RANGES
+
+
 def test_version_and_status_strings(L):
     assert "gfx950" in L.version()
     assert L.lib.hs_status_string(0) == b"ok"

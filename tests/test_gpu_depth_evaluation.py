@@ -290,6 +290,17 @@ def test_backprojected_depth_metrics(D):
             m = full.astype(np.float64)[idx]
             want = ((m[0] * wgt[0] + m[1] * wgt[1]) + m[2] * wgt[2]) + m[3] * wgt[3]
             np.testing.assert_array_equal(out[i], want)
+    # the fill rule on a hand-built table (pixel 0 inside the map, pixels 1 and 2 with one tap outside, of weight 0 and 0.25):
+    # the map is completed with NaN, and 0 * NaN stays NaN
+    from test_gpu_evaluation import hand_table_projector, hand_table_ref
+    import heal_swin_amd.evaluation as E
+
+    h = hand_table_projector(E)
+    for dt in (torch.float32, torch.bfloat16):
+        t = torch.from_numpy(rng.uniform(1, 60, (2, h.npix)).astype(np.float32)).to(DEV).to(dt)
+        out = h.depth(t).cpu().numpy().reshape(2, 3)
+        assert np.isfinite(out[:, 0]).all() and np.isnan(out[:, 1:]).all()
+        np.testing.assert_array_equal(out, hand_table_ref(t.double().cpu().numpy(), h, np.nan))
     img = p.depth(torch.from_numpy(vals).to(DEV))
     assert torch.isnan(img).any() and torch.isfinite(img).any()
     target = torch.from_numpy(rng.uniform(1, 60, (2,) + p.shape).astype(np.float32)).to(DEV)

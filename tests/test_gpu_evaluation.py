@@ -4,6 +4,7 @@ torchmetrics' bincount, on hand-made inputs, on a model's own output and at full
 import os
 import socket
 import sys
+import types
 
 import numpy as np
 import pytest
@@ -67,6 +68,26 @@ def _logits(rng, b, k, npix, dtype, pad=None):
     return view, view.float().cpu().numpy()
 
 
+def hand_table_projector(E):
+    """An HPBackProjector over 16 HEALPix pixels with a hand-built table of 3 output pixels: pixel 0 interpolates from four
+    pixels of the map, pixel 1 has one tap outside [0, npix) (the first index past the map) with weight 0, pixel 2 one
+    (a negative index) with weight 0.25.  What a tap outside reads is the fill rule of each method."""
+    p = E.HPBackProjector.__new__(E.HPBackProjector)
+    p.nside, p.base_pix, p.s2_bkgd_class, p.device, p.shape = 4, 1, 0, torch.device(DEV, torch.cuda.current_device()), (1, 3)
+    idx = np.array([[3, 16, 7], [5, 1, -1], [9, 2, 0], [14, 4, 12]], dtype=np.int32).reshape(4, 1, 3)
+    wgt = np.array([[0.5, 0.0, 0.375], [0.125, 0.5, 0.25], [0.25, 0.25, 0.125], [0.125, 0.25, 0.25]]).reshape(4, 1, 3)
+    p.idx, p.wgt = torch.from_numpy(idx).to(DEV), torch.from_numpy(wgt).to(DEV)
+    return p
+
+
+def hand_table_ref(values, p, fill):
+    """((v0 w0 + v1 w1) + v2 w2) + v3 w3 per output pixel of float64 maps [n, npix] completed with `fill` outside."""
+    idx, w = p.idx.cpu().numpy().reshape(4, 3), p.wgt.cpu().numpy().reshape(4, 3)
+    inside = (idx >= 0) & (idx < p.npix)
+    v = np.where(inside, values[:, np.where(inside, idx, 0)], fill)
+    return ((v[:, 0] * w[0] + v[:, 1] * w[1]) + v[:, 2] * w[2]) + v[:, 3] * w[3]
+
+
 # ------------------------------------------------------------------ kernels against the restatements
 @pytest.fixture(scope="module")
 def small_proj(E):
@@ -125,6 +146,12 @@ def test_backproject_image_bit_exact(E, small_proj):
     ref = images_ref(img, p.idx.cpu().numpy().astype(np.int64), p.wgt.cpu().numpy(), 16)
     assert np.array_equal(out.cpu().numpy(), ref)
     assert torch.equal(p.images(torch.from_numpy(img[1]).to(DEV)), out[1])
+    # the fill rule on the hand-built table: a tap outside the map reads 255.0, so it adds exactly 255.0 * its weight
+    h = hand_table_projector(E)
+    img = np.concatenate([np.zeros((1, h.npix), dtype=np.uint8), rng.integers(0, 256, (2, h.npix), dtype=np.uint8)])
+    out = h.images(torch.from_numpy(img).to(DEV)).cpu().numpy().reshape(3, 3)
+    assert out[0].tolist() == [0.0, 255.0 * 0.0, 255.0 * 0.25]
+    assert np.array_equal(out, hand_table_ref(img.astype(np.float64), h, 255.0))
 
 
 # ------------------------------------------------------------------ confusion matrix
@@ -184,9 +211,40 @@ def test_confusion_raises_on_out_of_range(E):
         m.update(torch.zeros((1, 5, 100), device=DEV), torch.zeros((1, 100), dtype=torch.uint8, device=DEV)[:, :99])
 
 
-@pytest.mark.parametrize("masked", [False, True])
-def test_confusion_image_plane(E, small_proj, masked):
+# hand: (classes, prediction kind) through a hand-built nearest table of 65 image pixels, one full wave and one lane, whose
+# pixels 0 and 64 are uncovered: with masked=True the first lane of both waves has nothing to count, and in the second wave
+# no other lane has either (the contract of the waves' aggregated add, csrc/hs_histogram.h: wave_count_lead)
+HAND_TABLES = [pytest.param(masked, (k, kind), id=f"{masked}-hand65-k{k}-{kind}")
+               for masked in (False, True) for k in (1, 3, 64) for kind in ("labels", "f32", "bf16")]
+
+
+def _hand_table_case(rng, k, kind):
+    npix, n_out = 100, 65
+    nearest = rng.integers(0, npix, n_out).astype(np.int32)
+    nearest[[0, 64]] = npix
+    p = types.SimpleNamespace(nearest=torch.from_numpy(nearest).to(DEV), n_out=n_out, npix=npix, shape=(n_out,), s2_bkgd_class=k - 1,
+                              valid=torch.from_numpy(nearest < npix).to(DEV))
+    if kind == "labels":
+        lab = rng.integers(0, k, (3, npix), dtype=np.uint8)
+        return p, torch.from_numpy(lab).to(DEV), lab
+    view, ref_logits = _logits(rng, 3, k, npix, torch.float32 if kind == "f32" else torch.bfloat16)
+    return p, view, argmax_ref(ref_logits).astype(np.uint8)
+
+
+@pytest.mark.parametrize("masked,hand", [pytest.param(False, None, id="False"), pytest.param(True, None, id="True")] + HAND_TABLES)
+def test_confusion_image_plane(E, small_proj, masked, hand):
     rng = np.random.default_rng(6)
+    if hand is not None:
+        k, kind = hand
+        p, pred, labels = _hand_table_case(rng, k, kind)
+        tgt = torch.from_numpy(rng.integers(0, k, (3, p.n_out), dtype=np.uint8)).to(DEV)
+        m = E.SegConfusion(k, device=DEV)
+        m.update(pred, tgt, projector=p, masked=masked)
+        back = torch.from_numpy(np.concatenate([labels, np.full((3, 1), k - 1, dtype=np.uint8)], 1)).to(DEV)[:, p.nearest.long()]
+        keep = p.valid.expand_as(tgt) if masked else torch.ones_like(tgt, dtype=torch.bool)
+        ref = torch.bincount(tgt[keep].long() * k + back[keep].long(), minlength=k * k).reshape(k, k)
+        assert int(ref.sum()) == 3 * (63 if masked else 65) and torch.equal(m.confmat, ref)
+        return
     p = small_proj
     k = 12
     view, ref_logits = _logits(rng, 3, k, p.npix, torch.float32, pad=16)

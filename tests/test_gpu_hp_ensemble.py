@@ -150,6 +150,22 @@ def test_identity_only_is_the_plain_argmax_and_softmax(E, k, dtype, layout):
     print(f"K {k} {dtype} {layout}: worst |prob - softmax| {err:.3e}")
     assert err <= TOL_P
     assert (ens._wsum == 1).all()
+    # torch.max's rule on the rows a random draw does not hold, in the logit mode (the sums of one unrotated member are its
+    # logits): a NaN outside class 0 (where there is one), NaNs in two classes, two and all classes tied at the maximum, all -inf
+    hi = k - 1
+    v[:, hi, 0] = np.nan
+    v[:, [k // 2, hi], 1] = np.nan
+    v[:, :, 2] = -1.0
+    v[:, [k // 2, hi], 2] = 5.0
+    v[:, :, 3] = 0.5
+    v[:, :, 4] = -np.inf
+    pred = device_pred(v if dtype == "f32" else (bf16_bits(v).astype(np.uint32) << 16).view(np.float32), dtype, layout)
+    ens = E.HPRotationEnsemble(nside, base_pix, s2_bkgd_class=BKGD, mode="logit")
+    ens.add(pred)
+    preds = ens.finish()
+    want = torch.max(pred.float().cpu(), 1)[1]
+    assert want[0, :5].tolist() == [hi, k // 2, k // 2, 0, 0] == np.argmax(v[0, :, :5], 0).tolist()
+    assert torch.equal(preds.cpu(), want.to(torch.uint8))
 
 
 # ------------------------------------------------------------------ 5. coverage, guards, non-finite matrices
