@@ -72,6 +72,12 @@ class FisheyeCamera(ctypes.Structure):
                 ("poly_order", c_int), ("width", c_int), ("height", c_int)]
 
 
+class SurroundRig(ctypes.Structure):
+    """`hs_surround_rig` (include/healswin.h): the cameras hs_surround_to_hp fuses, with their weights' parameters."""
+    _fields_ = [("n_cameras", c_int), ("cam", FisheyeCamera * 8), ("max_theta", ctypes.c_double * 8), ("edge_feather", ctypes.c_double),
+                ("blend", c_int)]
+
+
 # name -> argtypes; every function returns int status unless listed in _OTHER_RESTYPE
 _SIGNATURES = {
     "hs_nest2ring": [c_int, c_ptr, c_ptr, c_i64],
@@ -134,6 +140,10 @@ _SIGNATURES = {
                      c_ptr],
     "hs_erp_to_hp_host": [c_int, c_i64, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr,
                           c_float],
+    "hs_surround_to_hp": [c_int, c_i64, ctypes.POINTER(SurroundRig), c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr,
+                          c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr, c_ptr],
+    "hs_surround_to_hp_host": [c_int, c_i64, ctypes.POINTER(SurroundRig), c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr,
+                               c_ptr, c_int, c_ptr, c_ptr, c_float, c_ptr],
     "hs_hp_ensemble_add_seg": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr],
     "hs_hp_ensemble_add_seg_host": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int, c_int, c_ptr, c_ptr],
     "hs_hp_ensemble_add_depth": [c_int, c_i64, c_ptr, c_int, c_ptr, c_int, c_i64, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr],

@@ -1,4 +1,4 @@
-"""Argument handling shared by the sphere data path (projection, depth_data, hp_rotate, erp, hp_ensemble) and the evaluation
+"""Argument handling shared by the sphere data path (projection, depth_data, hp_rotate, erp, surround, hp_ensemble) and the evaluation
 path (evaluation, depth_evaluation, flat_evaluation): plain functions, one copy of each.  Everything here refuses by shape,
 dtype and value first and touches the device last, so a malformed call fails the same way with and without a GPU.
 """
@@ -133,15 +133,19 @@ def _gather_planes(given, batch=None):
     return planes, squeezes.pop(), batch
 
 
-def _device_planes(planes, names, device, owner, npix, src_dims, host_path="no CPU path"):
-    """(the planes, contiguous; an output [..., npix] for each, its last `src_dims` dimensions replaced) after the device
-    refusals: GPU tensors on `device` (that of `owner`, "the rotator")."""
+def _on_device(planes, names, device, owner, host_path="no CPU path"):
+    """the planes, contiguous, after the device refusals: GPU tensors on `device` (that of `owner`, "the rotator")"""
     for t, what in zip(planes, names):
         if t is not None and not t.is_cuda:
             raise RuntimeError(f"{what} must be a GPU tensor: {owner} runs in the HIP kernel only ({host_path})")
         if t is not None and t.device != _resolved(device):
             raise RuntimeError(f"{what} is on {t.device}, {owner} on {device}")
-    planes = [None if t is None else t.contiguous() for t in planes]
+    return [None if t is None else t.contiguous() for t in planes]
+
+
+def _device_planes(planes, names, device, owner, npix, src_dims, host_path="no CPU path"):
+    """(the planes of _on_device; an output [..., npix] for each, its last `src_dims` dimensions replaced)"""
+    planes = _on_device(planes, names, device, owner, host_path)
     return planes, [None if t is None else torch.empty(t.shape[:-src_dims] + (npix,), dtype=t.dtype, device=t.device) for t in planes]
 
 

@@ -1,5 +1,5 @@
 // HEALPix geometry evaluated per pixel, one copy for the device kernels and the host loops that restate them
-// (projection_aug.hip, hp_rotate.hip, hp_ensemble.hip, hs_erp_device.h): the centre of a nested pixel as a unit vector, its
+// (projection_aug.hip, hp_rotate.hip, hp_ensemble.hip, hs_erp_device.h, hs_surround_device.h): the centre of a nested pixel as a unit vector, its
 // rotation d = M g with the finiteness test and the longitude reduction every resampler applies to d, HEALPix's get_interpol of
 // a rotated pixel centre in nested order, and the coverage test of a source index.  Every function is __host__ __device__ (the
 // macros are empty in a plain C++ translation unit), float64, without FMA contraction, so that the host entry point runs the

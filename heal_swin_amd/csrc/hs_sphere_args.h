@@ -1,5 +1,5 @@
 // Host-side argument checks and launch shapes shared by the entry points of the sphere data path (projection_aug.hip,
-// hp_rotate.hip, hp_ensemble.hip, erp_project.hip) and of the evaluation path (evaluation.hip, depth_eval.hip, flat_eval.hip): the
+// hp_rotate.hip, hp_ensemble.hip, erp_project.hip, surround_project.hip) and of the evaluation path (evaluation.hip, depth_eval.hip, flat_eval.hip): the
 // HEALPix grid a call names, its batch, pixel counts and element kinds, and the memory ranges it may not mix.  Host only: nothing
 // here is called from a kernel.  `who` prefixes the message.
 #pragma once

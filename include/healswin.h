@@ -874,6 +874,54 @@ int hs_erp_to_hp_host(int nside, int64_t npix, const double* rot, int batch, int
                       const float* depth, float* depth_out, float depth_fill);
 
 /* ------------------------------------------------------------------------------------------------
+ * Surround view: the frames of a rig of 1 .. 8 calibrated fisheye cameras fused onto one sphere (heal_swin_amd/surround.py:
+ * SurroundProjector; csrc/surround_project.hip, csrc/hs_surround_device.h).  WoodScape's rig is four cameras (FV, RV, MVL, MVR)
+ * with an extrinsic quaternion each; the reference projects one camera at a time, offline, and has no counterpart.  All cameras
+ * share one image size height x width.  Per (sample b, pixel p), in float64 without FMA and without a math-library call:
+ *   g = centre of nested pixel p as a unit vector; for every camera c = 0 .. n_cameras - 1 with present[b, c] != 0 ([dev]
+ *   u8[batch, n_cameras]; NULL: all present), d = M[b, c] g with M = rot[(b n_cameras + c) 9 ..] row-major ([dev]); a camera whose d
+ *   is not finite is skipped;
+ *   r = sqrt(dx^2 + dy^2), theta = atan2(r, dz), cos phi = dx / r, sin phi = dy / r (1, 0 where r == 0); theta > max_theta[c]: not
+ *   seen (max_theta is what keeps a non-monotonic polynomial from folding far directions back into the image);
+ *   rho, u, v as in hs_hp_rotated_coords; SEEN iff -1/2 <= u < width - 1/2 and -1/2 <= v < height - 1/2 (the nearest image pixel
+ *   lies inside the image);
+ *   weight w = a e: a = 1 - theta / max_theta[c]; m = min(u + 1/2, width - 1/2 - u, v + 1/2, height - 1/2 - v);
+ *   e = min(1, m / edge_feather) for edge_feather > 0, else 1.  The camera COUNTS iff it is seen and w > 0.
+ * The pixel is covered iff some camera counts; the winner is the counting camera of largest w, the lowest c among equal weights.
+ *   frame [dev] u8 or f32 [batch, n_cameras, channels, height, width] -> frame_out [batch, channels, npix]: per camera the bilinear
+ *     value at (v, u), i0 = floor v, j0 = floor u, the expression of hs_erp_to_hp, rows AND columns clamped to the image.  blend 0:
+ *     the winner's value.  blend 1: (sum_c w_c val_c) / (sum_c w_c) over the counting cameras in ascending c, un-rounded values.
+ *     u8: rint (half to even) clamped to [0, 255]; f32: the value cast.  Uncovered: 0 (u8), NaN (f32).
+ *   labels [dev] u8[batch, n_cameras, height, width] -> labels_out [batch, npix], depth [dev] f32[the same] -> depth_out: the
+ *     winner's pixel at row rint(v), column rint(u) (half to even), copied (depth as a word: NaN and inf keep their bits);
+ *     `background` / depth_fill where uncovered.  Depth is each camera's own range: the parallax between the cameras' centres is
+ *     ignored, the rig is treated as one viewpoint.
+ *   camera_out [dev] u8[batch, npix], nullable: the winner's index, 255 where uncovered.
+ * Every matrix and present byte a thread needs is read before its first store; no load is issued for a camera that does not
+ * count.  One launch, one thread per (sample, output pixel), no table, no LDS, no atomics; rig [host] is read during the call and
+ * travels by value (under 1 KB).  hs_surround_to_hp_host runs the same inline function in a plain loop, every pointer [host]: the
+ * kernel's oracle, equal bit for bit.
+ * HS_ERR_INVALID_ARG before any launch: nside no power of two or above 8192, npix not in {1 .. 12} nside^2, batch outside
+ * 1 .. 65535, a null rig or rot, n_cameras outside 1 .. 8, a camera with poly_order outside 1 .. 8 or a size other than height x
+ * width, max_theta outside (0, pi] or not finite, edge_feather negative or not finite, blend outside {0, 1}, height or width
+ * below 1 or height width >= 2^31, exactly one pointer of a pair, no plane, with a frame another frame_kind or channels outside
+ * 1 .. 16, background outside 0 .. 255, an output overlapping an input, the matrices or the present bytes.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hs_surround_rig {
+    int n_cameras;                              /* 1 .. 8 */
+    hs_fisheye_camera cam[8];                   /* the intrinsics; every width / height equals the call's */
+    double max_theta[8];                        /* radians, in (0, pi] */
+    double edge_feather;                        /* pixels, >= 0 */
+    int blend;                                  /* 0 winner, 1 feather */
+} hs_surround_rig;
+int hs_surround_to_hp(int nside, int64_t npix, const hs_surround_rig* rig, const double* rot, const uint8_t* present, int batch, int height,
+                      int width, const void* frame, int frame_kind, int channels, void* frame_out, const uint8_t* labels, uint8_t* labels_out,
+                      int background, const float* depth, float* depth_out, float depth_fill, uint8_t* camera_out, void* stream);
+int hs_surround_to_hp_host(int nside, int64_t npix, const hs_surround_rig* rig, const double* rot, const uint8_t* present, int batch,
+                           int height, int width, const void* frame, int frame_kind, int channels, void* frame_out, const uint8_t* labels,
+                           uint8_t* labels_out, int background, const float* depth, float* depth_out, float depth_fill, uint8_t* camera_out);
+
+/* ------------------------------------------------------------------------------------------------
  * Rotation ensembles at evaluation (heal_swin_amd/hp_ensemble.py: HPRotationEnsemble; csrc/hp_ensemble.hip): the way back of
  * hs_hp_rotate.  A sample is predicted under several rotations; each prediction, made on a frame that hs_hp_rotate rotated by M
  * (pixel q shows the scene at M g_q), is resampled onto the unrotated grid and accumulated there; the finish kernels average.
