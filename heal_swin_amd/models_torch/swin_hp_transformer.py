@@ -86,6 +86,11 @@ class DropPath(nn.Module):
         return x * rs.to(x.dtype).view((x.shape[0],) + (1,) * (x.dim() - 1))
 
 
+def _exact_gelu(act):
+    """The erf GELU the Mlp kernels compute (ops.mlp, ops.fused_mlp_block)?"""
+    return isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none"
+
+
 class Mlp(nn.Module):
     """fc1 -> GELU(erf) -> drop -> fc2 -> drop (ref :21-44)."""
 
@@ -99,8 +104,7 @@ class Mlp(nn.Module):
     def forward(self, x, apply_out_drop=True, residual_alias=False, residual=None):
         """residual_alias: also return an alias of x whose gradient is folded into fc1's input-gradient GEMM.
         residual: added to the output inside fc2's epilogue (ops.RESID_EPILOGUE path; no output dropout then)."""
-        exact_gelu = isinstance(self.act, nn.GELU) and getattr(self.act, "approximate", "none") == "none"
-        if exact_gelu and x.dtype in (torch.bfloat16, torch.float32) and x.is_cuda:
+        if _exact_gelu(self.act) and x.dtype in (torch.bfloat16, torch.float32) and x.is_cuda:
             # one autograd node: GELU (+ hidden dropout) ride on the GEMM epilogues, masks regenerated in backward (ops.MlpFn)
             out = ops.mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
                           drop_p=self.drop.p if self.training else 0.0, passthrough=residual_alias, residual=residual)
@@ -194,47 +198,51 @@ class WindowAttention(nn.Module):
         if residual is None and self.trainable_fused(x, window_size):
             # training forward of a stage whose qkv weights fit the LDS, branch without a norm in front (v2 placement): qkv ->
             # attention -> proj in ONE launch that also writes what the backward reads (ops.window_attn_module_train)
-            return ops.window_attn_module_train(x, None, None, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias,
-                                                self.bias(), self.head_scale(), idx, roll, labels, self.num_heads, window_size,
-                                                self.use_cos_attn, residual_alias=residual_alias)
+            return ops.window_attn_module_train(x, None, None, *self._module_args(window_size, idx, roll, labels),
+                                                residual_alias=residual_alias)
         if residual_alias:
             qkv, x_res = self.qkv.forward_passthrough(x)
         else:
             qkv = self.qkv(x)
-        o = ops.window_attn_core(qkv, self.bias(), self.head_scale(), idx, roll, labels, self.num_heads, window_size,
-                                 self.use_cos_attn, attn_drop=drop)
+        o = ops.window_attn_core(qkv, *self._core_args(window_size, idx, roll, labels), attn_drop=drop)
         if residual is not None:  # x + proj(o) from the proj product's epilogue (ops.RESID_EPILOGUE; no proj dropout on this path)
             return self.proj.forward_residual(o, residual)
         y = self.proj(o)
         y = self.proj_drop(y) if apply_proj_drop else y  # the caller fuses proj_drop into the next norm kernel
         return (y, x_res) if residual_alias else y
 
+    def _core_args(self, window_size, idx, roll, labels):
+        """What ops.window_attn_core takes behind qkv: bias, score scale, the shift and the shape."""
+        return self.bias(), self.head_scale(), idx, roll, labels, self.num_heads, window_size, self.use_cos_attn
+
+    def _module_args(self, window_size, idx, roll, labels):
+        """What both module kernels take behind x (and the norm in front): the two Linears' parameters, then the core's arguments."""
+        return (self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias) + self._core_args(window_size, idx, roll, labels)
+
+    def _module_fits(self, window_size):
+        """What both forms of the module kernel ask beside their own ops.*_ok: nothing stochastic inside the branch, the bias table's window."""
+        return (not (self.training and (self.attn_drop.p > 0 or self.proj_drop.p > 0)) and
+                (self.rel_pos_bias is None or window_size == self.window_size))
+
     def fusable(self, x, window_size):
         """The one-launch inference kernel applies: no gradient wanted, supported shape, nothing stochastic switched on."""
-        return (ops.window_attn_module_ok(x, self.num_heads, window_size) and
-                not (self.training and (self.attn_drop.p > 0 or self.proj_drop.p > 0)) and
-                (self.rel_pos_bias is None or window_size == self.window_size))
+        return ops.window_attn_module_ok(x, self.num_heads, window_size) and self._module_fits(window_size)
 
     def fused_module(self, x, window_size, idx, roll, labels, norm=None, residual=False):
         """[x +] proj(attention(qkv([norm](x)))) by `hs_window_attn_module_fwd` (inference only; ops.window_attn_module_ok)."""
-        return ops.window_attn_module(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, self.bias(),
-                                      self.head_scale(), idx, roll, labels, self.num_heads, window_size, self.use_cos_attn,
+        return ops.window_attn_module(x, *self._module_args(window_size, idx, roll, labels),
                                       ln_weight=None if norm is None else norm.weight, ln_bias=None if norm is None else norm.bias,
                                       residual=residual)
 
     def trainable_fused(self, x, window_size):
         """The one-launch TRAINING form applies (ops.window_attn_module_train_ok): gradients wanted, supported shape, nothing
         stochastic inside the branch."""
-        return (ops.window_attn_module_train_ok(x, self.num_heads, window_size) and
-                not (self.training and (self.attn_drop.p > 0 or self.proj_drop.p > 0)) and
-                (self.rel_pos_bias is None or window_size == self.window_size))
+        return ops.window_attn_module_train_ok(x, self.num_heads, window_size) and self._module_fits(window_size)
 
     def fused_module_train(self, x, window_size, idx, roll, labels, norm, norm2=None):
         """x + proj(attention(qkv(norm(x)))) by `hs_window_attn_module_fwd_train`, differentiable (ops.window_attn_module_train);
         with norm2 the same launch also applies the block's second LayerNorm: returns (norm2(x1), x1)."""
-        return ops.window_attn_module_train(x, norm.weight, norm.bias, self.qkv.weight, self.qkv.bias, self.proj.weight,
-                                            self.proj.bias, self.bias(), self.head_scale(), idx, roll, labels, self.num_heads,
-                                            window_size, self.use_cos_attn,
+        return ops.window_attn_module_train(x, norm.weight, norm.bias, *self._module_args(window_size, idx, roll, labels),
                                             norm2=None if norm2 is None else (norm2.weight, norm2.bias))
 
     def forward(self, x, mask=None):
@@ -318,14 +326,17 @@ class SwinTransformerBlock(nn.Module):
         return (f"dim={self.dim}, input_resolution={self.input_resolution}, num_heads={self.num_heads}, "
                 f"window_size={self.window_size}, shift_size={self.shift_size}, mlp_ratio={self.mlp_ratio}")
 
-    def _attention_branch(self, x, apply_proj_drop=True, residual_alias=False, residual=None):
+    def _shift_args(self, x):
+        """(idx, roll, labels) of the block's shift as the attention kernels take it."""
         if not self._shifted:
-            return self.attn.attend(x, self.window_size, None, 0, None, apply_proj_drop, residual_alias, residual)
+            return None, 0, None
         idx, _, labels = self.shifter.tables(x.device)
         if self._is_roll:  # modular offset instead of a table
-            return self.attn.attend(x, self.window_size, None, self.shift_size % x.shape[1], labels, apply_proj_drop, residual_alias,
-                                    residual)
-        return self.attn.attend(x, self.window_size, idx, 0, labels, apply_proj_drop, residual_alias, residual)
+            return None, self.shift_size % x.shape[1], labels
+        return idx, 0, labels
+
+    def _attention_branch(self, x, apply_proj_drop=True, residual_alias=False, residual=None):
+        return self.attn.attend(x, self.window_size, *self._shift_args(x), apply_proj_drop, residual_alias, residual)
 
     def _stochastic(self):
         """Any dropout / DropPath on the two residual branches active right now?"""
@@ -345,122 +356,127 @@ class SwinTransformerBlock(nn.Module):
         branch; else None."""
         m = self.mlp
         if not (isinstance(self.norm2, HSLayerNorm) and isinstance(m.fc1, HSLinear) and isinstance(m.fc2, HSLinear) and
-                isinstance(m.act, nn.GELU) and getattr(m.act, "approximate", "none") == "none" and
-                ops.fused_mlp_ok(x1, m.fc1.weight.shape[0]) and m.fc2.weight.shape[0] == self.dim):
+                _exact_gelu(m.act) and ops.fused_mlp_ok(x1, m.fc1.weight.shape[0]) and m.fc2.weight.shape[0] == self.dim):
             return None
         rs = self._path_scale(x1) if self.training else None
         dp = m.drop.p if self.training else 0.0
-        if rs is None and not dp:
+        # with either: Mlp.drop (both sites) and DropPath inside the launch, which the kernel has for the v2 placement
+        if (rs is None and not dp) or ops.fused_mlp_stochastic_ok(x1, post_norm):
             return ops.fused_mlp_block(x1, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                                       post_norm=post_norm)
-        if ops.fused_mlp_stochastic_ok(x1, post_norm):  # Mlp.drop (both sites) and DropPath inside the launch (v2 placement)
-            return ops.fused_mlp_block(x1, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                                       post_norm=True, row_scale=rs, drop_p=dp)
+                                       post_norm=post_norm, row_scale=rs, drop_p=dp)
         return None
+
+    def placement(self):
+        """Where the block's norms sit and how its residual adds are made -- the one rule forward() and the stages' block loop go by:
+        "v1" (norm in front of the branch, HIP norms): both adds deferred into the LayerNorm kernel that consumes the sum, or into
+        a product's epilogue (forward_deferred); "v2" (norm behind the branch, HIP norms): the two `x + norm(branch)` results are the
+        residual stream itself (forward_stream_v2 where the stream is compensated); None: foreign norm layers, the plain composition."""
+        if not self._hs_norms():
+            return None
+        return "v2" if self.use_v2_norm_placement else "v1"
 
     def can_defer(self):
         """v1 placement with the HIP norms: both residual adds -- together with the dropout / DropPath on the added branch --
         ride on the LayerNorm kernel that consumes the sum."""
-        return not self.use_v2_norm_placement and self._hs_norms()
-
-    def _shift_args(self, x):
-        if not self._shifted:
-            return None, 0, None
-        idx, _, labels = self.shifter.tables(x.device)
-        if self._is_roll:
-            return None, self.shift_size % x.shape[1], labels
-        return idx, 0, labels
+        return self.placement() == "v1"
 
     def forward_deferred(self, x, pending, x_lo=None, comp=None):
         """v1 block on the input `x (+ x_lo) + rs*drop(p)` for pending = (p, rs, drop_p) (or None); returns (x1, pending', x1_lo)
         with the block output = x1 (+ x1_lo) + rs'*drop(m) (ref :337-338 and :316 of the next block).  x_lo / x1_lo are the
         rounding remainders of the compensated residual stream (bf16 runs; None when off or not yet started)."""
-        train = self.training
         comp = (ops.COMP_RESIDUAL if comp is None else comp) and x.dtype == torch.bfloat16
-        if self.attn.fusable(x, self.window_size) and not (train and isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0):
+        if self.attn.fusable(x, self.window_size) and not self._stochastic():
             # no-grad forward: x1 = xs + proj(attn(qkv(norm1(xs)))) is ONE launch (norm1 as the kernel's prologue, the
             # residual add as its epilogue), xs = x + previous block's MLP branch
             xs = self.resolve_pending(x, pending)
-            idx, roll, labels = self._shift_args(xs)
-            x1 = self.attn.fused_module(xs, self.window_size, idx, roll, labels, norm=self.norm1, residual=True)
-            x2 = self._fused_mlp(x1)  # ... and x2 = x1 + mlp(norm2(x1)) as a second one
+            x1 = self.attn.fused_module(xs, self.window_size, *self._shift_args(xs), norm=self.norm1, residual=True)
+            return self._mlp_half(x1, alias=False)
+        sites = self._resid_sites(x, x_lo, comp)
+        if sites is not None and pending is None and self.attn.trainable_fused(x, self.window_size):
+            # norm1 -> qkv -> attention -> proj -> residual add in ONE launch that also writes what the backward reads ... and, with
+            # ops.FUSED_NORM2, the block's norm2 on the sum it has just formed
+            out = self.attn.fused_module_train(x, self.window_size, *self._shift_args(x), self.norm1,
+                                               norm2=self.norm2 if ops.FUSED_NORM2 else None)
+            n2, x1 = out if ops.FUSED_NORM2 else (None, out)
+            return self._mlp_half(x1, n2, sites[1])
+        proj_site, fc2_site = sites or (None, None)
+        xs, n1, xs_lo = self._norm1_step(x, pending, x_lo, comp)
+        x1, n2, x1_lo = self._attention_half(xs, n1, proj_site, xs_lo, comp)
+        return self._mlp_half(x1, n2, fc2_site, x1_lo)
+
+    def _resid_sites(self, x, x_lo, comp):
+        """(proj's, fc2's) ops.resid_site -- a residual add leaves its branch's last product's epilogue where that product runs on
+        hs_gemm_nt anyway (the HBM-bound shapes of stages 0-1) and, fc2's, where it runs in the library (long K: stages 1-3); the
+        norm behind it is then a plain LayerNorm whose second output is an alias of its input (the alias' gradient is added inside
+        the LayerNorm backward kernel) -- or None where both adds stay in the norm kernels whatever the shapes: ops.RESID_EPILOGUE
+        off, not bf16, a compensated stream, or dropout / DropPath on the branches, which only the norm kernel applies with the add."""
+        if not (ops.RESID_EPILOGUE and x.dtype == torch.bfloat16 and not comp and x_lo is None and not self._stochastic()):
+            return None
+        C, rows = self.dim, x.numel() // self.dim
+        return (ops.resid_site(C, C, x.dtype, m=rows, lib=False),
+                ops.resid_site(C, self.mlp.fc1.weight.shape[0], x.dtype, m=rows))
+
+    def _norm1_step(self, x, pending, x_lo=None, comp=False):
+        """(xs, norm1(xs), xs_lo) for xs (+ xs_lo) = x (+ x_lo) + rs*drop(p), pending = (p, rs, drop_p) or None (xs is x)."""
+        if pending is None:  # x feeds norm1 AND the residual add behind the branch: the alias keeps the two gradients in one kernel
+            n1, xs = ops.layer_norm_passthrough(x, self.norm1.weight, self.norm1.bias)
+            return xs, n1, x_lo
+        t, rs, dp = pending
+        if comp:
+            return ops.add_layer_norm_stream(x, x_lo, t, self.norm1.weight, self.norm1.bias, row_scale=rs, drop_p=dp)
+        xs, n1 = ops.add_layer_norm(x, t, self.norm1.weight, self.norm1.bias, row_scale=rs, drop_p=dp)
+        return xs, n1, x_lo
+
+    def _attention_half(self, xs, n1, site=None, xs_lo=None, comp=False):
+        """(x1, n2, x1_lo) for x1 (+ x1_lo) = xs (+ xs_lo) + rs*drop(attention branch of n1): the add in proj's epilogue (site; n2 is
+        then None, norm2 is the Mlp half's business), else in the norm2 kernel, which applies proj_drop and DropPath with it."""
+        if site is not None:
+            return self._attention_branch(n1, apply_proj_drop=False, residual=xs), None, None
+        a = self._attention_branch(n1, apply_proj_drop=False)
+        rs, dp = self._path_scale(xs), self.attn.proj_drop.p if self.training else 0.0
+        if comp:
+            return ops.add_layer_norm_stream(xs, xs_lo, a, self.norm2.weight, self.norm2.bias, row_scale=rs, drop_p=dp)
+        x1, n2 = ops.add_layer_norm(xs, a, self.norm2.weight, self.norm2.bias, row_scale=rs, drop_p=dp)
+        return x1, n2, None
+
+    def _mlp_half(self, x1, n2=None, site=None, x1_lo=None, alias=True):
+        """The v1 block's second half on x1 (+ x1_lo), n2 = norm2(x1) where the step before has made it: (x2, None, None) where the
+        add rides in a launch of this block -- the fused Mlp block (norm2 -> fc1 -> GELU -> fc2 -> add in one), or fc2's epilogue
+        (site) -- else (x1, the pending Mlp branch, x1_lo).  alias=False (the no-grad module path): norm2 as a plain LayerNorm."""
+        if n2 is None:
+            x2 = self._fused_mlp(x1)
             if x2 is not None:
                 return x2, None, None
-            m = self.mlp(self.norm2(x1), apply_out_drop=False)
-            return x1, (m, None, 0.0), None
-        if ops.RESID_EPILOGUE and x.dtype == torch.bfloat16 and not comp and x_lo is None and not self._stochastic():
-            # a residual add leaves its branch's last product's epilogue WHERE that product runs on hs_gemm_nt anyway (the
-            # HBM-bound shapes of stages 0-1); the norm behind it is then a plain LayerNorm whose second output is an alias of its
-            # input (the alias' gradient is added inside the LayerNorm backward kernel).  Elsewhere the add stays in the norm kernel.
-            C = self.dim
-            proj_own = ops.own_gemm_ok(_lib.HS_EPI_BIAS, C, C, x.dtype, m=x.numel() // C)
-            fc2_own = ops.own_gemm_ok(_lib.HS_EPI_BIAS, C, self.mlp.fc1.weight.shape[0], x.dtype, m=x.numel() // C)
-            # ... and where fc2 runs in the library (long K: stages 1-3), on the library product's C operand (ops.LIB_RESID)
-            fc2_res = fc2_own or ops.lib_resid_ok(C, self.mlp.fc1.weight.shape[0], x.dtype)
-            if pending is None and self.attn.trainable_fused(x, self.window_size):
-                # norm1 -> qkv -> attention -> proj -> residual add in ONE launch that also writes what the backward reads
-                idx, roll, labels = self._shift_args(x)
-                # ... and the block's norm2 on the sum it has just formed (ops.FUSED_NORM2)
-                if ops.FUSED_NORM2:
-                    n2, x1 = self.attn.fused_module_train(x, self.window_size, idx, roll, labels, self.norm1, norm2=self.norm2)
-                else:
-                    x1 = self.attn.fused_module_train(x, self.window_size, idx, roll, labels, self.norm1)
-                    x2 = self._fused_mlp(x1)  # norm2 -> fc1 -> GELU -> fc2 -> residual add in one launch as well
-                    if x2 is not None:
-                        return x2, None, None
-                    n2, x1 = ops.layer_norm_passthrough(x1, self.norm2.weight, self.norm2.bias)
-                if fc2_res:
-                    return self.mlp(n2, apply_out_drop=False, residual=x1), None, None
-                return x1, (self.mlp(n2, apply_out_drop=False), None, 0.0), None
-            if proj_own or fc2_res:
-                if pending is None:
-                    n1, xs = ops.layer_norm_passthrough(x, self.norm1.weight, self.norm1.bias)
-                else:
-                    t, rs, dp = pending
-                    xs, n1 = ops.add_layer_norm(x, t, self.norm1.weight, self.norm1.bias, row_scale=rs, drop_p=dp)
-                if proj_own:
-                    x1 = self._attention_branch(n1, apply_proj_drop=False, residual=xs)
-                    x2 = self._fused_mlp(x1)
-                    if x2 is not None:
-                        return x2, None, None
-                    n2, x1 = ops.layer_norm_passthrough(x1, self.norm2.weight, self.norm2.bias)
-                else:
-                    x1, n2 = ops.add_layer_norm(xs, self._attention_branch(n1, apply_proj_drop=False), self.norm2.weight, self.norm2.bias)
-                if fc2_res:
-                    return self.mlp(n2, apply_out_drop=False, residual=x1), None, None
-                return x1, (self.mlp(n2, apply_out_drop=False), None, 0.0), None
-        if pending is None:  # x feeds norm1 AND the residual add below: the alias keeps the two gradients in one kernel
-            n1, x = ops.layer_norm_passthrough(x, self.norm1.weight, self.norm1.bias)
-        elif comp:
-            t, rs, dp = pending
-            x, n1, x_lo = ops.add_layer_norm_stream(x, x_lo, t, self.norm1.weight, self.norm1.bias, row_scale=rs, drop_p=dp)
-        else:
-            t, rs, dp = pending
-            x, n1 = ops.add_layer_norm(x, t, self.norm1.weight, self.norm1.bias, row_scale=rs, drop_p=dp)
-        a = self._attention_branch(n1, apply_proj_drop=False)
-        if comp:
-            x1, n2, x1_lo = ops.add_layer_norm_stream(x, x_lo, a, self.norm2.weight, self.norm2.bias, row_scale=self._path_scale(x),
-                                                      drop_p=self.attn.proj_drop.p if train else 0.0)
-        else:
-            x1_lo = None
-            x1, n2 = ops.add_layer_norm(x, a, self.norm2.weight, self.norm2.bias, row_scale=self._path_scale(x),
-                                        drop_p=self.attn.proj_drop.p if train else 0.0)
+            n2, x1 = ops.layer_norm_passthrough(x1, self.norm2.weight, self.norm2.bias) if alias else (self.norm2(x1), x1)
+        if site is not None:
+            return self.mlp(n2, apply_out_drop=False, residual=x1), None, None
         m = self.mlp(n2, apply_out_drop=False)
-        return x1, (m, self._path_scale(x), self.mlp.drop.p if train else 0.0), x1_lo
-
-    def can_stream_v2(self):
-        """v2 placement with the HIP norms: the block's two `x + norm(branch)` results are the residual stream itself."""
-        return self.use_v2_norm_placement and self._hs_norms()
+        return x1, (m, self._path_scale(x1), self.mlp.drop.p if self.training else 0.0), x1_lo
 
     def forward_stream_v2(self, x, x_lo=None):
         """v2 block (ref :334-335) on the compensated stream x (+ x_lo); returns (x', x'_lo)."""
+        return self._v2_block(x, x_lo, stream=True)
+
+    def _v2_block(self, x, x_lo=None, stream=False):
+        """ref :334-335: x + drop_path(norm(branch(x))) for both branches, each sum fused into its norm kernel; returns (x', x'_lo).
+        stream: on the compensated stream x (+ x_lo), the sums by ops.layer_norm_stream, which also emits the remainder.
+        The residual operand is the alias handed back by the branch's first Linear: its gradient is then added inside that
+        Linear's input-gradient GEMM, not by a separate elementwise kernel."""
         train = self.training
         a, xr = self._attention_branch(x, apply_proj_drop=False, residual_alias=True)
-        x, x_lo = ops.layer_norm_stream(a, self.norm1.weight, self.norm1.bias, xr, res_lo=x_lo, row_scale=self._path_scale(x),
-                                        drop_p=self.attn.proj_drop.p if train else 0.0)
+        x, x_lo = self._v2_add_norm(self.norm1, a, xr, x_lo, stream, self.attn.proj_drop.p if train else 0.0)
+        x2 = None if stream else self._fused_mlp(x, post_norm=True)  # x + norm2(mlp(x)) in one launch where the Mlp is HBM-bound (stage 0)
+        if x2 is not None:
+            return x2, None
         m, xr = self.mlp(x, apply_out_drop=False, residual_alias=True)
-        return ops.layer_norm_stream(m, self.norm2.weight, self.norm2.bias, xr, res_lo=x_lo, row_scale=self._path_scale(x),
-                                     drop_p=self.mlp.drop.p if train else 0.0)
+        return self._v2_add_norm(self.norm2, m, xr, x_lo, stream, self.mlp.drop.p if train else 0.0)
+
+    def _v2_add_norm(self, norm, t, xr, x_lo, stream, drop_p):
+        """(xr (+ x_lo) + rs*norm(drop(t)), its remainder or None): one norm kernel either way, but not the same call."""
+        rs = self._path_scale(xr)
+        if stream:
+            return ops.layer_norm_stream(t, norm.weight, norm.bias, xr, res_lo=x_lo, row_scale=rs, drop_p=drop_p)
+        return norm(t, residual=xr, row_scale=rs, drop_p=drop_p), None
 
     @staticmethod
     def resolve_pending(x, pending):
@@ -480,19 +496,11 @@ class SwinTransformerBlock(nn.Module):
     def forward(self, x):
         B, N, C = x.shape
         assert N == self.n_tokens, f"expected {self.n_tokens} tokens, got {N}"
-        if self.can_defer():
+        place = self.placement()
+        if place == "v1":
             return self.resolve_pending(*self.forward_deferred(x, None)[:2])
-        train = self.training
-        if self.use_v2_norm_placement and self._hs_norms():  # ref :334-335: x + drop_path(norm(branch)), fused per branch
-            # the residual operand is the alias handed back by the branch's first Linear: its gradient is then added inside
-            # that Linear's input-gradient GEMM, not by a separate elementwise kernel
-            a, xr = self._attention_branch(x, apply_proj_drop=False, residual_alias=True)
-            x = self.norm1(a, residual=xr, row_scale=self._path_scale(x), drop_p=self.attn.proj_drop.p if train else 0.0)
-            x2 = self._fused_mlp(x, post_norm=True)  # x + norm2(mlp(x)) in one launch where the Mlp is HBM-bound (stage 0)
-            if x2 is not None:
-                return x2
-            m, xr = self.mlp(x, apply_out_drop=False, residual_alias=True)
-            return self.norm2(m, residual=xr, row_scale=self._path_scale(x), drop_p=self.mlp.drop.p if train else 0.0)
+        if place == "v2":
+            return self._v2_block(x)[0]
         if self.use_v2_norm_placement:  # foreign norm layers
             x = x + self.drop_path(self.norm1(self._attention_branch(x)))
             return x + self.drop_path(self.norm2(self.mlp(x)))
@@ -549,35 +557,39 @@ class FinalPatchExpand_X4(nn.Module):
 
 
 # ----------------------------------------------------------------------------- stages
-def _build_blocks(dim, input_resolution, depth, num_heads, window_size, base_pix, shift_size, shift_strategy, rel_pos_bias,
-                  mlp_ratio, qkv_bias, qk_scale, drop, attn_drop, drop_path, norm_layer, use_v2_norm_placement, use_cos_attn):
-    return nn.ModuleList([
-        SwinTransformerBlock(dim=dim, input_resolution=input_resolution, base_pix=base_pix, num_heads=num_heads,
-                             window_size=window_size, shift_size=shift_size if i % 2 else 0,  # odd blocks shifted (ref :516)
-                             shift_strategy=shift_strategy, rel_pos_bias=rel_pos_bias, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
-                             qk_scale=qk_scale, drop=drop, attn_drop=attn_drop,
-                             drop_path=drop_path[i] if isinstance(drop_path, list) else drop_path, norm_layer=norm_layer,
-                             use_v2_norm_placement=use_v2_norm_placement, use_cos_attn=use_cos_attn)
-        for i in range(depth)
-    ])
-
-
 class _Stage(nn.Module):
+    """What the four stage classes (encoder and decoder, HEALPix and flat) share: the constructor body, the block loop, forward."""
+
+    _resample = None  # name of the attribute that holds the stage's PatchMerging / PatchExpand (or None)
+
+    def _build(self, block_cls, dim, input_resolution, depth, use_checkpoint, shifts, drop_path, **block_kw):
+        """The stage's attributes and its `depth` blocks of block_cls(**block_kw): even blocks with shifts[0] (none), odd ones with
+        shifts[1] (ref :516); drop_path a rate or one per block."""
+        self.dim, self.input_resolution, self.depth, self.use_checkpoint = dim, input_resolution, depth, use_checkpoint
+        self.blocks = nn.ModuleList([
+            block_cls(dim=dim, input_resolution=input_resolution, shift_size=shifts[i % 2],
+                      drop_path=drop_path[i] if isinstance(drop_path, list) else drop_path, **block_kw)
+            for i in range(depth)
+        ])
+
+    def forward(self, x):
+        x = self._run_blocks(x)
+        resample = getattr(self, self._resample)
+        return x if resample is None else resample(x)
+
     def _run_blocks(self, x):
         pending = None  # second residual branch of the previous block, added inside the next block's first LayerNorm
         x_lo = None     # rounding remainder of the residual stream (compensated bf16 stream, ops.COMP_RESIDUAL); dropped at the
         #                 end of the stage (one ordinary rounding): every tensor that leaves a stage is a plain activation
         for blk in self.blocks:
-            if self.use_checkpoint:
-                x, pending, x_lo = SwinTransformerBlock.resolve_pending(x, pending), None, None
-                x = checkpoint.checkpoint(blk, x, use_reentrant=False)
-            elif blk.can_defer():
+            place = None if self.use_checkpoint else blk.placement()  # (a checkpointed block runs whole, through its forward)
+            if place == "v1":
                 x, pending, x_lo = blk.forward_deferred(x, pending, x_lo, comp=self._comp())
-            elif blk.can_stream_v2() and self._comp() and x.dtype == torch.bfloat16 and x.is_cuda:
+            elif place == "v2" and self._comp() and x.dtype == torch.bfloat16 and x.is_cuda:
                 x, x_lo = blk.forward_stream_v2(x, x_lo)
             else:
                 x, pending, x_lo = SwinTransformerBlock.resolve_pending(x, pending), None, None
-                x = blk(x)
+                x = checkpoint.checkpoint(blk, x, use_reentrant=False) if self.use_checkpoint else blk(x)
         return SwinTransformerBlock.resolve_pending(x, pending)
 
     comp_residual = None  # None: follow ops.COMP_RESIDUAL; True / False: this stage's own setting (see UnetDecoder)
@@ -592,37 +604,33 @@ class _Stage(nn.Module):
 class BasicLayer(_Stage):
     """Encoder stage: blocks + optional PatchMerging (ref :455-547)."""
 
+    _resample = "downsample"
+
     def __init__(self, dim, input_resolution, depth, num_heads, window_size, base_pix, shift_size, shift_strategy, rel_pos_bias,
                  mlp_ratio=4.0, qkv_bias=True, qk_scale=None, drop=0.0, attn_drop=0.0, drop_path=0.0, norm_layer=nn.LayerNorm,
                  downsample=None, use_checkpoint=False, use_v2_norm_placement=False, use_cos_attn=False):
         super().__init__()
-        self.dim, self.input_resolution, self.depth, self.use_checkpoint = dim, input_resolution, depth, use_checkpoint
-        self.blocks = _build_blocks(dim, input_resolution, depth, num_heads, window_size, base_pix, shift_size, shift_strategy,
-                                    rel_pos_bias, mlp_ratio, qkv_bias, qk_scale, drop, attn_drop, drop_path, norm_layer,
-                                    use_v2_norm_placement, use_cos_attn)
+        self._build(SwinTransformerBlock, dim, input_resolution, depth, use_checkpoint, (0, shift_size), drop_path,
+                    base_pix=base_pix, num_heads=num_heads, window_size=window_size, shift_strategy=shift_strategy,
+                    rel_pos_bias=rel_pos_bias, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop, attn_drop=attn_drop,
+                    norm_layer=norm_layer, use_v2_norm_placement=use_v2_norm_placement, use_cos_attn=use_cos_attn)
         self.downsample = downsample(dim=dim, norm_layer=norm_layer) if downsample is not None else None
-
-    def forward(self, x):
-        x = self._run_blocks(x)
-        return x if self.downsample is None else self.downsample(x)
 
 
 class BasicLayer_up(_Stage):
     """Decoder stage: blocks + optional PatchExpand (ref :561-653)."""
 
+    _resample = "upsample"
+
     def __init__(self, dim, input_resolution, depth, num_heads, window_size, base_pix, shift_size, shift_strategy, rel_pos_bias,
                  mlp_ratio=4.0, qkv_bias=True, qk_scale=None, drop=0.0, attn_drop=0.0, drop_path=0.0, norm_layer=nn.LayerNorm,
                  upsample=None, use_checkpoint=False, use_v2_norm_placement=False, use_cos_attn=False):
         super().__init__()
-        self.dim, self.input_resolution, self.depth, self.use_checkpoint = dim, input_resolution, depth, use_checkpoint
-        self.blocks = _build_blocks(dim, input_resolution, depth, num_heads, window_size, base_pix, shift_size, shift_strategy,
-                                    rel_pos_bias, mlp_ratio, qkv_bias, qk_scale, drop, attn_drop, drop_path, norm_layer,
-                                    use_v2_norm_placement, use_cos_attn)
+        self._build(SwinTransformerBlock, dim, input_resolution, depth, use_checkpoint, (0, shift_size), drop_path,
+                    base_pix=base_pix, num_heads=num_heads, window_size=window_size, shift_strategy=shift_strategy,
+                    rel_pos_bias=rel_pos_bias, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop, attn_drop=attn_drop,
+                    norm_layer=norm_layer, use_v2_norm_placement=use_v2_norm_placement, use_cos_attn=use_cos_attn)
         self.upsample = PatchExpand(dim=dim, dim_scale=2, norm_layer=norm_layer) if upsample is not None else None
-
-    def forward(self, x):
-        x = self._run_blocks(x)
-        return x if self.upsample is None else self.upsample(x)
 
 
 class PatchEmbed(nn.Module):
@@ -657,6 +665,15 @@ class PatchEmbed(nn.Module):
         return x if self.norm is None else self.norm(x)
 
 
+def _stage_kw(config, data_spec):
+    """What every stage of a model takes from its config; width, resolution, depth, heads, drop-path rates and resampling are its own."""
+    return dict(window_size=config.window_size, base_pix=data_spec.base_pix, shift_size=config.shift_size,
+                shift_strategy=config.shift_strategy, rel_pos_bias=config.rel_pos_bias, mlp_ratio=config.mlp_ratio,
+                qkv_bias=config.qkv_bias, qk_scale=config.qk_scale, use_cos_attn=config.use_cos_attn, drop=config.drop_rate,
+                attn_drop=config.attn_drop_rate, norm_layer=config.norm_layer, use_v2_norm_placement=config.use_v2_norm_placement,
+                use_checkpoint=config.use_checkpoint)
+
+
 class UnetDecoder(nn.Module):
     """Expanding path with skip connections (ref :704-791)."""
 
@@ -678,14 +695,8 @@ class UnetDecoder(nn.Module):
             self.concat_back_dim.append(HSLinear(2 * width, width))
             lo = sum(config.depths[:down])
             self.layers_up.append(BasicLayer_up(
-                dim=width, input_resolution=num_patches // (4 ** down), depth=config.depths[down],
-                num_heads=config.num_heads[down], window_size=config.window_size, base_pix=data_spec.base_pix,
-                shift_size=config.shift_size, shift_strategy=config.shift_strategy, rel_pos_bias=config.rel_pos_bias,
-                mlp_ratio=config.mlp_ratio, qkv_bias=config.qkv_bias, qk_scale=config.qk_scale,
-                use_cos_attn=config.use_cos_attn, drop=config.drop_rate, attn_drop=config.attn_drop_rate,
-                drop_path=dpr[lo:lo + config.depths[down]], norm_layer=config.norm_layer,
-                use_v2_norm_placement=config.use_v2_norm_placement, upsample=PatchExpand if down > 0 else None,
-                use_checkpoint=config.use_checkpoint))
+                dim=width, input_resolution=num_patches // (4 ** down), depth=config.depths[down], num_heads=config.num_heads[down],
+                drop_path=dpr[lo:lo + config.depths[down]], upsample=PatchExpand if down > 0 else None, **_stage_kw(config, data_spec)))
         if ops.COMP_RESIDUAL_LAST_STAGE and isinstance(self.layers_up[-1], BasicLayer_up):
             # the last decoder stage feeds the tail directly: its residual stream is carried as hi + lo (ops.COMP_RESIDUAL_LAST_STAGE)
             self.layers_up[-1].comp_residual = True
@@ -693,16 +704,20 @@ class UnetDecoder(nn.Module):
         self.output = nn.Conv1d(in_channels=config.embed_dim, out_channels=data_spec.f_out, kernel_size=1, bias=False)
         self.norm_up = _make_norm(config.norm_layer, config.embed_dim)
 
-    def forward(self, x, x_downsample, task=None):
-        """task: None for the logits, or the SegTask / DepthTask of decoder_tail, whose result is returned instead."""
-        dbg = self.config.dev_mode
+    def forward_up_features(self, x, x_downsample):
+        """The expanding path (also the flat model's, which keeps layers_up / concat_back_dim on itself as its reference does)."""
         for inx, layer_up in enumerate(self.layers_up):
             if inx > 0:
                 lin = self.concat_back_dim[inx]  # Linear(2c -> c) on cat([x, skip]) (ref :772-775), without the concat copy
                 x = ops.concat_linear(x, x_downsample[self.num_layers - 1 - inx], lin.weight, lin.bias)
             x = layer_up(x)
-            if dbg:
+            if self.config.dev_mode:
                 print(f"feature shape after decoder layer {inx}: {x.size()}")
+        return x
+
+    def forward(self, x, x_downsample, task=None):
+        """task: None for the logits, or the SegTask / DepthTask of decoder_tail, whose result is returned instead."""
+        x = self.forward_up_features(x, x_downsample)
         w = self.output.weight  # 1x1 conv without bias (ref :756-761) as the [f_out, C] matrix it is (ops.LinearFn)
         out = decoder_tail(self.norm_up, self.up, w, self.up.patch_size, x, task)
         return out if task is not None else out.float().transpose(1, 2)  # B, f_out, Npix (fp32)
@@ -899,13 +914,8 @@ class SwinHPTransformerSys(nn.Module):
             lo = sum(config.depths[:i])
             self.layers.append(BasicLayer(
                 dim=int(config.embed_dim * 2 ** i), input_resolution=num_patches // (4 ** i), depth=config.depths[i],
-                num_heads=config.num_heads[i], window_size=config.window_size, base_pix=data_spec.base_pix,
-                shift_size=config.shift_size, shift_strategy=config.shift_strategy, rel_pos_bias=config.rel_pos_bias,
-                mlp_ratio=config.mlp_ratio, qkv_bias=config.qkv_bias, qk_scale=config.qk_scale,
-                use_cos_attn=config.use_cos_attn, drop=config.drop_rate, attn_drop=config.attn_drop_rate,
-                drop_path=dpr[lo:lo + config.depths[i]], norm_layer=config.norm_layer,
-                use_v2_norm_placement=config.use_v2_norm_placement,
-                downsample=PatchMerging if i < L - 1 else None, use_checkpoint=config.use_checkpoint))
+                num_heads=config.num_heads[i], drop_path=dpr[lo:lo + config.depths[i]], downsample=PatchMerging if i < L - 1 else None,
+                **_stage_kw(config, data_spec)))
         # a reference config object names the reference's own UnetDecoder class: use this package's counterpart
         decoder_cls = config.decoder_class
         if getattr(decoder_cls, "__name__", "") == "UnetDecoder":
@@ -1009,7 +1019,16 @@ class SwinHPTransformerSys(nn.Module):
             x, x_downsample = self.forward_features(x.to(dt))
             return self.decoder(x, x_downsample) if task is None else self.decoder(x, x_downsample, task)
 
+    # Hooks of the forward_seg_* / forward_depth_* methods below; the flat model overrides them for its pixel order and images.
+    def _batch(self, x):
+        return x.shape[0]
+
+    def _as_image(self, preds):
+        """A step's predictions (or None) in the layout forward() gives: here the decoder's rows are the HEALPix pixels already."""
+        return preds
+
     def _seg_labels(self, x, labels):
+        """uint8 labels [B, Npix] in the decoder's row order, on x's device."""
         self._require_device(x)
         if labels.dtype != torch.uint8 and self.data_spec.f_out <= 255:
             # the kernels read one byte per pixel and ignore ids >= f_out.  A plain cast would WRAP (256 -> class 0, and
@@ -1021,8 +1040,9 @@ class SwinHPTransformerSys(nn.Module):
         return None if class_weights is None else class_weights.to(device=x.device, dtype=torch.float32).contiguous()
 
     def _depth_target(self, x, target):
+        """The fp32 target [B, Npix] in the decoder's row order, on x's device."""
         self._require_device(x)
-        assert target.shape == (x.shape[0], x.shape[-1]), "target [B, Npix]"
+        assert target.shape == (self._batch(x), x.shape[-1]), "target [B, Npix]"
         return target.to(device=x.device, dtype=torch.float32).contiguous()
 
     def forward(self, x):
@@ -1048,7 +1068,8 @@ class SwinHPTransformerSys(nn.Module):
         composed from the logits rows.  Labels >= f_out carry no weight and are not counted; the SegConfusion reports them at its
         next metric read (no synchronisation here, as update(..., check=False))."""
         check_step_confusion(confusion, self.data_spec.f_out)
-        return self._run(x, SegTask(self._seg_labels(x, labels), self._class_weights(x, class_weights), True, confusion, bool(return_preds)))
+        loss, preds = self._run(x, SegTask(self._seg_labels(x, labels), self._class_weights(x, class_weights), True, confusion, bool(return_preds)))
+        return loss, self._as_image(preds)
 
     def forward_depth_loss(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
         """get_depth_loss(cfg)(self(x), target) -- the depth caller's training step (training/loss_depth_regression.py) -- as ONE
@@ -1083,7 +1104,8 @@ class SwinHPTransformerSys(nn.Module):
         kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
         check_depth_channels(kind, self.data_spec.f_out)
         check_depth_step_args(transform, metrics, self.data_spec.f_out, x.device)
-        return self._run(x, DepthTask(self._depth_target(x, target), kind, delta, True, transform, metrics, bool(return_preds)))
+        loss, preds = self._run(x, DepthTask(self._depth_target(x, target), kind, delta, True, transform, metrics, bool(return_preds)))
+        return loss, self._as_image(preds)
 
     def _param_casts(self, dt):
         """bf16 copies of the Linear parameters, re-made in one multi-tensor kernel after each optimizer step (ops.ParamCastCache)."""

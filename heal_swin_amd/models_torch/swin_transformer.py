@@ -189,53 +189,36 @@ class FinalPatchExpand_X4(hp.FinalPatchExpand_X4):
         return self.norm(x.reshape(B, N * self.children_per_token, C // self.children_per_token))
 
 
-def _build_blocks(dim, input_resolution, depth, num_heads, window_size, shift_size, mlp_ratio, qkv_bias, qk_scale, drop, attn_drop,
-                  drop_path, norm_layer, use_masking, use_cos_attn, use_v2_norm_placement, use_rel_pos_bias, tile):
-    return nn.ModuleList([
-        SwinTransformerBlock(dim=dim, input_resolution=input_resolution, num_heads=num_heads, window_size=window_size,
-                             shift_size=[0, 0] if i % 2 == 0 else shift_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
-                             qk_scale=qk_scale, drop=drop, attn_drop=attn_drop,
-                             drop_path=drop_path[i] if isinstance(drop_path, list) else drop_path, norm_layer=norm_layer,
-                             use_masking=use_masking, use_cos_attn=use_cos_attn, use_v2_norm_placement=use_v2_norm_placement,
-                             use_rel_pos_bias=use_rel_pos_bias, tile=tile)
-        for i in range(depth)
-    ])
-
-
 class BasicLayer(hp._Stage):
     """Encoder stage: blocks + optional PatchMerging (ref :538-640)."""
+
+    _resample = "downsample"
 
     def __init__(self, dim, input_resolution, depth, num_heads, window_size, shift_size, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
                  drop=0.0, attn_drop=0.0, drop_path=0.0, norm_layer=nn.LayerNorm, downsample=None, use_checkpoint=False,
                  use_masking=True, use_cos_attn=False, use_v2_norm_placement=False, use_rel_pos_bias=True, tile=None):
         super().__init__()
-        self.dim, self.input_resolution, self.depth, self.use_checkpoint = dim, tuple(input_resolution), depth, use_checkpoint
-        self.blocks = _build_blocks(dim, input_resolution, depth, num_heads, window_size, shift_size, mlp_ratio, qkv_bias, qk_scale,
-                                    drop, attn_drop, drop_path, norm_layer, use_masking, use_cos_attn, use_v2_norm_placement,
-                                    use_rel_pos_bias, tile)
+        self._build(SwinTransformerBlock, dim, tuple(input_resolution), depth, use_checkpoint, ([0, 0], shift_size), drop_path,
+                    num_heads=num_heads, window_size=window_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop,
+                    attn_drop=attn_drop, norm_layer=norm_layer, use_masking=use_masking, use_cos_attn=use_cos_attn,
+                    use_v2_norm_placement=use_v2_norm_placement, use_rel_pos_bias=use_rel_pos_bias, tile=tile)
         self.downsample = downsample(input_resolution, dim=dim, norm_layer=norm_layer) if downsample is not None else None
-
-    def forward(self, x):
-        x = self._run_blocks(x)
-        return x if self.downsample is None else self.downsample(x)
 
 
 class BasicLayer_up(hp._Stage):
     """Decoder stage: blocks + optional PatchExpand (ref :643-736)."""
 
+    _resample = "upsample"
+
     def __init__(self, dim, input_resolution, depth, num_heads, window_size, shift_size, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
                  drop=0.0, attn_drop=0.0, drop_path=0.0, norm_layer=nn.LayerNorm, upsample=None, use_checkpoint=False,
                  use_masking=True, use_cos_attn=False, use_v2_norm_placement=False, use_rel_pos_bias=True, tile=None):
         super().__init__()
-        self.dim, self.input_resolution, self.depth, self.use_checkpoint = dim, tuple(input_resolution), depth, use_checkpoint
-        self.blocks = _build_blocks(dim, input_resolution, depth, num_heads, window_size, shift_size, mlp_ratio, qkv_bias, qk_scale,
-                                    drop, attn_drop, drop_path, norm_layer, use_masking, use_cos_attn, use_v2_norm_placement,
-                                    use_rel_pos_bias, tile)
+        self._build(SwinTransformerBlock, dim, tuple(input_resolution), depth, use_checkpoint, ([0, 0], shift_size), drop_path,
+                    num_heads=num_heads, window_size=window_size, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop,
+                    attn_drop=attn_drop, norm_layer=norm_layer, use_masking=use_masking, use_cos_attn=use_cos_attn,
+                    use_v2_norm_placement=use_v2_norm_placement, use_rel_pos_bias=use_rel_pos_bias, tile=tile)
         self.upsample = PatchExpand(input_resolution, dim=dim, dim_scale=2, norm_layer=norm_layer) if upsample is not None else None
-
-    def forward(self, x):
-        x = self._run_blocks(x)
-        return x if self.upsample is None else self.upsample(x)
 
 
 class PatchEmbed(nn.Module):
@@ -304,7 +287,14 @@ class SwinTransformerConfig:
 
 class SwinTransformerSys(hp.SwinHPTransformerSys):
     """Flat Swin-UNet: forward(x[B, f_in, H, W]) -> [B, f_out, H, W] fp32 logits (ref :823-1136).  Shares the HEALPix model's
-    runtime machinery (compute dtype, bf16 parameter-cast cache, batched attention parameters, forward_seg_loss)."""
+    runtime machinery (compute dtype, bf16 parameter-cast cache, batched attention parameters) and its forward_seg_loss /
+    forward_seg_step / forward_depth_loss / forward_depth_step, through the hooks _seg_labels, _depth_target, _as_image and _batch
+    (the callers: models_lightning/segmentation/model_lightning_swin.py, training/loss_depth_regression.py).  Here labels are
+    [B, H, W] integer class ids and target [B, H, W] depths -- or the flat_data.PixelRows FlatFrameTransform.masks / .depth(layout=
+    "rows") made, x then usually being the PatchRows of .frames(layout="rows") -- and a step's preds come back as images: uint8
+    [B, H, W] = self(x).argmax(1), fp32 [B, f_out, H, W] = self(x) with channel 0 in metres.  Neither the weighted / masked mean of
+    a loss nor the confusion counts and metric sums depend on the pixel order (median_std is the median over the sample's pixels in
+    either order), so in bf16 training the NCHW logits and the head rows are never written."""
 
     def __init__(self, config: SwinTransformerConfig, data_spec: DataSpec, **kwargs):
         nn.Module.__init__(self)
@@ -337,6 +327,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         if config.final_upsample != "expand_first":
             raise NotImplementedError(f"final_upsample={config.final_upsample!r}: only 'expand_first' is supported")
         self.tile = wh * mf  # side of the Z-order tiles at stage 0 (a window at the last stage)
+        self._image_layout = (H, W, ph, self.tile)  # what the layout kernels between image and pixel rows take
 
         self.patch_embed = PatchEmbed(config, data_spec=data_spec, tile=self.tile)
         num_patches = self.patch_embed.num_patches
@@ -403,13 +394,7 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
                 print(f"forward_features after layer {k}: {x.size()}")
         return self.norm(x), x_downsample
 
-    def forward_up_features(self, x, x_downsample):
-        for inx, layer_up in enumerate(self.layers_up):
-            if inx > 0:
-                lin = self.concat_back_dim[inx]  # Linear(2c -> c) on cat([x, skip]) (ref :1093-1094), without the concat copy
-                x = ops.concat_linear(x, x_downsample[self.num_layers - 1 - inx], lin.weight, lin.bias)
-            x = layer_up(x)
-        return x
+    forward_up_features = hp.UnetDecoder.forward_up_features  # (ref :1093-1094: the same loop over this model's own layers_up)
 
     def _run(self, x, task=None):
         self._require_device(x)
@@ -421,13 +406,11 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         with self._run_scope(dt):
             x, x_downsample = self.forward_features(x, dt)
             x = self.forward_up_features(x, x_downsample)
-            p = self.config.patch_size[0]
-            return hp.decoder_tail(self.norm_up, self.up, self.output.weight, p * p, x, task)
+            return hp.decoder_tail(self.norm_up, self.up, self.output.weight, self.up.children_per_token, x, task)
 
     def forward(self, x):
         rows = self._run(x)  # B, Npix, f_out logits rows (children of a token consecutive)
-        H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
-        return ops.flat_pixel_image(rows.float(), H, W, self.config.patch_size[0], self.tile)
+        return ops.flat_pixel_image(rows.float(), *self._image_layout)
 
     def forward_rows(self, x):
         """The head rows forward() lays out as NCHW, as the decoder tail leaves them: [B, H * W, f_out] fp32 (the padded rows
@@ -436,85 +419,42 @@ class SwinTransformerSys(hp.SwinHPTransformerSys):
         so that the NCHW tensor is never written; ops.flat_pixel_image(rows, H, W, p, self.tile) is forward(x)."""
         return self._run(x)
 
-    def forward_seg_loss(self, x, labels, class_weights=None):
-        """nn.CrossEntropyLoss(weight=class_weights)(self(x), labels.long()) as ONE call (models_lightning/segmentation/
-        model_lightning_swin.py): the labels are laid out in the logits rows' pixel order by a HIP kernel (ids outside [0, 254]
-        become 255, ignored), so that the loss rides on the decoder tail's kernels and, in bf16 training, the NCHW logits are never
-        written (the weighted mean does not depend on the pixel order).  labels: [B, H, W] integer class ids, or the flat_data.PixelRows
-        FlatFrameTransform.masks(layout="rows") made (x then usually being the PatchRows of .frames(layout="rows"))."""
-        return self._run(x, hp.SegTask(self._seg_labels(x, labels, "forward_seg_loss"), self._class_weights(x, class_weights)))
+    def _batch(self, x):
+        return x.batch if isinstance(x, PatchRows) else x.shape[0]
 
-    def forward_seg_step(self, x, labels, class_weights=None, confusion=None, return_preds=True):
-        """The flat segmentation caller's `shared_step` (models_lightning/segmentation/model_lightning_swin.py: argmax, weighted
-        cross-entropy, IoU / Accuracy on (preds, masks)) as ONE call, as SwinHPTransformerSys.forward_seg_step: (loss, preds) with
-        forward_seg_loss's loss and gradients, preds uint8 [B, H, W] = self(x).argmax(1) (None with return_preds=False; the class
-        ids of the pixel rows laid out as an image by a HIP kernel), and the (label, pred) counts added to `confusion` (an
-        evaluation.SegConfusion; the counts do not depend on the pixel order).  labels as forward_seg_loss takes them."""
-        hp.check_step_confusion(confusion, self.data_spec.f_out)
-        lab = self._seg_labels(x, labels, "forward_seg_step")
-        loss, preds = self._run(x, hp.SegTask(lab, self._class_weights(x, class_weights), True, confusion, bool(return_preds)))
-        if preds is not None:
-            H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
-            preds = ops.flat_label_image(preds.contiguous(), H, W, self.config.patch_size[0], self.tile)
-        return loss, preds
+    def _as_image(self, preds):
+        """A step's predictions in the rows' pixel order, laid out as images by a HIP kernel: class ids uint8 [B, H * W] -> [B, H, W];
+        fp32 [B, f_out, H * W] (any strides) -> [B, f_out, H, W], one channel at a time."""
+        if preds is None:
+            return None
+        if preds.dtype == torch.uint8:
+            return ops.flat_label_image(preds.contiguous(), *self._image_layout)
+        return torch.cat([ops.flat_pixel_image(preds[:, c].contiguous().unsqueeze(2), *self._image_layout) for c in range(preds.shape[1])], 1)
 
-    def forward_depth_loss(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, mask_background=False):
-        """get_depth_loss(cfg)(self(x), target) as ONE call (the flat depth baseline's training step, training/
-        loss_depth_regression.py): the target is laid out in the head rows' pixel order by a HIP kernel (fp32 copied bit for bit:
-        infinite and NaN depths survive), so that the loss rides on the decoder tail's kernels and, in bf16 training, the NCHW
-        prediction and the head rows are never written (the masked mean does not depend on the pixel order).  target: [B, H, W]
-        depths, or the flat_data.PixelRows FlatFrameTransform.depth(layout="rows") made; the other arguments as
-        SwinHPTransformerSys.forward_depth_loss."""
-        from ..losses import check_depth_channels, depth_loss_spec
-        kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
-        check_depth_channels(kind, self.data_spec.f_out)
-        return self._run(x, hp.DepthTask(self._depth_target(x, target), kind, delta))
-
-    def forward_depth_step(self, x, target, loss="l2", huber_delta=1.0, use_logvar=False, transform=None, metrics=None, return_preds=True,
-                           mask_background=False):
-        """The flat depth caller's `shared_step` (loss in the normalised space, unnormalize_and_retransform of prediction and target,
-        the metrics' update) as ONE call, as SwinHPTransformerSys.forward_depth_step: (loss, preds) with forward_depth_loss's loss
-        and gradients, preds fp32 [B, f_out, H, W] = self(x) with channel 0 in metres (None with return_preds=False; the pixel rows
-        laid out as an image by a HIP kernel), and `metrics` updated on (preds, target in metres) (the sums do not depend on the
-        pixel order; median_std is the median over the sample's pixels in either order).  target as forward_depth_loss takes it,
-        in the normalised space; the same stated deviation from the reference's loss."""
-        from ..losses import check_depth_channels, depth_loss_spec
-        kind, delta = depth_loss_spec(loss, huber_delta, use_logvar)
-        f_out = self.data_spec.f_out
-        check_depth_channels(kind, f_out)
-        hp.check_depth_step_args(transform, metrics, f_out, x.device)
-        tgt = self._depth_target(x, target)
-        loss, preds = self._run(x, hp.DepthTask(tgt, kind, delta, True, transform, metrics, bool(return_preds)))
-        if preds is not None:  # [B, f_out, Npix] in the rows' pixel order (any strides) -> the image, one channel at a time
-            H, W = self.data_spec.dim_in[0], self.data_spec.dim_in[1]
-            p = self.config.patch_size[0]
-            preds = torch.cat([ops.flat_pixel_image(preds[:, c].contiguous().unsqueeze(2), H, W, p, self.tile) for c in range(f_out)], 1)
-        return loss, preds
-
-    def _seg_labels(self, x, labels, caller):
-        """uint8 labels [B, H * W] in the logits rows' pixel order, on x's device (ids outside [0, 254] become 255)."""
+    def _seg_labels(self, x, labels):
+        """uint8 labels [B, H * W] in the logits rows' pixel order, on x's device, laid out by a HIP kernel (ids outside [0, 254]
+        become 255, ignored)."""
         self._require_device(x)
         if self.data_spec.f_out > 255:
-            raise NotImplementedError(f"{caller} supports at most 255 classes")
+            raise NotImplementedError("the flat model's segmentation loss and step support at most 255 classes")
         if isinstance(labels, PixelRows):
             return self._pixel_rows(labels, x, torch.uint8, "labels")
         if labels.dtype not in (torch.uint8, torch.int32, torch.int64):
             labels = labels.long()
-        return ops.flat_labels(labels.to(x.device), self.config.patch_size[0], self.tile)
+        return ops.flat_labels(labels.to(x.device), *self._image_layout[2:])
 
     def _depth_target(self, x, target):
-        """The fp32 target [B, H * W] in the head rows' pixel order, on x's device."""
+        """The fp32 target [B, H * W] in the head rows' pixel order, on x's device, laid out by a HIP kernel (fp32 copied bit for bit:
+        infinite and NaN depths survive)."""
         self._require_device(x)
         if isinstance(target, PixelRows):
             return self._pixel_rows(target, x, torch.float32, "target")
-        batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
-        assert tuple(target.shape) == (batch,) + tuple(self.data_spec.dim_in[:2]), "target [B, H, W]"
-        return ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), self.config.patch_size[0], self.tile)
+        assert tuple(target.shape) == (self._batch(x),) + tuple(self.data_spec.dim_in[:2]), "target [B, H, W]"
+        return ops.flat_depth_target(target.to(device=x.device, dtype=torch.float32), *self._image_layout[2:])
 
     def _pixel_rows(self, rows, x, dtype, what):
         """The tensor of a PixelRows built for this model, on x's device, one row set per sample of x."""
         t = rows.check_model(self)
-        batch = x.batch if isinstance(x, PatchRows) else x.shape[0]
-        if t.dtype != dtype or t.device != x.device or t.shape[0] != batch:
-            raise ValueError(f"{what} rows must be {dtype} [{batch}, H * W] on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if t.dtype != dtype or t.device != x.device or t.shape[0] != self._batch(x):
+            raise ValueError(f"{what} rows must be {dtype} [{self._batch(x)}, H * W] on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
         return t

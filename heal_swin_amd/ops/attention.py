@@ -7,7 +7,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
-from .runtime import RT, _cast_param, _f32, _require_gpu, _sink_buffer, _timed  # noqa: F401
+from .runtime import RT, _cast_param, _draw_seed, _f32, _require_gpu, _sink_buffer, _timed  # noqa: F401
 from .norm import LayerNormFn  # noqa: F401
 from .gemm import LinearFn  # noqa: F401
 
@@ -281,7 +281,7 @@ def window_attn_core(qkv, bias, head_scale, idx, roll, labels, num_heads, window
     """attn_drop > 0 applies the reference's dropout on the attention probabilities; `seed` (64-bit) fixes the mask,
     by default it is drawn from torch's CPU generator (so torch.manual_seed makes runs repeatable)."""
     if attn_drop > 0.0 and seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = _draw_seed()
     return WindowAttnCoreFn.apply(qkv, bias, head_scale, idx, roll, labels, num_heads, window_size, cosine,
                                   float(attn_drop), int(seed or 0))
 

@@ -305,11 +305,26 @@ LIB_RESID = os.environ.get("HS_LIB_RESID", "1") != "0"
 LIB_GEMM_CALLS = [0]  # hs_lib_gemm_nt launches so far (tests count them; profiles use the `lib fwd+res` tag)
 
 
-def lib_resid_ok(n, k, dtype, stochastic=False, comp=False):
-    """Whether a residual add may ride on the library product [*, k] x [n, k]^T (`_lib_linear_resid`): bf16, hipBLASLt reachable,
-    nothing stochastic on the branch, no compensated residual stream -- the restrictions of the hs_gemm_nt form of the same add."""
-    return bool(LIB_RESID and dtype == torch.bfloat16 and not stochastic and not comp and n % 8 == 0 and n >= 16 and k % 8 == 0 and
-                lib.hs_lib_gemm_supported())
+def lib_resid_ok(n, k, dtype):
+    """Whether a residual add may ride on the library product [*, k] x [n, k]^T (`_lib_linear_resid`): bf16, hipBLASLt reachable, the
+    shape restrictions of the hs_gemm_nt form of the same add."""
+    return bool(LIB_RESID and dtype == torch.bfloat16 and n % 8 == 0 and n >= 16 and k % 8 == 0 and lib.hs_lib_gemm_supported())
+
+
+def resid_site(n, k, dtype, m=None, lib=True, forced=False):
+    """Where the residual add behind a product [m, k] x [n, k]^T rides -- the ONE answer the block (which leaves the add out of the
+    next norm kernel where a product takes it) and the ops that run the product (MlpFn, LinearFn) both go by:
+        "own"  hs_gemm_nt's RESID epilogue, where that kernel runs the product anyway (own_gemm_ok, m included: stages 0-1);
+        "lib"  the library product's C operand (lib_resid_ok: the long-K fc2 of stages 1-3); lib=False: not on offer (proj);
+        None   no epilogue: the add stays in the norm kernel that follows.
+    forced: the caller holds a residual that HAS to be added by this product's op (ops.mlp(..., residual=) / ops.linear_residual called
+    outside the block's rule): hs_gemm_nt's epilogue wherever that kernel CAN run the product (own_gemm_legal), and None only where it
+    cannot -- the op then adds after the plain product."""
+    if own_gemm_ok(_lib.HS_EPI_BIAS, n, k, dtype, m=m):
+        return "own"
+    if lib and lib_resid_ok(n, k, dtype):
+        return "lib"
+    return "own" if forced and own_gemm_legal(n, k, dtype) else None
 
 
 def lib_gemm_nt(a2, w, bias, res2):
@@ -496,7 +511,8 @@ class LinearFn(torch.autograd.Function):
         elif residual is not None:
             # y = x W^T + b + residual: the add rides on the product's epilogue (one rounding); its gradient is dy itself
             assert not passthrough
-            if own_gemm_legal(n_out, k_in, x.dtype) and x.is_contiguous():
+            # (the block hands a residual over only where resid_site says "own"; a caller outside it is served wherever hs_gemm_nt can)
+            if resid_site(n_out, k_in, x.dtype, lib=False, forced=True) == "own" and x.is_contiguous():
                 res2 = residual.reshape(-1, n_out)
                 res2 = res2 if res2.is_contiguous() else res2.contiguous()
                 y = gemm_nt(x.reshape(-1, k_in), w, bias, _lib.HS_EPI_RESID, aux=res2)[0].view(x.shape[:-1] + (n_out,))

@@ -8,7 +8,7 @@ from .. import _lib
 from .._lib import check, lib, ptr, stream_ptr
 from .runtime import RT, _aligned, _cast_param, _defer_flag, _defer_keep, _draw_seed, _extras, _f32, _require_gpu, _timed  # noqa: F401
 from .norm import _norm_param_grads, _norm_param_result  # noqa: F401
-from .gemm import (_Split, _bf16x3_ok, _cast_param_t, _input_grad, _lib_linear, _lib_linear_resid, _lib_matmul, _param_grads, lib_resid_ok, _split_of, gemm_nt, own_gemm_legal, own_gemm_ok)  # noqa: F401
+from .gemm import (_Split, _bf16x3_ok, _cast_param_t, _input_grad, _lib_linear, _lib_linear_resid, _lib_matmul, _param_grads, _split_of, gemm_nt, own_gemm_ok, resid_site)  # noqa: F401
 
 
 class MlpFn(torch.autograd.Function):
@@ -50,12 +50,11 @@ class MlpFn(torch.autograd.Function):
         if residual is not None:
             res2 = residual.reshape(-1, w2.shape[0])
             res2 = res2 if res2.is_contiguous() else res2.contiguous()
-        # the add rides on fc2's epilogue: the LIBRARY's where the library runs this shape faster (long K; the same question
-        # forward_deferred asked, m included), else hs_gemm_nt's
-        lib_res = res2 is not None and lib_resid_ok(w2.shape[0], hid, dt) and not own_gemm_ok(_lib.HS_EPI_BIAS, w2.shape[0], hid, dt, m=x2.shape[0])
-        if lib_res:
+        # the add rides on fc2's epilogue: the LIBRARY's where the library runs this shape faster (long K), else hs_gemm_nt's
+        site = None if res2 is None else resid_site(w2.shape[0], hid, dt, m=x2.shape[0], forced=True)
+        if site == "lib":
             y = _lib_linear_resid(a, w2c, None if b2 is None else _cast_param(b2, dt), res2)
-        elif res2 is not None and own_gemm_legal(w2.shape[0], hid, dt):
+        elif site == "own":
             y = gemm_nt(a, w2c, b2, _lib.HS_EPI_RESID, aux=res2)[0]
         elif own_gemm_ok(_lib.HS_EPI_BIAS, w2.shape[0], hid, dt):
             y = gemm_nt(a, w2c, b2)[0]
@@ -64,7 +63,7 @@ class MlpFn(torch.autograd.Function):
             a3 = _split_of(a)
             if isinstance(a, _Split):
                 a = None
-        if res2 is not None and not lib_res and not own_gemm_legal(w2.shape[0], hid, dt):
+        if res2 is not None and site is None:
             y = y + res2
         assert not isinstance(a, _Split)
         # (fp32 runs: the weight gradients read the bf16x3 splits the forward products made, not x2 / a themselves)

@@ -95,8 +95,14 @@ def test_refusals(supported):
     finally:
         L.lib.hs_lib_gemm_set_supported(1)
     assert L.lib.hs_lib_gemm_supported() == 1 and ops.lib_resid_ok(96, 384, torch.bfloat16)
-    assert not ops.lib_resid_ok(96, 384, torch.float32) and not ops.lib_resid_ok(96, 384, torch.bfloat16, stochastic=True)
-    assert not ops.lib_resid_ok(96, 384, torch.bfloat16, comp=True) and not ops.lib_resid_ok(92, 384, torch.bfloat16)
+    assert not ops.lib_resid_ok(96, 384, torch.float32) and not ops.lib_resid_ok(92, 384, torch.bfloat16)
+    # nothing stochastic on the branch, no compensated residual stream: the block asks ops.resid_site for neither
+    from heal_swin_amd.models_torch import swin_hp_transformer as M
+    x = torch.zeros(2, 512, 96, device=DEV, dtype=torch.bfloat16)
+    plain = M.SwinTransformerBlock(96, 512, 8, 3, window_size=64).train()
+    assert plain._resid_sites(x, None, False) is not None
+    assert M.SwinTransformerBlock(96, 512, 8, 3, window_size=64, drop_path=0.1).train()._resid_sites(x, None, False) is None
+    assert plain._resid_sites(x, None, True) is None and plain._resid_sites(x, x, False) is None
 
 
 def test_pick_is_stable_and_every_candidate_can_be_pinned(supported):

@@ -185,6 +185,55 @@ def test_own_gemm_policy_class_rule_tuner_picks_and_overrides(monkeypatch):
     assert ops.own_gemm_ok(_lib.HS_EPI_BIAS, 128, 128, bf, m=1 << 20) and ops.own_gemm_ok(_lib.HS_EPI_BIAS, 512, 2048, bf)
 
 
+def test_resid_site_table(monkeypatch):
+    """ops.resid_site, the one answer to where a product's residual add rides: (n, k, m, dtype, switches) -> the site the block is told
+    (fc2: library on offer; proj: lib=False) and the site an op that already holds a residual takes (forced).  Every row is also what
+    the two rules this function replaced both give, spelt here from own_gemm_ok / own_gemm_legal / lib_resid_ok: the block's (own
+    product, else for fc2 the library's, else the norm kernel) and MlpFn's (library where lib_resid_ok and not own, else hs_gemm_nt
+    where legal, else an add behind the plain product)."""
+    import types
+
+    import torch
+    from heal_swin_amd import _lib, ops
+    from heal_swin_amd.ops import gemm as G
+    bf, f32 = torch.bfloat16, torch.float32
+    monkeypatch.setattr(G, "GEMM_TUNER", G.GemmTuner())
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)  # no trial: the class rule answers, m or not
+    monkeypatch.setattr(G, "lib", types.SimpleNamespace(hs_lib_gemm_supported=lambda: 1))  # the library reachable, as on the device
+    base = dict(OWN_GEMM="auto", LIB_RESID=True, prefer=False)
+    table = [  # n, k, m, dtype, switches, fc2's site, proj's site, forced site
+        (512, 128, 4096, bf, {}, "own", "own", "own"),          # k <= 128
+        (512, 136, 4096, bf, {}, "lib", None, "lib"),
+        (128, 2048, 4096, bf, {}, "own", "own", "own"),         # n <= 128
+        (136, 2048, 4096, bf, {}, "lib", None, "lib"),
+        (256, 256, 4096, bf, {}, "own", "own", "own"),          # n <= 256 and k <= 256
+        (256, 264, 4096, bf, {}, "lib", None, "lib"),
+        (264, 256, 4096, bf, {}, "lib", None, "lib"),
+        (512, 2048, None, bf, {}, "lib", None, "lib"),          # (no m: as the call of an op outside the block)
+        (128, 512, 4096, f32, {}, None, None, None),            # fp32: the add stays in the norm kernel / behind the product
+        (132, 512, 4096, bf, {}, None, None, None),             # n % 8: neither kernel stores such rows
+        (128, 512, 4096, bf, dict(OWN_GEMM="0"), "lib", None, "lib"),
+        (128, 512, 4096, bf, dict(OWN_GEMM="0", LIB_RESID=False), None, None, None),
+        (512, 2048, 4096, bf, dict(OWN_GEMM="1"), "own", "own", "own"),
+        (512, 2048, 4096, bf, dict(LIB_RESID=False), None, None, "own"),  # a residual already handed over: hs_gemm_nt can, so it does
+        (128, 512, 4096, bf, dict(LIB_RESID=False), "own", "own", "own"),
+        (512, 2048, 4096, bf, dict(prefer=True), "own", "own", "own"),
+    ]
+    for n, k, m, dt, sw, fc2, proj, forced in table:
+        sw = dict(base, **sw)
+        monkeypatch.setattr(ops, "OWN_GEMM", sw["OWN_GEMM"])
+        monkeypatch.setattr(ops, "LIB_RESID", sw["LIB_RESID"])
+        monkeypatch.setattr(ops.RT, "prefer_own_gemm", sw["prefer"])
+        row = (n, k, m, dt, sw)
+        assert ops.resid_site(n, k, dt, m=m) == fc2, row
+        assert ops.resid_site(n, k, dt, m=m, lib=False) == proj, row
+        assert ops.resid_site(n, k, dt, m=m, forced=True) == forced, row
+        own, legal, lib = ops.own_gemm_ok(_lib.HS_EPI_BIAS, n, k, dt, m=m), ops.own_gemm_legal(n, k, dt), ops.lib_resid_ok(n, k, dt)
+        assert ("own" if own else "lib" if lib else None) == fc2 and ("own" if own else None) == proj, row   # the block's rule
+        assert ("lib" if (lib and not own) else "own" if legal else None) == forced, row                      # MlpFn's, given a residual
+        assert fc2 is None or forced == fc2, row  # where the block hands a residual over, the op puts it where the block thinks it is
+
+
 def test_weight_split_cache_hits_for_fresh_views_and_follows_the_weight_epoch(monkeypatch):
     """callers pass `w.view(n, k)` / `w.reshape(...)` -- a new tensor object per call -- so an identity check
     never hit.  The entry is now found by the storage it views; it is dropped when the parameter's version OR the weight epoch
